@@ -10,7 +10,14 @@ images (latents 4x64x64, 9-channel UNet input) per GPU, `output_type="latent"` (
 says).  Inputs are resident in HBM before the timed region.  Weak scaling: every rank denoises its own 4 images; the
 only collective is the start-up RCCL broadcast of the packed UNet parameters from rank 0.
 
-Prints ONE JSON line on rank 0 (fields: see the driver contract; plus `roofline` and `cpu_baseline`).
+Prints ONE JSON line on rank 0 (fields: see the driver contract).  A plain run does only what that line's headline
+figure needs: set up, warm up, time the K steps, print.  `--full` adds the measurements that take runs of their own:
+the live `roofline` / `hbm_roofline` / per-family replays of one denoising step and the `cpu_baseline` of the CPU
+oracle (each can still be dropped with `--no-roofline` / `--no-cpu-baseline`).
+
+`--dump-outputs DIR` writes what the last timed step returned (the latents a caller of the pipeline receives, float32)
+as DIR/latents.npy (N > 1: DIR/latents_rank<r>.npy per rank); the inputs and the random-init weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -420,13 +427,21 @@ def main():
     ap.add_argument("--scheduler", default=None, choices=["ddim", "dpm", "pndm", "unipc"],
                     help="default: ddim (v1, controlnet), dpm = DPM-Solver++(2M) (v2)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--dump-launches", default=None, help="write per-launch HIP-event timings of one step (JSON)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the live roofline / per-family replays and the CPU-oracle baseline (runs of their own)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline replays")
+    ap.add_argument("--dump-launches", default=None, help="--full: write per-launch HIP-event timings of one step (JSON)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the output of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--dist-timeout", type=float, default=180.0,
                     help="N > 1: seconds the RCCL rendezvous / first all-reduce / weight broadcast may take before the "
                          "rank exits with a message naming the stuck stage (0 = wait forever)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_launches and not (args.full and not args.no_roofline):
+        ap.error("--dump-launches is part of the roofline pass: add --full (and drop --no-roofline)")
 
     rank, world, local = ppdist.init_from_env(timeout_s=args.dist_timeout)
     if world != args.gpus:
@@ -458,6 +473,11 @@ def main():
     dt = ppdist.max_over_ranks(time.perf_counter() - t0, device)
     assert torch.isfinite(out).all()
     pipe._loop.flush_faults()          # (in-kernel split-K combines: no share left uncombined in any of the timed calls)
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "latents" if world == 1 else f"latents_rank{rank}"
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), out.detach().float().cpu().numpy())
 
     if rank == 0:
         images = args.per_gpu * world * args.steps
@@ -500,13 +520,13 @@ def main():
             "launches_per_denoise_step": len(pipe._loop.program.calls) if getattr(pipe, "_loop", None) is not None
             and getattr(pipe._loop, "program", None) is not None else None,
         }
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 headline = (args.config, args.latent, args.per_gpu, args.dtype) == ("v1", 64, 4, "bf16")
                 res.update(roofline_report(pipe, args.dump_launches, profile_matches=headline))
             except Exception as e:      # the headline number must still be reported: keep the one JSON line
                 res["roofline"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline()
             except Exception as e:

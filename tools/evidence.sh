@@ -25,10 +25,10 @@ python tools/prof_summary.py $DB $O/kernel_stats.txt "bench.py --steps 1 --warmu
 python tools/step_timeline.py $DB $O/step_timeline.txt > /dev/null 2>&1; rm -rf $O/prof; head -14 $O/kernel_stats.txt; head -3 $O/step_timeline.txt
 bash tools/hbm_traffic.sh > $O/hbm.log 2>&1; cp gpurun_out/hbm_traffic.json $O/hbm_traffic.json
 cp $O/kernel_stats.txt profiles/${R}_kernel_stats.txt; cp $O/hbm_traffic.json profiles/${R}_hbm_traffic.json     # (bench.py reads these)
-timeout 400 python bench.py --dump-launches $O/launches.json > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 1800 $O/bench.json
-timeout 600 python bench.py --config v2 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_v2.json 2>> $O/bench.err; echo "v2 rc=$?"
-timeout 600 python bench.py --config controlnet --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_controlnet.json 2>> $O/bench.err; echo "cn rc=$?"
-timeout 900 python bench.py --config v2 --latent 128 --per-gpu 2 --denoise-steps 30 --dtype fp16 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_config5.json 2>> $O/bench.err; echo "cfg5 rc=$?"
+timeout 400 python bench.py --full --dump-launches $O/launches.json > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 1800 $O/bench.json
+timeout 600 python bench.py --full --config v2 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_v2.json 2>> $O/bench.err; echo "v2 rc=$?"
+timeout 600 python bench.py --full --config controlnet --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_controlnet.json 2>> $O/bench.err; echo "cn rc=$?"
+timeout 900 python bench.py --full --config v2 --latent 128 --per-gpu 2 --denoise-steps 30 --dtype fp16 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_config5.json 2>> $O/bench.err; echo "cfg5 rc=$?"
 timeout 600 python bench.py --dtype fp16 --steps 2 --warmup 1 --no-cpu-baseline --no-roofline > $O/bench_fp16.json 2>> $O/bench.err; echo "fp16 rc=$?"
 for f in bench bench_v2 bench_controlnet bench_config5 bench_fp16; do python - <<PY
 import json
