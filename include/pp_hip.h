@@ -66,6 +66,18 @@ const char* pp_last_error(void);
  *            (weights/bias pre-interleaved by the host), out has N/2 columns.
  *            out_vt != NULL: columns >= vt_col0 are written TRANSPOSED per batch item to out_vt[b][n - vt_col0][row in batch]
  *            (V^T for attention), the others to `out`.
+ * Aliasing:  res1 MAY be the same tensor as `out` (same pointer, ldres1 == ldo: `out += (acc + bias) * scale`, in place) on a
+ *            launch with the plain 16-bit epilogue: act = PP_ACT_NONE, no out_f32 / out_vt / row_stats_out / ln_stats /
+ *            gn_next_out, out_dup_rows == 0 and res1_wrap_rows == 0.  On every path such a launch can take -- the staged
+ *            single-pass epilogue, the register-staged one, split-K with the separate combine launch (the GEMM kernel then
+ *            touches only the fp32 slabs), split-K with the in-kernel share combine -- element [m][n] is read as res1 and
+ *            then written as `out` by ONE thread, each exactly once, and no workgroup reads `out` as an operand, so no
+ *            other thread can observe the element in between.  out_dup_rows stores rows a second thread's res1 read may
+ *            cover and res1_wrap_rows reads rows another thread writes: not in place.  Any other overlap of res1 / res2 /
+ *            x* / w with `out` (offset pointers, different row strides, res2 -- kept for the skip tensors, which never
+ *            alias) is undefined.  Several ControlNets use it: the zero convs of every net but the first accumulate into the
+ *            first net's residual buffers (MultiControlNetModel, /root/reference/powerpaint/pipelines/
+ *            pipeline_PowerPaint_ControlNet.py:306,1686-1694 -- diffusers sums the nets' residuals in separate adds).
  */
 #define PP_X_PLAIN 0
 #define PP_X_CONV3X3 1

@@ -86,8 +86,9 @@ def groupnorm_apply_acc(x: torch.Tensor, acc: torch.Tensor, gamma, beta, eps: fl
 def gemm(x: torch.Tensor, w: torch.Tensor, bias=None, x2=None, res1=None, res2=None, scale: float = 1.0, act: int = 0,
          rowvec=None, rows_per_batch: int = 0, out_f32: bool = False, vt_col0: int = 0, tile: int = 0,
          splitk: int = 0, row_stats: bool = False, ln_stats=None, ln_colsum=None, ln_dim: int = 0,
-         ln_eps: float = 1e-5, gn=None, res1_wrap: int = 0, fuse_combine: bool = False):
+         ln_eps: float = 1e-5, gn=None, res1_wrap: int = 0, fuse_combine: bool = False, out=None):
     """x [M,K1] (+ x2 [M,K2]) bf16, w [N,K1+K2] bf16 -> out [M,N] (or [M,N/2] for GEGLU; (out, vt) when vt_col0).
+    out: write into this contiguous tensor instead of a new one; it may BE res1 (in place, include/pp_hip.h "Aliasing").
     w [nb, N, K]: one matrix per batch item of rows_per_batch rows (PPGemmArgs.w_batch_stride); with act =
     L.PP_ACT_SOFTMAX80 bias / ln_colsum may then be [nb, N] as well (vec_batch_stride).
     res1_wrap: res1 holds that many rows only, row m adds res1[m mod res1_wrap] (PPGemmArgs.res1_wrap_rows).
@@ -113,7 +114,10 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias=None, x2=None, res1=None, res2=N
     a.res2, a.ldres2 = _p(res2), (res2.stride(0) if res2 is not None else N)
     a.scale, a.act = scale, act
     n_out = N // 2 if act == L.PP_ACT_GEGLU else (vt_col0 if vt_col0 else N)
-    out = torch.empty(M, n_out, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty(M, n_out, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    elif tuple(out.shape) != (M, n_out) or not out.is_contiguous() or out.dtype != (torch.float32 if out_f32 else x.dtype):
+        raise L.PPError(f"gemm: `out` must be a contiguous [{M}, {n_out}] tensor of the output format")
     a.dtype = L.dtype_code(x.dtype)
     a.out, a.ldo, a.out_f32 = _p(out), n_out, int(out_f32)
     vt = None

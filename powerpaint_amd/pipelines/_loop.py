@@ -18,6 +18,16 @@ pipeline_PowerPaint_Brushnet_CA.py:1384-1466, pipeline_PowerPaint_ControlNet.py:
                                                                        pp_cfg_sched_step when nothing behind it reads the counter)
 No host->device traffic and no host synchronisation inside the loop.
 
+Several ControlNets (`side` = a MultiControlNetModel, pipeline_PowerPaint_ControlNet.py:306,1678-1694): one runtime per
+net (own arena, time-embedding table, hoisted control-image embedding, twin-prefix decision); the step is
+    head(net 0) .. head(net N-1), head(UNet), plan(net 0) .. plan(net N-1), plan(UNet), scheduler step
+in ONE stream and ONE hipGraph without parallel branches.  The UNet is wired to net 0's residual buffers; the first net
+of a step overwrites them and every later net's zero convs add to them in place through the GEMM epilogue's `res1`
+(NetRuntime.chained_step_calls): the sum costs no launch and no pass over the residuals.  A net whose guidance window
+is closed at a step (scale 0) is LEFT OUT of that step: one program and one captured graph per distinct set of active
+nets (at most 2 N + 1 over a schedule), cached on the loop and picked per step on the host; with no net active the
+set's program zeroes the shared buffers itself.
+
 A scheduler that is not one of powerpaint_amd.schedulers (any object with the diffusers protocol the reference
 duck-types: `.timesteps`, `.scale_model_input`, `.step(...)`, e.g. the UniPC scheduler app.py:197 installs) is driven
 the way the reference drives it: the network part of the step is the same captured launch program, the guidance
@@ -39,7 +49,11 @@ def _temb_table_enabled() -> bool:
 
 
 class DenoiseLoop:
-    def __init__(self, unet, scheduler, side=None, side_kind: Optional[str] = None):
+    def __init__(self, unet, scheduler, side=None, side_kind: Optional[str] = None, keep_closed_nets: bool = False):
+        """keep_closed_nets (several ControlNets only): a net whose guidance window is closed at a step still runs, with
+        scale 0, as the reference does (pipeline_PowerPaint_ControlNet.py:1651-1658,1681) -- same numbers, a wasted forward
+        pass; the default leaves its launches out of the step.  The pipelines never pass it; it exists to check the
+        skipping against."""
         self.foreign = not isinstance(scheduler, _SchedulerBase)     # duck-typed scheduler: its own .step per step
         if self.foreign and not (hasattr(scheduler, "step") and hasattr(scheduler, "timesteps")):
             raise TypeError(f"{type(scheduler).__name__} does not follow the scheduler protocol (.timesteps, .step)")
@@ -49,6 +63,10 @@ class DenoiseLoop:
         self.graph = None
         self._key = None
         self._graph_scale = None      # side-branch conditioning scale baked into the captured graph (by-value kernel arg)
+        self.keep_closed_nets = bool(keep_closed_nets)
+        self._multi = False           # several ControlNets bound: per-active-set programs (self._sets) instead of ONE program
+        self._sets = {}
+        self.side_rts = []
         self.latents: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------
@@ -99,11 +117,25 @@ class DenoiseLoop:
                 b_.copy_(v.to(device=dev, dtype=torch.float32).reshape(b_.shape))
             self._blend = bufs
         half = bool(guess_mode and do_cfg)                   # side network on the conditional half only
+        # a MultiControlNetModel: its nets, one runtime each.  A wrapper around ONE net is that net (same plans, same launches)
+        nets = list(self.side.nets) if (self.side is not None and hasattr(self.side, "nets")) else None
+        multi = nets is not None and len(nets) > 1
+        side = self.side if (nets is None or multi) else nets[0]
+        if nets is not None:
+            if self.side_kind != "controlnet":
+                raise L.PPError("a list of side networks is a ControlNet feature (MultiControlNetModel)")
+            controlnet_cond = self.side.per_net(controlnet_cond, "controlnet_cond")
+            if not isinstance(side_scale, (list, tuple)):
+                side_scale = [side_scale] * len(nets)
+            side_scale = [float(v) for v in self.side.per_net(side_scale, "side_scale")]
+            if not multi:
+                controlnet_cond, side_scale = controlnet_cond[0], side_scale[0]
+        side0 = nets[0] if multi else side                   # (global_pool_conditions is read from nets[0], :1536-1540)
         # guess mode scales the n residuals by logspace(-1, 0, n) * conditioning_scale (BrushNet_CA.py:905-928): `run`'s
         # per-step scalar schedule is expanded the same way before it is patched into the zero-conv launches
         self._guess_ramp = None
-        if guess_mode and self.side is not None and not self.side.config.global_pool_conditions:
-            self._guess_ramp = [float(v) for v in torch.logspace(-1, 0, len(self.side.net._zero_conv_specs()))]
+        if guess_mode and side is not None and not side0.config.global_pool_conditions:
+            self._guess_ramp = [float(v) for v in torch.logspace(-1, 0, len(side0.net._zero_conv_specs()))]
         Bs = B if half else Be
 
         # The CFG pair is built here, as `cat([latents] * 2)` (pipeline_PowerPaint.py:990): where every other network input
@@ -120,25 +152,36 @@ class DenoiseLoop:
         twin_u = bool(do_cfg) and all(halves_equal(t) for t, _ in static_inputs)
         # (the control image goes through set_cond, which accepts the un-duplicated batch as well and copies it to both halves)
         twin_s = bool(do_cfg) and not half and all(halves_equal(t) for t, _ in side_static_inputs) and \
-            (self.side_kind == "brushnet" or halves_equal(controlnet_cond))
+            (self.side_kind == "brushnet" or multi or halves_equal(controlnet_cond))
         if self.side is not None and self.side.dtype != self.unet.dtype:
             # the fused loop hands the side network's residuals to the UNet as raw NHWC arena pointers, every step: both
             # must store activations in the same 16-bit format (the reference raises a dtype error in its first conv)
             raise L.PPError(f"{type(self.side).__name__} computes in {self.side.dtype}, the UNet in {self.unet.dtype}: "
                             f"load both with the same torch_dtype")
-        if self.side is not None:
+        side_rts = []
+        if side is not None:
             if half and prompt_embeds_side.shape[0] == Be:
                 prompt_embeds_side = prompt_embeds_side.chunk(2)[1]
             if self.side_kind == "brushnet":
-                side_rt = self.side.prepare((Bs, Cl, h, w), prompt_embeds_side, side_scale, bool(guess_mode), half,
-                                            twin=twin_s)
-                d, m, u = self.side.outputs()
+                side_rt = side.prepare((Bs, Cl, h, w), prompt_embeds_side, side_scale, bool(guess_mode), half,
+                                       twin=twin_s)
+                d, m, u = side.outputs()
                 wiring_kw = dict(down_block_add_samples=d, mid_block_add_sample=m, up_block_add_samples=u)
-            else:
-                side_rt = self.side.prepare((Bs, Cl, h, w), prompt_embeds_side, controlnet_cond, side_scale,
-                                            bool(guess_mode), half, twin=twin_s)
-                d, m = self.side.outputs()
+            elif multi:
+                # every net on the same latents and prompt, its own control image (and so its own twin-prefix decision);
+                # the UNet reads net 0's residual buffers, which every step's program fills with the sum
+                side_rts = [net.prepare((Bs, Cl, h, w), prompt_embeds_side, cond, sc, bool(guess_mode), half,
+                                        twin=twin_s and halves_equal(cond))
+                            for net, cond, sc in zip(nets, controlnet_cond, side_scale)]
+                d, m = nets[0].outputs()
                 wiring_kw = dict(down_block_additional_residuals=d, mid_block_additional_residual=m)
+            else:
+                side_rt = side.prepare((Bs, Cl, h, w), prompt_embeds_side, controlnet_cond, side_scale,
+                                       bool(guess_mode), half, twin=twin_s)
+                d, m = side.outputs()
+                wiring_kw = dict(down_block_additional_residuals=d, mid_block_additional_residual=m)
+        if side_rt is not None:
+            side_rts = [side_rt]
         rt = self.unet.prepare((Be, cin, h, w), prompt_embeds, twin=twin_u, **wiring_kw)
         # one-time (per call) static channels of the UNet / side inputs
         rt.load_input(list(static_inputs))
@@ -163,9 +206,9 @@ class DenoiseLoop:
             mp = sch.m_prev(lat) if sch.kind >= 1 else None  # scheduler state: DPM m_{i-1}; PNDM history + saved sample
             kind, src = sch.kind, lat
         key = (tuple(latents_shape), bool(do_cfg), bool(guess_mode), self._eta > 0, float(guidance_scale), id(rt.step_plan),
-               id(side_rt.step_plan) if side_rt is not None else None, kind, ts.data_ptr(), step.data_ptr(),
+               tuple(id(r.step_plan) for r in side_rts) if side_rts else None, kind, ts.data_ptr(), step.data_ptr(),
                0 if self.foreign else sch.coef_table().data_ptr(), mp.data_ptr() if mp is not None else 0, src.data_ptr(),
-               _temb_table_enabled(), int(ts.numel()), tuple(getattr(r.net.params, "version", 0) for r in (rt, side_rt) if r is not None),
+               _temb_table_enabled(), int(ts.numel()), tuple(getattr(r.net.params, "version", 0) for r in [rt] + side_rts),
                tuple(b.data_ptr() for b in self._blend) if self._blend is not None else None,
                sch.renoise_table().data_ptr() if (self._blend is not None and not self.foreign) else 0)
         if key == self._key and self.program is not None:
@@ -179,10 +222,14 @@ class DenoiseLoop:
         mod = B if do_cfg else 0
         self._temb = {}
         head_skip = {}
-        for r in ([side_rt] if side_rt is not None else []) + [rt]:
+        heads, skips = {}, {}           # per runtime: the launches at the head of the step; the plan indices they replace
+        tail = prog                     # (the launches behind the networks are collected in `prog`, the networks come in front)
+        for r in side_rts + [rt]:
+            prog = Plan()
+            heads[id(r)] = prog.calls
             info = self._temb_split(r, ts) if _temb_table_enabled() else None
             x = r.lay["x_in"]
-            nb_r = Bs if r is side_rt else Be                    # (guess mode: the side network takes `latents` as is)
+            nb_r = Be if r is rt else Bs                    # (guess mode: the side network takes `latents` as is)
             calls = r.step_plan.calls
             zero = calls[0] if (calls and calls[0][2] == "zero_u64") else None
             if info is not None and zero is not None:
@@ -201,11 +248,10 @@ class DenoiseLoop:
                 prog.add("step_select_t", lib.pp_step_select_t, ts.data_ptr(), step.data_ptr(), r.lay["t_dev"])
             prog.add("nchw_to_nhwc", lib.pp_nchw_to_nhwc, src.data_ptr(), 0, nb_r, Cl, hw, mod if nb_r != B else 0,
                      x.ptr, x.C, 0, L.dtype_code(r.net.dtype))
-        for r in ([side_rt] if side_rt is not None else []) + [rt]:
+        prog = tail
+        for r in side_rts + [rt]:
             skip = set(self._temb[id(r)]["idx"]) if id(r) in self._temb else set()
-            skip |= head_skip.get(id(r), set())
-            prog.calls += [c for i, c in enumerate(r.step_plan.calls) if i not in skip]
-            prog.flops += r.step_plan.flops
+            skips[id(r)] = skip | head_skip.get(id(r), set())
         # (round 5) where pp_cfg_sched_step is the step's last reader of the counter, its last block moves the counter on:
         # no pp_step_advance launch behind it
         fold_advance = (not self.foreign) and not (self._eta > 0) and self._blend is None and \
@@ -227,9 +273,22 @@ class DenoiseLoop:
                          sch.renoise_table().data_ptr(), step.data_ptr(), B, Cl, hw)
         if not fold_advance:
             prog.add("step_advance", lib.pp_step_advance, step.data_ptr())
-        self.program = prog
-        self.rt, self.side_rt = rt, side_rt
+        self.rt, self.side_rt, self.side_rts = rt, side_rt, side_rts
         self.graph = None
+        self._multi, self._sets = multi, {}
+        if multi:
+            self._parts = dict(heads=heads, skips=skips, tail=prog.calls)
+            self._guess_ramps = [self._guess_ramp] * len(side_rts)      # (same zero convs in every net: one ramp, per net)
+            self.program = self._set_entry(tuple(range(len(side_rts))))["program"]     # (every net active: flop counts, tools)
+        else:
+            full = Plan()
+            for r in side_rts + [rt]:
+                full.calls += heads[id(r)]
+            for r in side_rts + [rt]:
+                full.calls += [c for i, c in enumerate(r.step_plan.calls) if i not in skips[id(r)]]
+                full.flops += r.step_plan.flops
+            full.calls += prog.calls
+            self.program = full
         self._keep = (ts, step, mp, lat)
         return self
 
@@ -291,10 +350,75 @@ class DenoiseLoop:
         sc = getattr(self.side_rt, "_scale", None) if getattr(self, "side_rt", None) is not None else None
         return tuple(sc) if isinstance(sc, (list, tuple)) else sc
 
+    # ---- several ControlNets: one program (and graph) per set of active nets
+    def _set_entry(self, active):
+        """The step program for the nets `active` (ascending indices): heads and plans of those nets only, the first one
+        overwriting net 0's residual buffers, the others adding to them in place; no net -> one zeroing launch over the
+        buffers (the UNet plan is never rebuilt).  keep_closed_nets: every net is in, the closed ones get scale 0."""
+        active = tuple(active)
+        ent = self._sets.get(active)
+        if ent is not None:
+            return ent
+        P, rts = self._parts, self.side_rts
+        included = list(range(len(rts))) if self.keep_closed_nets else list(active)
+        prog = Plan()
+        for k in included:
+            prog.calls += P["heads"][id(rts[k])]
+        prog.calls += P["heads"][id(self.rt)]
+        records = {}
+        for n, k in enumerate(included):
+            calls, records[k] = rts[k].chained_step_calls(rts[0], accumulate=n > 0, scale=0.0,
+                                                         skip=P["skips"][id(rts[k])])
+            prog.calls += calls
+            prog.flops += rts[k].step_plan.flops
+        if not included:
+            prog.add("zero_u64", self.lib.pp_zero_u64, *rts[0].residual_block())
+        prog.calls += [c for i, c in enumerate(self.rt.step_plan.calls) if i not in P["skips"][id(self.rt)]]
+        prog.flops += self.rt.step_plan.flops
+        prog.calls += P["tail"]
+        ent = self._sets[active] = dict(active=active, included=included, program=prog, records=records, graph=None,
+                                        scales=None)
+        return ent
+
+    def _set_scales(self, ent, scales):
+        """Write this call's per-net scales into the set's zero-conv launch records (by-value kernel arguments: a graph
+        captured with other values is dropped).  Within a call every scale of a set is constant."""
+        want = tuple(float(scales[k]) if k in ent["active"] else 0.0 for k in ent["included"])
+        if want == ent["scales"]:
+            return
+        for k, v in zip(ent["included"], want):
+            ramp = self._guess_ramps[k]
+            vals = [r * v for r in ramp] if ramp is not None else [v] * len(ent["records"][k])
+            for rec, x in zip(ent["records"][k], vals):
+                rec.scale = float(x)
+        ent["scales"], ent["graph"] = want, None
+
+    def _multi_schedule(self, scale_schedule, num_steps):
+        """Per step: the set's entry, its scales written and (use_graph) its graph captured -- all before the first step."""
+        n = len(self.side_rts)
+        if scale_schedule is None:
+            raise L.PPError("several ControlNets need a per-step schedule of per-net scales")
+        rows = [[float(v) for v in row] for row in scale_schedule[:num_steps]]
+        if len(rows) < num_steps or any(len(r) != n for r in rows):
+            raise L.PPError(f"scale_schedule must hold {num_steps} rows of {n} per-net scales")
+        ents = []
+        for row in rows:
+            ent = self._set_entry(tuple(k for k, v in enumerate(row) if v != 0.0))
+            ents.append((ent, row))
+        seen = {}
+        for ent, row in ents:
+            act = tuple(row[k] for k in ent["active"])
+            if seen.setdefault(ent["active"], act) != act:
+                raise L.PPError("the scale of an active ControlNet changed inside one call")
+        return ents
+
     def capture(self):
         """Capture one step into a hipGraph (torch.cuda.CUDAGraph).  The captured launches read the step counter from
         device memory, so the same graph serves every step."""
         self._graph_scale = self._scale_now()
+        self.graph = self._capture_program(self.program)
+
+    def _capture_program(self, program):
         torch.cuda.synchronize()
         step = self._keep[1]
         saved_step = step.clone()
@@ -303,19 +427,19 @@ class DenoiseLoop:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self.program.run(s.cuda_stream)        # warm-up outside capture (func attributes, lazy module load)
+            program.run(s.cuda_stream)             # warm-up outside capture (func attributes, lazy module load)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self.program.run(torch.cuda.current_stream().cuda_stream)
+            program.run(torch.cuda.current_stream().cuda_stream)
         # undo the warm-up's side effects
         step.copy_(saved_step)
         self.latents.copy_(saved_lat)
         if saved_m is not None:
             self._keep[2].copy_(saved_m)
         torch.cuda.synchronize()
-        self.graph = g
+        return g
 
     def run(self, latents: torch.Tensor, num_steps: int, use_graph: bool = True,
             callback: Optional[Callable] = None, timesteps=None, scale_schedule: Optional[List[float]] = None):
@@ -329,6 +453,16 @@ class DenoiseLoop:
             self._keep[2].zero_()
         self._fill_temb_tables()
         self.latents.copy_(latents.to(self.latents.device, torch.float32))
+        ents = None
+        if self._multi:
+            ents = self._multi_schedule(scale_schedule, num_steps)
+            for ent, row in ents:
+                self._set_scales(ent, row)
+                if use_graph and ent["graph"] is None:
+                    ent["graph"] = self._capture_program(ent["program"])
+            scale_schedule = None
+        elif scale_schedule is not None:          # (a wrapper around one net hands rows of one scale)
+            scale_schedule = [s[0] if isinstance(s, (list, tuple)) else s for s in scale_schedule]
         varying = scale_schedule is not None and len(set(scale_schedule)) > 1
         if not varying and scale_schedule and self.side_rt is not None and \
                 self._scale_now() != self._side_scale(scale_schedule[0]):
@@ -342,7 +476,12 @@ class DenoiseLoop:
             if self._eta > 0:         # this step's variance noise (stream-ordered before the step that consumes it)
                 self._var_noise.copy_(variance_noise(self._var_noise.shape, self._gen, self._var_noise.device,
                                                      self._noise_dtype))
-            if use_graph and not varying:
+            if ents is not None:
+                if use_graph:
+                    ents[i][0]["graph"].replay()
+                else:
+                    ents[i][0]["program"].run(stream)
+            elif use_graph and not varying:
                 self.graph.replay()
             else:
                 self.program.run(stream)
@@ -355,7 +494,7 @@ class DenoiseLoop:
         """Where a plan combines split-K in-kernel (launches of 2 / 4 co-resident splits: pp_gemm_combine_ctr_bytes()): the
         plan's fault word is examined WITHOUT a synchronisation -- copied to pinned memory behind this call's work, read by a
         later call (NetRuntime.check_faults).  `flush_faults()` is the blocking form for a caller that synchronises anyway."""
-        for r in (getattr(self, "rt", None), getattr(self, "side_rt", None)):
+        for r in [getattr(self, "rt", None)] + list(getattr(self, "side_rts", [])):
             if r is not None and r.combines_in_kernel():
                 r.check_faults(blocking=blocking)
 
@@ -382,6 +521,14 @@ class DenoiseLoop:
         self._fill_temb_tables()
         self._f_step.zero_()
         lat = latents.to(self.latents.device, torch.float32).clone()
+        ents = None
+        if self._multi:
+            ents = self._multi_schedule(scale_schedule, num_steps)
+            for ent, row in ents:
+                self._set_scales(ent, row)
+            scale_schedule = None
+        elif scale_schedule is not None:
+            scale_schedule = [s[0] if isinstance(s, (list, tuple)) else s for s in scale_schedule]
         varying = scale_schedule is not None and len(set(scale_schedule)) > 1
         stream = torch.cuda.current_stream().cuda_stream
         for i in range(num_steps):
@@ -390,7 +537,16 @@ class DenoiseLoop:
             self._f_x.copy_(x)
             if varying and self.side_rt is not None:
                 self.side_rt._patch_scale(self._side_scale(scale_schedule[i]))
-            if use_graph and not varying:
+            if ents is not None:
+                ent = ents[i][0]
+                if use_graph:
+                    if ent["graph"] is None:
+                        ent["graph"] = self._capture_program(ent["program"])
+                        self._f_step.fill_(i)
+                    ent["graph"].replay()
+                else:
+                    ent["program"].run(stream)
+            elif use_graph and not varying:
                 if self.graph is None or self._graph_scale != self._scale_now():
                     self.capture()
                     self._f_step.fill_(i)

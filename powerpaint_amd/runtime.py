@@ -1,6 +1,8 @@
 """Per-network runtime: static arena, compiled launch plans, step-invariant setup, optional hipGraph replay."""
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import ctypes as C
+
 import torch
 
 from . import _lib as L
@@ -143,6 +145,7 @@ class NetRuntime:
         self.lay, self.setup_plan, self.step_plan, self.outputs = self._build(
             self.arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin)
         self.twin = bool(twin)
+        self.pad_uncond = bool(pad_uncond)
         self.key = key
         self._scale = 1.0
         if scale != 1.0:
@@ -161,6 +164,58 @@ class NetRuntime:
             a.scale = float(v)
         self._scale = tuple(float(v) for v in scale) if isinstance(scale, (list, tuple)) else scale
         self.graph = None
+
+    # ------------------------------------------------------------------ several side networks, one sum
+    def zero_conv_records(self):
+        """The PPGemmArgs of the step plan's zero-conv launches, in output order (down..., mid[, up...])."""
+        return [args[0]._obj for fn, args, name in self.step_plan.calls if name == "zero_conv"]
+
+    def residual_block(self) -> Tuple[int, int]:
+        """(pointer, 64-bit words) of the contiguous arena block that holds every residual output of a side network
+        (SDNet.build_step allocates them back to back; with pad_uncond the zeroed unconditional halves included)."""
+        o = self.outputs
+        acts = list(o["down"]) + [o["mid"]] + list(o.get("up", []))
+        end = acts[-1].ptr + acts[-1].rows * acts[-1].C * 2
+        return acts[0].ptr, (end - acts[0].ptr + 7) // 8
+
+    def chained_step_calls(self, target: "NetRuntime", accumulate: bool, scale, skip=()):
+        """This side network's step launches (indices in `skip` left out) with the zero convs writing into `target`'s
+        residual buffers instead of its own: `accumulate=False` overwrites them (the first network of a sum),
+        `accumulate=True` adds to what they hold IN PLACE, `out = res1 = target buffer` -- the sum of several ControlNets
+        rides the zero convs' epilogues, `v = (acc + bias) * scale + res1` (include/pp_hip.h, "res1 may alias out"), and
+        costs no launch and no pass of its own.  `scale`: a float or one value per zero conv.
+        The launch records are COPIES (the network's own plan, its scale and its outputs stay as they are); the caller keeps
+        the returned records alive as long as the calls.  With pad_uncond the network's launch that zeroes the unconditional
+        halves is pointed at the target's block when it overwrites and dropped when it accumulates.
+        Returns (calls, records)."""
+        mine, theirs = self.zero_conv_records(), target.zero_conv_records()
+        if len(mine) != len(theirs) or any((a.M, a.N, a.ldo) != (b.M, b.N, b.ldo) for a, b in zip(mine, theirs)):
+            raise L.PPError("side networks whose residuals are summed must produce residuals of the same shapes")
+        vals = [float(v) for v in scale] if isinstance(scale, (list, tuple)) else [float(scale)] * len(mine)
+        if len(vals) != len(mine):
+            raise L.PPError(f"{len(vals)} residual scales for {len(mine)} zero convs")
+        pad_ptr = self.residual_block()[0] if self.pad_uncond else 0
+        calls, records, k = [], [], 0
+        for i, (fn, args, name) in enumerate(self.step_plan.calls):
+            if i in skip:
+                continue
+            if name == "zero_conv":
+                a, b = mine[k], theirs[k]
+                if a.out_dup_rows or a.res1_wrap_rows or a.res1:
+                    raise L.PPError("zero conv with a residual or a twin store cannot join a sum")
+                r = type(a).from_buffer_copy(a)
+                r.scale = vals[k]
+                r.out = b.out
+                r.res1, r.ldres1 = (b.out, b.ldo) if accumulate else (None, a.ldres1)
+                records.append(r)
+                calls.append((fn, (C.byref(r),), name))
+                k += 1
+            elif name == "zero_u64" and pad_ptr and args[0] == pad_ptr:
+                if not accumulate:
+                    calls.append((fn, target.residual_block(), name))
+            else:
+                calls.append((fn, args, name))
+        return calls, records
 
     # ------------------------------------------------------------------ inputs
     def set_timestep(self, t):
