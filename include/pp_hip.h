@@ -29,7 +29,7 @@ extern "C" {
 #define PP_ERR_LAUNCH (-3)       /* hipLaunchKernel / hipFuncSetAttribute failed                  */
 #define PP_ERR_WORKSPACE (-4)    /* workspace pointer null or too small                           */
 
-#define PP_ABI_VERSION 22
+#define PP_ABI_VERSION 23
 /* 16-bit storage format of activations and matrix weights ("dtype" arguments; the same codes pp_nchw_to_nhwc uses for
  * its source): bf16 or fp16 -- the reference's default is fp16 (/root/reference/app.py:548,559).  MFMA accumulation,
  * norm statistics, softmax, biases and latents are fp32 with either. */
@@ -574,6 +574,58 @@ int pp_softmax_rows(const float* s, long long lds, int rows, int n, float scale,
  */
 int pp_attention_small(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
                        int batch, int heads, int nq, int nk, int d, float scale, int causal, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * (ABI v23) LoRA merge: one block of a packed parameter tensor rebuilt in place from its fp32 source weight and up to
+ * PP_LORA_MAX_ADAPTERS low-rank adapters.  The reference keeps adapters as side branches: its pipelines inherit
+ * LoraLoaderMixin (/root/reference/powerpaint/pipelines/pipeline_PowerPaint_Brushnet_CA.py:147-148), forward
+ * cross_attention_kwargs["scale"] to the UNet (/root/reference/powerpaint/models/unet_2d_condition.py:1192-1195,1357-1358)
+ * and to the text encoder (pipeline_PowerPaint_Brushnet_CA.py:451-493,1248), two small GEMMs per adapted layer per step.
+ * Here the step is a fixed launch plan over one parameter buffer, so the adapters are folded INTO that buffer:
+ *     W_eff[n][k] = W[n][k] + sum_a coef[a] * sum_r up[a][n][r] * down[a][r][k]         (fp32, fmaf chains)
+ *     out[row_off + rowmap(n)][col_off + colmap(k)] = round(W_eff[n][k] * gamma[k])     (one rounding to out_dtype)
+ *   w     : fp32 [N][K] in SOURCE (diffusers) order, row stride ldw; a conv [Cout][Cin][kh][kw] is K = Cin*kh*kw
+ *   up[a] : fp32 [N][rank[a]], down[a] : fp32 [rank[a]][K], coef[a] = adapter weight * call scale * alpha / rank
+ *   gamma : NULL or fp32 [K] per-column factor (the LayerNorm weight of a folded entry), indexed by SOURCE column
+ *   rowmap: PP_LORA_ROWS_PLAIN n | PP_LORA_ROWS_GEGLU [h ; g] halves -> quads (h_2q, h_2q+1, g_2q, g_2q+1), N % 4 == 0
+ *   colmap: PLAIN k | IGEMM (c, t) -> t * cin_pad + c with taps = kh*kw (channels cin..cin_pad-1 are written as zero) |
+ *           KPERM / KPERM_GEGLU the permutations inside groups of 32 of the chained-GEMM kernels (K % 32 == 0)
+ *   out   : out_dtype PP_DT_BF16 / PP_DT_F16 / PP_DT_F32 (unrounded), a matrix of out_rows x out_cols elements with
+ *           row stride ldo; a block that does not lie inside it is PP_ERR_BAD_ARG
+ *   colsum: NULL or fp32, colsum[row] = sum over the block's columns of the values AS STORED (rounded), by destination row
+ *   bias  : NULL or fp32, bias[row] = sum_k W_eff[n][k] * beta[k] + badd[n]  (beta [K] and badd [N] each optional)
+ * Zero adapters is a plain re-pack.  More than 8 adapters or a rank outside 1..128 is PP_ERR_BAD_ARG (the caller refuses,
+ * calls are not chained).  Side vectors make the launch walk all columns of a 64-row block in one workgroup.
+ */
+#define PP_LORA_MAX_ADAPTERS 8
+#define PP_LORA_MAX_RANK 128
+#define PP_LORA_ROWS_PLAIN 0
+#define PP_LORA_ROWS_GEGLU 1
+#define PP_LORA_COLS_PLAIN 0
+#define PP_LORA_COLS_IGEMM 1
+#define PP_LORA_COLS_KPERM 2
+#define PP_LORA_COLS_KPERM_GEGLU 3
+typedef struct PPLoraMergeArgs {
+  int32_t N, K;
+  const float* w;
+  int64_t ldw;
+  int32_t n_adapters;
+  int32_t rank[PP_LORA_MAX_ADAPTERS];
+  float coef[PP_LORA_MAX_ADAPTERS];
+  const float* up[PP_LORA_MAX_ADAPTERS];
+  const float* down[PP_LORA_MAX_ADAPTERS];
+  const float* gamma;
+  const float* beta;
+  const float* badd;
+  void* out;
+  int64_t ldo;
+  int32_t out_rows, out_cols, out_dtype;
+  int32_t row_mode, row_off;
+  int32_t col_mode, col_off, taps, cin_pad;
+  float* colsum;
+  float* bias;
+} PPLoraMergeArgs;
+int pp_lora_merge(const PPLoraMergeArgs* args, void* stream);
 
 #ifdef __cplusplus
 }

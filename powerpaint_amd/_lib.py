@@ -16,7 +16,7 @@ PP_ACT_NONE, PP_ACT_GEGLU, PP_ACT_SILU, PP_ACT_SOFTMAX80 = 0, 1, 2, 3
 PP_TILE_AUTO, PP_TILE_128x160, PP_TILE_64x160, PP_TILE_256x160 = 0, 1, 2, 3
 PP_DT_F32, PP_DT_BF16, PP_DT_F16 = 0, 1, 2      # dtype codes of the C ABI (include/pp_hip.h)
 PP_ATTN_AUTO, PP_ATTN_PHASED, PP_ATTN_PIPE_Q32, PP_ATTN_PIPE_Q64, PP_ATTN_PIPE_LOG2 = 0, 1, 2, 3, 4   # pp_attention_fwd_variant
-ABI_VERSION = 22                                  # PP_ABI_VERSION of include/pp_hip.h this binding was written against
+ABI_VERSION = 23                                  # PP_ABI_VERSION of include/pp_hip.h this binding was written against
 PP_ERR = {0: "PP_OK", -1: "PP_ERR_BAD_ARG", -2: "PP_ERR_UNSUPPORTED", -3: "PP_ERR_LAUNCH", -4: "PP_ERR_WORKSPACE"}
 
 vp, i32, f32, sz = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
@@ -47,6 +47,23 @@ class PPGemmArgs(C.Structure):
         ("gn_next_out", vp), ("gn_next_gamma", vp), ("gn_next_beta", vp), ("gn_next_eps", f32), ("gn_next_silu", i32),
         ("gn_next_sub", i32), ("gn_dup_mask", i32), ("vec_batch_stride", i32),
         ("tile_ctr", vp), ("combine_fault", vp),
+    ]
+
+
+PP_LORA_MAX_ADAPTERS, PP_LORA_MAX_RANK = 8, 128
+PP_LORA_ROWS_PLAIN, PP_LORA_ROWS_GEGLU = 0, 1
+PP_LORA_COLS_PLAIN, PP_LORA_COLS_IGEMM, PP_LORA_COLS_KPERM, PP_LORA_COLS_KPERM_GEGLU = 0, 1, 2, 3
+
+
+class PPLoraMergeArgs(C.Structure):
+    _fields_ = [
+        ("N", i32), ("K", i32), ("w", vp), ("ldw", C.c_int64), ("n_adapters", i32),
+        ("rank", i32 * PP_LORA_MAX_ADAPTERS), ("coef", f32 * PP_LORA_MAX_ADAPTERS),
+        ("up", vp * PP_LORA_MAX_ADAPTERS), ("down", vp * PP_LORA_MAX_ADAPTERS),
+        ("gamma", vp), ("beta", vp), ("badd", vp),
+        ("out", vp), ("ldo", C.c_int64), ("out_rows", i32), ("out_cols", i32), ("out_dtype", i32),
+        ("row_mode", i32), ("row_off", i32), ("col_mode", i32), ("col_off", i32), ("taps", i32), ("cin_pad", i32),
+        ("colsum", vp), ("bias", vp),
     ]
 
 
@@ -110,6 +127,7 @@ SIGNATURES = {
     "pp_step_head": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
                               C.c_longlong, vp]),
     "pp_step_advance": (C.c_int, [vp, vp]),
+    "pp_lora_merge": (C.c_int, [C.POINTER(PPLoraMergeArgs), vp]),
     "pp_mask_prep": (C.c_int, [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
 }
 

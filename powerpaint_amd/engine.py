@@ -584,6 +584,33 @@ def _geglu_interleave(w: torch.Tensor) -> torch.Tensor:
     return torch.cat([h, g], dim=1).reshape(F2, *rest)
 
 
+@dataclass
+class PackRecipe:
+    """How ONE 16-bit packed entry (and the fp32 side vectors that belong to it) is made of diffusers tensors."""
+    name: str                       # packed entry
+    rows: List[str]                 # source modules ("<module>.weight" [N][K] | [Cout][Cin][k][k]) concatenated along rows
+    cols: str = "plain"             # column order: plain | igemm (_conv_igemm) | kperm | kperm_geglu | direct (_conv_direct)
+    cin_pad: int = 0                # igemm: input channels zero-padded to this many (conv_in)
+    tail: Optional[str] = None      # module whose [N][Kt] weight follows as a K tail (conv_shortcut merged into conv2)
+    compose: Optional[str] = None   # module W2: the entry is [W_rows @ W2 | W_rows] (`cols` orders the product's columns)
+    row_order: str = "plain"        # plain | geglu (_geglu_interleave)
+    gamma: Optional[str] = None     # LayerNorm module folded in: per-column factor norm.weight (beta = norm.bias)
+    colsum: Optional[str] = None    # fp32 entry: row sums of the ROUNDED weights
+    bias: Optional[str] = None      # fp32 entry: W beta (+ badd)   | composed: W_rows b2 + badd
+    badd: Optional[str] = None      # diffusers key of the additive bias
+
+    def sources(self) -> List[str]:
+        return list(self.rows) + ([self.tail] if self.tail else []) + ([self.compose] if self.compose else [])
+
+
+@dataclass
+class PackVec:
+    """One fp32 packed vector: copy | sum of two | cat | gb ((gamma, beta) interleaved) | geglu (interleaved) of state-dict keys."""
+    name: str
+    op: str
+    keys: Tuple[str, ...]
+
+
 class SDNet:
     """One network of the SD-1.5 family ("unet" | "brushnet" | "controlnet") compiled to HIP launch plans.
 
@@ -801,135 +828,316 @@ class SDNet:
                 sd[k] = torch.randn(shp, generator=g, device=device) * std
         return sd
 
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], device, materialize: bool = True):
-        """sd: diffusers-format state dict (fp32/any float, CPU or meta).  Packs into kernel layouts on `device`."""
-        pk = ParamPack()
-        bf, f32 = self.dtype, torch.float32      # `bf`: the 16-bit storage format of matrix weights (bf16 or fp16)
+    # ---------------------------------------------------------------- the packing table
+    def pack_table(self) -> List[object]:
+        """Every packed entry of this network in buffer order, as ONE recipe each: which diffusers tensors it is made of and
+        how (PackRecipe: 16-bit matrices and the fp32 side vectors derived from them; PackVec: fp32 vectors copied from the
+        state dict).  `load_state_dict` evaluates the table on the host, `repack` evaluates single recipes on the device
+        (pp_lora_merge) into the slots the first one laid out.  Built once per `load_state_dict` (which also takes the
+        time-embedding row offsets from it) and kept."""
+        if getattr(self, "_table", None) is None:
+            self._table, self.temb_off, self.temb_total = self._build_pack_table()
+        return self._table
 
-        def W(k):
-            return sd[k].float() if sd[k].device.type != "meta" else sd[k]
+    def _build_pack_table(self):
+        T: List[object] = []
+        R, V = PackRecipe, PackVec
+
+        def vec(name, key=None):
+            T.append(V(name, "copy", (key or name,)))
 
         conv_in = "conv_in_condition" if self.kind == "brushnet" else "conv_in"
-        pk.add("conv_in.weight", _conv_igemm_cpad(W(conv_in + ".weight"), self.cin_pad), bf)
-        pk.add("conv_in.bias", W(conv_in + ".bias"), f32)
+        T.append(R("conv_in.weight", [conv_in], cols="igemm", cin_pad=self.cin_pad))
+        vec("conv_in.bias", conv_in + ".bias")
         for n in ("linear_1", "linear_2"):
-            pk.add(f"time_embedding.{n}.weight", W(f"time_embedding.{n}.weight"), bf)
-            pk.add(f"time_embedding.{n}.bias", W(f"time_embedding.{n}.bias"), f32)
+            T.append(R(f"time_embedding.{n}.weight", [f"time_embedding.{n}"]))
+            vec(f"time_embedding.{n}.bias")
         # resnets
-        tw, tb, off = [], [], 0
+        tw, off = [], 0
+        temb_off: Dict[str, int] = {}
         for pre, cin, cout in self._resnet_specs():
             for nrm in ("norm1", "norm2"):
-                pk.add(f"{pre}.{nrm}.weight", W(f"{pre}.{nrm}.weight"), f32)
-                pk.add(f"{pre}.{nrm}.bias", W(f"{pre}.{nrm}.bias"), f32)
+                vec(f"{pre}.{nrm}.weight")
+                vec(f"{pre}.{nrm}.bias")
                 # (gamma, beta) interleaved per channel: what the fused norm -> SiLU -> conv loader DMAs per 64-channel chunk
-                pk.add(f"{pre}.{nrm}.gb", torch.stack([W(f"{pre}.{nrm}.weight"), W(f"{pre}.{nrm}.bias")], 1), f32)
-            pk.add(f"{pre}.conv1.weight", _conv_igemm(W(f"{pre}.conv1.weight")), bf)
-            pk.add(f"{pre}.conv1.bias", W(f"{pre}.conv1.bias"), f32)
+                T.append(V(f"{pre}.{nrm}.gb", "gb", (f"{pre}.{nrm}.weight", f"{pre}.{nrm}.bias")))
+            T.append(R(f"{pre}.conv1.weight", [f"{pre}.conv1"], cols="igemm"))
+            vec(f"{pre}.conv1.bias")
             if cin != cout and self.merge_shortcut:
                 # conv2(h) + conv_shortcut(x) = one implicit GEMM: the 1x1 shortcut is a K tail over the block input
-                pk.add(f"{pre}.conv2.weight", torch.cat([_conv_igemm(W(f"{pre}.conv2.weight")),
-                                                          W(f"{pre}.conv_shortcut.weight").reshape(cout, cin)], 1), bf)
-                pk.add(f"{pre}.conv2.bias", W(f"{pre}.conv2.bias") + W(f"{pre}.conv_shortcut.bias"), f32)
+                T.append(R(f"{pre}.conv2.weight", [f"{pre}.conv2"], cols="igemm", tail=f"{pre}.conv_shortcut"))
+                T.append(V(f"{pre}.conv2.bias", "sum", (f"{pre}.conv2.bias", f"{pre}.conv_shortcut.bias")))
             else:
-                pk.add(f"{pre}.conv2.weight", _conv_igemm(W(f"{pre}.conv2.weight")), bf)
-                pk.add(f"{pre}.conv2.bias", W(f"{pre}.conv2.bias"), f32)
+                T.append(R(f"{pre}.conv2.weight", [f"{pre}.conv2"], cols="igemm"))
+                vec(f"{pre}.conv2.bias")
                 if cin != cout:
-                    pk.add(f"{pre}.conv_shortcut.weight", W(f"{pre}.conv_shortcut.weight").reshape(cout, cin), bf)
-                    pk.add(f"{pre}.conv_shortcut.bias", W(f"{pre}.conv_shortcut.bias"), f32)
-            tw.append(W(f"{pre}.time_emb_proj.weight"))
-            tb.append(W(f"{pre}.time_emb_proj.bias"))
-            self.temb_off[pre] = off
+                    T.append(R(f"{pre}.conv_shortcut.weight", [f"{pre}.conv_shortcut"]))
+                    vec(f"{pre}.conv_shortcut.bias")
+            tw.append(f"{pre}.time_emb_proj")
+            temb_off[pre] = off
             off += cout
-        self.temb_total = off
-        pk.add("temb_all.weight", torch.cat(tw, 0), bf)
-        pk.add("temb_all.bias", torch.cat(tb, 0), f32)
+        temb_total = off
+        T.append(R("temb_all.weight", tw))
+        T.append(V("temb_all.bias", "cat", tuple(m + ".bias" for m in tw)))
         # samplers
         for i in range(len(self.boc) - 1):
             pre = f"down_blocks.{i}.downsamplers.0.conv"
-            pk.add(pre + ".weight", _conv_igemm(W(pre + ".weight")), bf)
-            pk.add(pre + ".bias", W(pre + ".bias"), f32)
+            T.append(R(pre + ".weight", [pre], cols="igemm"))
+            vec(pre + ".bias")
             if self.kind != "controlnet":
                 pre = f"up_blocks.{i}.upsamplers.0.conv"
-                pk.add(pre + ".weight", _conv_igemm(W(pre + ".weight")), bf)
-                pk.add(pre + ".bias", W(pre + ".bias"), f32)
+                T.append(R(pre + ".weight", [pre], cols="igemm"))
+                vec(pre + ".bias")
         # transformers
         for pre, c in self._attn_specs():
-            pk.add(f"{pre}.norm.weight", W(f"{pre}.norm.weight"), f32)
-            pk.add(f"{pre}.norm.bias", W(f"{pre}.norm.bias"), f32)
-            pk.add(f"{pre}.proj_in.weight", W(f"{pre}.proj_in.weight").reshape(c, c), bf)
-            pk.add(f"{pre}.proj_in.bias", W(f"{pre}.proj_in.bias"), f32)
-            w_po, b_po = W(f"{pre}.proj_out.weight").reshape(c, c), W(f"{pre}.proj_out.bias")
+            vec(f"{pre}.norm.weight")
+            vec(f"{pre}.norm.bias")
+            T.append(R(f"{pre}.proj_in.weight", [f"{pre}.proj_in"]))
+            vec(f"{pre}.proj_in.bias")
+            tb_ = f"{pre}.transformer_blocks.0"
             if self.merge_ff2_proj_out:
                 # FF2 and proj_out are two linear maps with only a residual add between them:
                 #   proj_out(FF2(g) + hs) = [g | hs] [W_po W_ff2 | W_po]^T + (W_po b_ff2 + b_po)
                 # -> ONE GEMM over the K-concatenation of g and hs (same FLOPs, one launch and one hidden-state round
                 # trip less per transformer); composed in fp32 at pack time.
-                w_f2, b_f2 = W(f"{pre}.transformer_blocks.0.ff.net.2.weight"), W(f"{pre}.transformer_blocks.0.ff.net.2.bias")
-                pk.add(f"{pre}.ff2_proj_out.weight", torch.cat([w_po @ w_f2, w_po], 1), bf)
-                pk.add(f"{pre}.ff2_proj_out.bias", w_po @ b_f2 + b_po, f32)
+                T.append(R(f"{pre}.ff2_proj_out.weight", [f"{pre}.proj_out"], compose=f"{tb_}.ff.net.2",
+                           bias=f"{pre}.ff2_proj_out.bias", badd=f"{pre}.proj_out.bias"))
                 if c == 320 and self.fuse_ff and self.fold_ln and not self.ff_w8:
                     # the same matrix with its hidden index permuted: second GEMM of the 4-wave fused feed-forward
-                    pk.add(f"{pre}.ff2_proj_out.weight_kp", torch.cat([_kperm_geglu(w_po @ w_f2), w_po], 1), bf)
+                    T.append(R(f"{pre}.ff2_proj_out.weight_kp", [f"{pre}.proj_out"], compose=f"{tb_}.ff.net.2",
+                               cols="kperm_geglu"))
             else:
-                pk.add(f"{pre}.proj_out.weight", w_po, bf)
-                pk.add(f"{pre}.proj_out.bias", b_po, f32)
-            tb_ = f"{pre}.transformer_blocks.0"
-            wqkv = torch.cat([W(f"{tb_}.attn1.to_q.weight"), W(f"{tb_}.attn1.to_k.weight"),
-                              W(f"{tb_}.attn1.to_v.weight")], 0)
-            wff1, bff1 = W(f"{tb_}.ff.net.0.proj.weight"), W(f"{tb_}.ff.net.0.proj.bias")
+                T.append(R(f"{pre}.proj_out.weight", [f"{pre}.proj_out"]))
+                vec(f"{pre}.proj_out.bias")
+            qkv = [f"{tb_}.attn1.to_q", f"{tb_}.attn1.to_k", f"{tb_}.attn1.to_v"]
             if self.fold_ln:
                 # LayerNorm folded into the Linear that consumes it:  LN(x) W^T = rstd (x (g.W)^T - mean colsum) + W b
-                def fold(name, w, nrm, bias=None, il=False):
-                    g_, b_ = W(f"{tb_}.{nrm}.weight"), W(f"{tb_}.{nrm}.bias")
-                    wf = w * g_[None, :]
-                    cs = wf.to(bf).float().sum(1)          # of the weights as the MFMA sees them
-                    t = w @ b_ if bias is None else w @ b_ + bias
-                    if il:
-                        wf, cs, t = _geglu_interleave(wf), _geglu_interleave(cs), _geglu_interleave(t)
-                    pk.add(f"{name}.weight", wf, bf)
-                    pk.add(f"{name}.colsum", cs, f32)
-                    pk.add(f"{name}.bias", t, f32)
+                def fold(name, mods, nrm, badd=None, il=False):
+                    T.append(R(f"{name}.weight", mods, gamma=f"{tb_}.{nrm}", colsum=f"{name}.colsum", bias=f"{name}.bias",
+                               badd=badd, row_order="geglu" if il else "plain"))
 
-                fold(f"{tb_}.attn1.qkv", wqkv, "norm1")
-                if wqkv.shape[1] == 320 and self.fuse_tfront:
+                fold(f"{tb_}.attn1.qkv", qkv, "norm1")
+                if c == 320 and self.fuse_tfront:
                     # the same folded weight with its input index permuted: second GEMM of the fused front end (csrc/tfront.hip)
-                    g_ = W(f"{tb_}.norm1.weight")
-                    pk.add(f"{tb_}.attn1.qkv.weight_kp", _kperm(wqkv * g_[None, :]), bf)
-                fold(f"{tb_}.attn2.to_q", W(f"{tb_}.attn2.to_q.weight"), "norm2")
-                fold(f"{tb_}.ff1", wff1, "norm3", bff1, il=True)
+                    T.append(R(f"{tb_}.attn1.qkv.weight_kp", qkv, gamma=f"{tb_}.norm1", cols="kperm"))
+                fold(f"{tb_}.attn2.to_q", [f"{tb_}.attn2.to_q"], "norm2")
+                fold(f"{tb_}.ff1", [f"{tb_}.ff.net.0.proj"], "norm3", f"{tb_}.ff.net.0.proj.bias", il=True)
             else:
                 for nrm in ("norm1", "norm2", "norm3"):
-                    pk.add(f"{tb_}.{nrm}.weight", W(f"{tb_}.{nrm}.weight"), f32)
-                    pk.add(f"{tb_}.{nrm}.bias", W(f"{tb_}.{nrm}.bias"), f32)
-                pk.add(f"{tb_}.attn1.qkv.weight", wqkv, bf)
-                pk.add(f"{tb_}.attn2.to_q.weight", W(f"{tb_}.attn2.to_q.weight"), bf)
-                pk.add(f"{tb_}.ff1.weight", _geglu_interleave(wff1), bf)
-                pk.add(f"{tb_}.ff1.bias", _geglu_interleave(bff1), f32)
-            pk.add(f"{tb_}.attn1.to_out.weight", W(f"{tb_}.attn1.to_out.0.weight"), bf)
-            pk.add(f"{tb_}.attn1.to_out.bias", W(f"{tb_}.attn1.to_out.0.bias"), f32)
-            pk.add(f"{tb_}.attn2.kv.weight", torch.cat([W(f"{tb_}.attn2.to_k.weight"), W(f"{tb_}.attn2.to_v.weight")], 0), bf)
-            pk.add(f"{tb_}.attn2.to_out.weight", W(f"{tb_}.attn2.to_out.0.weight"), bf)
-            pk.add(f"{tb_}.attn2.to_out.bias", W(f"{tb_}.attn2.to_out.0.bias"), f32)
+                    vec(f"{tb_}.{nrm}.weight")
+                    vec(f"{tb_}.{nrm}.bias")
+                T.append(R(f"{tb_}.attn1.qkv.weight", qkv))
+                T.append(R(f"{tb_}.attn2.to_q.weight", [f"{tb_}.attn2.to_q"]))
+                T.append(R(f"{tb_}.ff1.weight", [f"{tb_}.ff.net.0.proj"], row_order="geglu"))
+                T.append(V(f"{tb_}.ff1.bias", "geglu", (f"{tb_}.ff.net.0.proj.bias",)))
+            T.append(R(f"{tb_}.attn1.to_out.weight", [f"{tb_}.attn1.to_out.0"]))
+            vec(f"{tb_}.attn1.to_out.bias", f"{tb_}.attn1.to_out.0.bias")
+            T.append(R(f"{tb_}.attn2.kv.weight", [f"{tb_}.attn2.to_k", f"{tb_}.attn2.to_v"]))
+            T.append(R(f"{tb_}.attn2.to_out.weight", [f"{tb_}.attn2.to_out.0"]))
+            vec(f"{tb_}.attn2.to_out.bias", f"{tb_}.attn2.to_out.0.bias")
             if not self.merge_ff2_proj_out:
-                pk.add(f"{tb_}.ff2.weight", W(f"{tb_}.ff.net.2.weight"), bf)
-                pk.add(f"{tb_}.ff2.bias", W(f"{tb_}.ff.net.2.bias"), f32)
+                T.append(R(f"{tb_}.ff2.weight", [f"{tb_}.ff.net.2"]))
+                vec(f"{tb_}.ff2.bias", f"{tb_}.ff.net.2.bias")
         if self.kind == "unet":
-            pk.add("conv_norm_out.weight", W("conv_norm_out.weight"), f32)
-            pk.add("conv_norm_out.bias", W("conv_norm_out.bias"), f32)
-            pk.add("conv_out.weight", _conv_igemm(W("conv_out.weight")), bf)
-            pk.add("conv_out.bias", W("conv_out.bias"), f32)
+            vec("conv_norm_out.weight")
+            vec("conv_norm_out.bias")
+            T.append(R("conv_out.weight", ["conv_out"], cols="igemm"))
+            vec("conv_out.bias")
         for pre, c in self._zero_conv_specs():
-            pk.add(pre + ".weight", W(pre + ".weight").reshape(c, c), bf)
-            pk.add(pre + ".bias", W(pre + ".bias"), f32)
+            T.append(R(pre + ".weight", [pre]))
+            vec(pre + ".bias")
         if self.kind == "controlnet":
             ce = "controlnet_cond_embedding"
             names = ["conv_in"] + [f"blocks.{i}" for i in range(2 * (len(self.cond_embed_channels) - 1))] + ["conv_out"]
             for n in names:
-                pk.add(f"{ce}.{n}.weight", _conv_direct(W(f"{ce}.{n}.weight")), bf)
-                pk.add(f"{ce}.{n}.bias", W(f"{ce}.{n}.bias"), f32)
+                T.append(R(f"{ce}.{n}.weight", [f"{ce}.{n}"], cols="direct"))
+                vec(f"{ce}.{n}.bias")
+        return T, temb_off, temb_total
+
+    def pack_host(self, it, W) -> List[Tuple[str, torch.Tensor, torch.dtype]]:
+        """One table item evaluated with torch on wherever `W(key)` (fp32 source tensor by diffusers key) lives:
+        -> [(packed name, tensor, storage dtype)] in buffer order."""
+        bf, f32 = self.dtype, torch.float32      # `bf`: the 16-bit storage format of matrix weights (bf16 or fp16)
+        if isinstance(it, PackVec):
+            k = it.keys
+            if it.op == "copy":
+                t = W(k[0])
+            elif it.op == "sum":
+                t = W(k[0]) + W(k[1])
+            elif it.op == "cat":
+                t = torch.cat([W(x) for x in k], 0)
+            elif it.op == "gb":
+                t = torch.stack([W(k[0]), W(k[1])], 1)
+            else:
+                t = _geglu_interleave(W(k[0]))
+            return [(it.name, t, f32)]
+        r = it
+
+        def mat(m):
+            w = W(m + ".weight")
+            if r.cols == "igemm" and not r.compose:
+                return _conv_igemm_cpad(w, r.cin_pad) if r.cin_pad else _conv_igemm(w)
+            if r.cols == "direct":
+                return _conv_direct(w)
+            return w.reshape(w.shape[0], -1) if w.dim() == 4 else w
+
+        if r.compose:
+            w_po, w_f2 = mat(r.rows[0]), W(r.compose + ".weight")
+            prod = w_po @ w_f2
+            if r.cols == "kperm_geglu":
+                prod = _kperm_geglu(prod)
+            out = [(r.name, torch.cat([prod, w_po], 1), bf)]
+            if r.bias:
+                out.append((r.bias, w_po @ W(r.compose + ".bias") + W(r.badd), f32))
+            return out
+        ws = [mat(m) for m in r.rows]
+        w = ws[0] if len(ws) == 1 else torch.cat(ws, 0)
+        cs = t = None
+        if r.gamma:
+            g_, b_ = W(r.gamma + ".weight"), W(r.gamma + ".bias")
+            wf = w * g_[None, :]
+            if r.colsum:
+                cs = wf.to(bf).float().sum(1)          # of the weights as the MFMA sees them
+                t = w @ b_ if r.badd is None else w @ b_ + W(r.badd)
+            w = wf
+        if r.cols == "kperm":
+            w = _kperm(w)
+        if r.tail:
+            wt = W(r.tail + ".weight")
+            w = torch.cat([w, wt.reshape(wt.shape[0], -1)], 1)
+        if r.row_order == "geglu":
+            w = _geglu_interleave(w)
+            if cs is not None:
+                cs, t = _geglu_interleave(cs), _geglu_interleave(t)
+        out = [(r.name, w, bf)]
+        if cs is not None:
+            out += [(r.colsum, cs, f32), (r.bias, t, f32)]
+        return out
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], device, materialize: bool = True):
+        """sd: diffusers-format state dict (fp32/any float, CPU or meta).  Packs into kernel layouts on `device`."""
+        pk = ParamPack()
+
+        def W(k):
+            return sd[k].float() if sd[k].device.type != "meta" else sd[k]
+
+        self._table = None                     # (the lab switches may have changed since the last load)
+        for it in self.pack_table():
+            for name, t, dt in self.pack_host(it, W):
+                pk.add(name, t, dt)
         pk.to_device(device, materialize)
         self.params, self.P = pk, pk.ptr
         return self
+
+    def recipes_of(self, modules) -> List["PackRecipe"]:
+        """The recipes (in buffer order) whose packed entry depends on the weight of one of these source modules."""
+        mods = set(modules)
+        return [r for r in self.pack_table() if isinstance(r, PackRecipe) and mods & set(r.sources())]
+
+    def repack(self, modules, merged: Dict[str, list], source: Dict[str, torch.Tensor], stream: Optional[int] = None,
+               composed_out: Optional[dict] = None):
+        """Rebuild, on the device and in place, every packed entry that depends on the weight of one of `modules`
+        (diffusers module names, e.g. "mid_block.attentions.0.proj_in"), then `params.touch()`.
+          merged: module -> [(up [N][r], down [r][K], coefficient), ...] fp32 device tensors: the low-rank terms folded into that
+                  module's weight (W + sum c U D; a module that is not named is repacked as it is);
+          source: diffusers key -> fp32 device tensor, at least the weights of every source module of the touched recipes,
+                  the LayerNorm weight / bias of the folded ones and the biases their side vectors take in.
+        The sums are formed in fp32 and rounded once, after the pack-time transformations (pp_lora_merge); a composed entry
+        ([W_po W_ff2 | W_po]) goes through fp32 temporaries of its two merged factors (handed out through `composed_out`:
+        recipe name -> (W_po', W_po' @ W_ff2'), for whoever wants to check them).  Returns the recipes it rebuilt."""
+        if self.params is None or self.params.buf is None or self.params.buf.device.type != "cuda":
+            raise L.PPError("SDNet.repack: the parameters must be packed on the GPU first (load_state_dict)")
+        lib = L.lib()
+        recipes = self.recipes_of(modules)
+        keep = []                      # temporaries and argument records stay alive until every launch is queued
+        cache: Dict[Tuple[str, str], Tuple[torch.Tensor, torch.Tensor]] = {}
+        dev = self.params.buf.device
+        if stream is None:             # (the fp32 temporaries are torch allocations: the launches go where torch orders them)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def src(key):
+            if key not in source:
+                raise L.PPError(f"SDNet.repack: the fp32 source tensor {key!r} is missing")
+            t = source[key]
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise L.PPError(f"SDNet.repack: source tensor {key!r} must be contiguous fp32 on {dev}")
+            return t
+
+        def launch(w, N, K, ads, out, out_dt, ldo, out_rows, out_cols, row_mode=0, row_off=0, col_mode=0, col_off=0, taps=0,
+                   cin_pad=0, gamma=None, beta=None, badd=None, colsum=None, bias=None):
+            if len(ads) > L.PP_LORA_MAX_ADAPTERS:
+                raise L.PPError(f"at most {L.PP_LORA_MAX_ADAPTERS} adapters can be merged into one module "
+                                f"({len(ads)} active)")
+            a = L.PPLoraMergeArgs()
+            a.N, a.K, a.w, a.ldw, a.n_adapters = N, K, w.data_ptr(), K, len(ads)
+            for i, (up, down, coef) in enumerate(ads):
+                rk = down.shape[0]
+                if rk > L.PP_LORA_MAX_RANK:
+                    raise L.PPError(f"adapter rank {rk} is above the kernel's limit of {L.PP_LORA_MAX_RANK}")
+                if up.numel() != N * rk or down.numel() != rk * K or up.dtype != torch.float32 or \
+                        down.dtype != torch.float32 or not up.is_contiguous() or not down.is_contiguous():
+                    raise L.PPError(f"adapter factors do not fit a [{N}][{K}] weight: up {tuple(up.shape)}, down "
+                                    f"{tuple(down.shape)} (contiguous fp32 expected)")
+                a.rank[i], a.coef[i], a.up[i], a.down[i] = rk, float(coef), up.data_ptr(), down.data_ptr()
+            ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+            a.gamma, a.beta, a.badd = ptr(gamma), ptr(beta), ptr(badd)
+            a.out, a.ldo, a.out_rows, a.out_cols, a.out_dtype = out.data_ptr(), ldo, out_rows, out_cols, out_dt
+            a.row_mode, a.row_off, a.col_mode, a.col_off, a.taps, a.cin_pad = row_mode, row_off, col_mode, col_off, taps, cin_pad
+            a.colsum, a.bias = ptr(colsum), ptr(bias)
+            keep.append((a, w, ads, gamma, beta, badd))
+            L.check(lib.pp_lora_merge(C.byref(a), stream), "pp_lora_merge")
+
+        dt16 = L.dtype_code(self.dtype)
+        cmode = {"plain": L.PP_LORA_COLS_PLAIN, "igemm": L.PP_LORA_COLS_IGEMM, "kperm": L.PP_LORA_COLS_KPERM,
+                 "kperm_geglu": L.PP_LORA_COLS_KPERM_GEGLU}
+        for r in recipes:
+            if r.cols == "direct":
+                raise L.PPError(f"{r.name}: this layout is not rebuilt on the device (the network takes no adapters)")
+            dst = self.params.tensor(r.name)
+            R_, Ct = dst.shape
+            if r.compose:
+                po, f2 = r.rows[0], r.compose
+                if (po, f2) not in cache:
+                    w_po, w_f2 = src(po + ".weight"), src(f2 + ".weight")
+                    Cc, F = w_po.shape[0], w_f2.shape[1]
+                    t1 = torch.empty(Cc, Cc, dtype=torch.float32, device=dev)
+                    t2 = torch.empty(Cc, F, dtype=torch.float32, device=dev)
+                    launch(w_f2, Cc, F, merged.get(f2, ()), t2, L.PP_DT_F32, F, Cc, F)
+                    if r.bias is None:
+                        raise L.PPError(f"{r.name}: the first recipe of a composed pair carries the bias")
+                    launch(w_po, Cc, Cc, merged.get(po, ()), t1, L.PP_DT_F32, Cc, Cc, Cc, beta=src(f2 + ".bias"),
+                           badd=src(r.badd), bias=self.params.tensor(r.bias))
+                    cache[(po, f2)] = (t1, t1 @ t2)
+                t1, prod = cache[(po, f2)]
+                if composed_out is not None:
+                    composed_out[r.name] = (t1, prod)
+                Cc, F = prod.shape
+                launch(prod, Cc, F, (), dst, dt16, Ct, R_, Ct, col_mode=cmode[r.cols])
+                launch(t1, Cc, Cc, (), dst, dt16, Ct, R_, Ct, col_off=F)
+                continue
+            gamma = src(r.gamma + ".weight") if r.gamma else None
+            beta = src(r.gamma + ".bias") if r.gamma and r.colsum else None
+            colsum = self.params.tensor(r.colsum) if r.colsum else None
+            bias = self.params.tensor(r.bias) if r.colsum else None
+            row_off, kd = 0, 0
+            for m in r.rows:
+                w = src(m + ".weight")
+                N, K = w.shape[0], w.numel() // w.shape[0]
+                taps = K // w.shape[1] if r.cols == "igemm" else 0
+                cpad = (r.cin_pad or w.shape[1]) if r.cols == "igemm" else 0
+                kd = taps * cpad if r.cols == "igemm" else K
+                launch(w, N, K, merged.get(m, ()), dst, dt16, Ct, R_, Ct, row_off=row_off, col_mode=cmode[r.cols], taps=taps,
+                       cin_pad=cpad, row_mode=L.PP_LORA_ROWS_GEGLU if r.row_order == "geglu" else L.PP_LORA_ROWS_PLAIN,
+                       gamma=gamma, beta=beta, badd=src(r.badd)[row_off:row_off + N] if r.badd else None, colsum=colsum,
+                       bias=bias)             # (the kernel indexes badd by the block's own rows)
+                row_off += N
+            if r.tail:
+                w = src(r.tail + ".weight")
+                N, K = w.shape[0], w.numel() // w.shape[0]
+                launch(w, N, K, merged.get(r.tail, ()), dst, dt16, Ct, R_, Ct, col_off=kd)
+        self.params.touch()
+        self.repack_launches = len(keep)      # (temporaries are stream-ordered allocations: safe to let go once queued)
+        return recipes
 
     # ---------------------------------------------------------------- plan pieces
     def _resnet(self, pb: Builder, pre: str, x: Act, cout: int, temb_all: int, x2: Optional[Act] = None,

@@ -123,7 +123,79 @@ class CLIPTextModel(nn.Module, PretrainedMixin):
             if k == "text_model.embeddings.token_embedding.weight":
                 k = "text_model.embeddings.token_embedding.wrapped.weight"
             sd[k] = v
+        if self.__dict__.get("_lora_orig"):      # new weights: what was kept for un-merging is void, adapters re-merge
+            self.__dict__["_lora_orig"], self.__dict__["_lora_state"] = {}, None
         return super().load_state_dict(sd, strict=strict, assign=assign)
+
+    # ---- LoRA adapters: merged into the nn.Parameters in place from kept originals (123 M parameters, once per change of
+    #      the adapter set / weights / scale: not a hot path, plain torch).  The in-place copy bumps the parameters' version
+    #      counters, which `_params_stamp` keys on, so the next forward repacks the tower.
+    def _lora_set(self):
+        from ..lora import AdapterSet
+        if "_adapters" not in self.__dict__:
+            self.__dict__["_adapters"] = AdapterSet()
+            self.__dict__["_lora_orig"], self.__dict__["_lora_state"] = {}, None
+        return self.__dict__["_adapters"]
+
+    def load_lora_adapter(self, adapter, adapter_name: str = "default"):
+        """adapter: a `powerpaint_amd.lora.LoraAdapter` (its `text_encoder` part is taken) or {module: (down, up, alpha)}."""
+        from ..lora import LoraAdapter, text_targets
+        fac = adapter.text_encoder if isinstance(adapter, LoraAdapter) else dict(adapter)
+        targets = text_targets(self)
+        for m, (down, up, alpha) in fac.items():
+            if m not in targets:
+                raise L.PPError(f"LoRA module {m!r} matches no target module of the text encoder")
+            if (up.shape[0], down.shape[1]) != targets[m] or up.shape[1] != down.shape[0]:
+                raise L.PPError(f"LoRA module {m!r}: factors down {tuple(down.shape)} / up {tuple(up.shape)} do not fit "
+                                f"{m}.weight {targets[m]}")
+        self._lora_set().add(adapter_name, fac)
+        return self
+
+    def set_adapters(self, adapter_names, weights=None):
+        self._lora_set().set(adapter_names, weights)
+        return self
+
+    def delete_adapters(self, adapter_names):
+        self._lora_set().delete(adapter_names)
+        if not self._lora_set().active:
+            self.merge_adapters(1.0)
+        return self
+
+    def active_adapters(self):
+        return list(self._lora_set().active)
+
+    @torch.no_grad()
+    def merge_adapters(self, scale: float = 1.0) -> bool:
+        """Parameters := originals + sum_a w_a * scale * (alpha_a / r_a) U_a D_a (float64 sum, one rounding to the parameters'
+        dtype).  Returns whether anything changed."""
+        d = self.__dict__
+        ads = d.get("_adapters")
+        if ads is None or (not ads.loaded and d["_lora_state"] is None):
+            return False
+        if d.get("lora_scale_fixed") is not None:                    # (pipeline.fuse_lora: later scales have no effect)
+            scale = d["lora_scale_fixed"]
+        state = ads.state(scale)
+        if state == d["_lora_state"]:
+            return False
+        mods = dict(self.named_modules())
+        delta = {}
+        for name, w in ads.active.items():
+            for m, (down, up, alpha) in ads.loaded[name].items():
+                p = mods[m].weight
+                c = w * float(scale) * float(alpha) / down.shape[0]
+                t = (up.to(p.device, torch.float64) @ down.to(p.device, torch.float64)) * c
+                delta[m] = delta[m] + t if m in delta else t
+        orig = d["_lora_orig"]
+        for m in list(orig):
+            if m not in delta:
+                mods[m].weight.copy_(orig.pop(m))
+        for m, t in delta.items():
+            p = mods[m].weight
+            if m not in orig:
+                orig[m] = p.detach().clone()
+            p.copy_((orig[m].double() + t).to(p.dtype))
+        d["_lora_state"] = state
+        return True
 
     def _params_stamp(self):
         return tuple((p.data_ptr(), p._version) for n, p in self.named_parameters() if ".token_embedding." not in n)

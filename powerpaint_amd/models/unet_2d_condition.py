@@ -11,6 +11,7 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 import torch
 
 from .. import _lib as L
+from ..lora import AdapterSet, LoraAdapter, unet_targets
 from ._base import SD15_DOWN, SD15_UP, Output, _HipModel
 
 
@@ -37,6 +38,131 @@ class UNet2DConditionModel(_HipModel):
             resnet_time_scale_shift="default", mid_block_scale_factor=1, downsample_padding=1,
             num_attention_heads=None, projection_class_embeddings_input_dim=None, encoder_hid_dim=None,
             encoder_hid_dim_type=None, addition_time_embed_dim=None, transformer_layers_per_block=1)
+
+    # ------------------------------------------------------------------ LoRA adapters (DESIGN.md "LoRA adapters")
+    # Adapters are MERGED into the packed parameter buffer in place (SDNet.repack -> pp_lora_merge): the launch plans, the
+    # captured graphs and the step cost stay what they are without adapters.  Kept from the first adapter on, and only for the
+    # modules adapters touch: an fp32 device copy of the source weights and a byte snapshot of the packed entries that get
+    # overwritten; both go when the active set becomes empty.
+    def load_state_dict(self, sd, strict: bool = True, keep_state_dict: bool = False, materialize: bool = True):
+        """keep_state_dict=True keeps `sd` (as BrushNetModel.from_unet needs it, and as from_pretrained does): the fp32
+        source of an adapter merge is read from it, at the time of the first merge."""
+        super().load_state_dict(sd, strict, keep_state_dict, materialize)
+        self._lora_forget()
+        return self
+
+    def _lora_set(self) -> AdapterSet:
+        if "_adapters" not in self.__dict__:
+            self._adapters = AdapterSet()
+            self._lora_forget()
+        return self._adapters
+
+    def _lora_forget(self):
+        """The packed buffer holds the plain weights (again): drop what was derived for merging."""
+        self._lora_src, self._lora_snap, self._lora_dirty, self._lora_state = {}, {}, [], None
+        self._lora_dev = {}
+
+    def load_lora_adapter(self, adapter, adapter_name: str = "default"):
+        """adapter: a `powerpaint_amd.lora.LoraAdapter` (its `unet` part is taken) or {module: (down, up, alpha)}."""
+        fac = adapter.unet if isinstance(adapter, LoraAdapter) else dict(adapter)
+        targets = unet_targets(self.net)
+        for m, (down, up, alpha) in fac.items():
+            if m not in targets:
+                raise L.PPError(f"LoRA module {m!r} matches no target module of the unet")
+            shp, r = targets[m], down.shape[0]
+            if tuple(down.shape[1:]) != tuple(shp[1:]) or up.reshape(up.shape[0], -1).shape != (shp[0], r):
+                raise L.PPError(f"LoRA module {m!r}: factors down {tuple(down.shape)} / up {tuple(up.shape)} do not fit "
+                                f"{m}.weight {shp}")
+            if not 1 <= r <= L.PP_LORA_MAX_RANK:
+                raise L.PPError(f"LoRA module {m!r}: rank {r} is outside 1..{L.PP_LORA_MAX_RANK}")
+        self._lora_set().add(adapter_name, fac)
+        return self
+
+    def set_adapters(self, adapter_names, weights=None):
+        self._lora_set().set(adapter_names, weights)
+        return self
+
+    def delete_adapters(self, adapter_names):
+        ads = self._lora_set()
+        ads.delete(adapter_names)
+        if not ads.active:
+            self.merge_adapters(1.0)          # the last one left: back to the plain weights now, copies freed
+        return self
+
+    def active_adapters(self):
+        return list(self._lora_set().active)
+
+    def list_adapters(self):
+        return list(self._lora_set().loaded)
+
+    def _lora_source(self, keys):
+        sd = self._sd
+        for k in keys:
+            if k not in self._lora_src:
+                if sd is None or k not in sd or sd[k].device.type == "meta":
+                    raise L.PPError(f"{type(self).__name__}: merging an adapter needs the fp32 source weights ({k!r}), but "
+                                    f"the model keeps no state dict: load it with from_pretrained or with "
+                                    f"load_state_dict(sd, keep_state_dict=True) (a buffer filled through param_buffer() has "
+                                    f"no source)")
+                self._lora_src[k] = sd[k].to(device=self._device, dtype=torch.float32).contiguous()
+        return self._lora_src
+
+    def merge_adapters(self, scale: float = 1.0):
+        """Bring the packed weights to `W + sum_a w_a * scale * (alpha_a / r_a) U_a D_a` over the active adapters; nothing
+        happens when they are there already (same adapters, weights and scale)."""
+        ads = self.__dict__.get("_adapters")
+        if ads is None or (not ads.loaded and self._lora_state is None):
+            return self
+        if getattr(self, "lora_scale_fixed", None) is not None:      # (pipeline.fuse_lora: later scales have no effect)
+            scale = self.lora_scale_fixed
+        state = ads.state(scale)
+        if state == self._lora_state:
+            return self
+        net, pk = self.net, self.net.params
+        merged = {}
+        for stale in [k for k in self._lora_dev if k not in {(n, ads.gen[n]) for n in ads.loaded}]:
+            del self._lora_dev[stale]
+        for name, w in ads.active.items():
+            dev = self._lora_dev.get((name, ads.gen[name]))
+            if dev is None:
+                dev = self._lora_dev[(name, ads.gen[name])] = {
+                    m: (up.reshape(up.shape[0], -1).to(device=self._device, dtype=torch.float32).contiguous(),
+                        down.reshape(down.shape[0], -1).to(device=self._device, dtype=torch.float32).contiguous(),
+                        float(alpha) / down.shape[0]) for m, (down, up, alpha) in ads.loaded[name].items()}
+            for m, (up, down, a_over_r) in dev.items():
+                merged.setdefault(m, []).append((up, down, w * float(scale) * a_over_r))
+        recipes = net.recipes_of(merged) if merged else []
+        names = [r.name for r in recipes]
+        entries = lambda r: [e for e in (r.name, r.colsum, r.bias) if e]      # noqa: E731
+        source = None
+        if recipes:                         # (before anything is touched: a model without a kept state dict refuses here)
+            keys = set()
+            for r in recipes:
+                keys |= {m + ".weight" for m in r.sources()}
+                if r.gamma:
+                    keys |= {r.gamma + ".weight", r.gamma + ".bias"}
+                if r.badd:
+                    keys.add(r.badd)
+                if r.compose:
+                    keys.add(r.compose + ".bias")
+            source = self._lora_source(sorted(keys))
+        # entries that leave the merge go back to their snapshot; entries that enter it are snapshot first
+        for r in self._lora_dirty:
+            if r.name not in names:
+                for e in entries(r):
+                    pk.tensor(e).copy_(self._lora_snap[e])
+        for r in recipes:
+            for e in entries(r):
+                if e not in self._lora_snap:
+                    self._lora_snap[e] = pk.tensor(e).clone()
+        if recipes:
+            net.repack(list(merged), merged, source, torch.cuda.current_stream(self._device).cuda_stream)
+        self._lora_dirty = recipes
+        self._lora_state = state
+        if state is None:
+            self._lora_forget()
+        self.params_changed()
+        return self
 
     # ------------------------------------------------------------------
     def _wiring(self, down_add, mid_add, up_add, ctrl_down, ctrl_mid):
@@ -95,8 +221,9 @@ class UNet2DConditionModel(_HipModel):
                         ("down_intrablock_additional_residuals", down_intrablock_additional_residuals)):
             if v is not None:
                 raise NotImplementedError(f"{name} is outside the PowerPaint hot path (never set by the pipelines)")
-        if cross_attention_kwargs and cross_attention_kwargs.get("scale", 1.0) != 1.0:
-            raise NotImplementedError("LoRA scale != 1 is outside the hot path")
+        # LoRA scale (unet_2d_condition.py:1192-1195 of the reference): folded into the packed weights before the step
+        # runs; with no adapter loaded a scale is a no-op, as in the reference
+        self.merge_adapters((cross_attention_kwargs or {}).get("scale", 1.0))
         rt = self.prepare(tuple(sample.shape), encoder_hidden_states, down_block_add_samples, mid_block_add_sample,
                           up_block_add_samples, down_block_additional_residuals, mid_block_additional_residual)
         # the reference consumes the BrushNet lists destructively (.pop(0), unet_2d_condition.py:1223,1234,1318)

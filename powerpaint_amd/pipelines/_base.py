@@ -177,6 +177,115 @@ class PipelineBase(PipelinePretrainedMixin):
     def disable_xformers_memory_efficient_attention(self):
         return None
 
+    # ---- LoRA adapters (the reference's pipelines inherit LoraLoaderMixin, pipeline_PowerPaint_Brushnet_CA.py:147-148).
+    # Every active adapter is always MERGED into the packed weights (models/unet_2d_condition.py, models/clip_text.py); the
+    # call's `cross_attention_kwargs["scale"]` is folded in before the loop starts.  UNet keys go to `unet`, text-encoder keys
+    # to `text_encoder` only (`text_encoder_brushnet`, BrushNet, ControlNet and VAE take no adapters).
+    def _lora_components(self):
+        out = [("unet", self.unet)] if hasattr(self.unet, "merge_adapters") else []     # (duck-typed networks take none)
+        te = getattr(self, "text_encoder", None)
+        if te is not None and hasattr(te, "load_lora_adapter"):
+            out.append(("text_encoder", te))
+        return out
+
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, weight_name=None, adapter_name=None, **kwargs):
+        from ..lora import read_lora, text_targets, unet_targets
+        comps = dict(self._lora_components())
+        if "unet" not in comps:
+            raise L.PPError(f"{type(self.unet).__name__} takes no LoRA adapters")
+        ad = read_lora(pretrained_model_name_or_path_or_dict, weight_name, unet_targets(self.unet.net),
+                       text_targets(comps["text_encoder"]) if "text_encoder" in comps else {})
+        names = self.__dict__.setdefault("_lora_names", {})
+        if adapter_name is None:
+            i = 0
+            while f"default_{i}" in names:
+                i += 1
+            adapter_name = f"default_{i}"
+        if adapter_name in names:
+            raise ValueError(f"Adapter name {adapter_name} already in use in the pipeline")
+        if ad.text_encoder and "text_encoder" not in comps:
+            raise L.PPError(f"the adapter has text-encoder keys (e.g. {next(iter(ad.text_encoder))!r}) but the pipeline has "
+                            f"no text encoder that takes adapters")
+        parts, done = [c for c, fac in ad.components().items() if fac], []
+        try:
+            for c in parts:
+                comps[c].load_lora_adapter(ad, adapter_name)
+                done.append(c)
+        except Exception:
+            for c in done:                      # all components or none: no half-loaded name stays behind
+                comps[c].delete_adapters(adapter_name)
+            raise
+        names[adapter_name] = parts
+        return self
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        adapter_names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        if adapter_weights is None or not isinstance(adapter_weights, (list, tuple)):
+            adapter_weights = [adapter_weights] * len(adapter_names)
+        if len(adapter_weights) != len(adapter_names):
+            raise ValueError(f"Length of adapter names {len(adapter_names)} is not equal to the length of the weights "
+                             f"{len(adapter_weights)}")
+        names = self.__dict__.get("_lora_names", {})
+        for n in adapter_names:
+            if n not in names:
+                raise ValueError(f"Adapter {n!r} is not loaded (loaded: {sorted(names)})")
+        for c, m in self._lora_components():
+            pairs = [(n, w) for n, w in zip(adapter_names, adapter_weights) if c in names[n]]
+            m.set_adapters([n for n, _ in pairs], [w for _, w in pairs])
+
+    def get_active_adapters(self):
+        out = []
+        for _, m in self._lora_components():
+            out += [n for n in m.active_adapters() if n not in out]
+        return out
+
+    def get_list_adapters(self):
+        out = {}
+        for n, cs in self.__dict__.get("_lora_names", {}).items():
+            for c in cs:
+                out.setdefault(c, []).append(n)
+        return out
+
+    def delete_adapters(self, adapter_names):
+        adapter_names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        names = self.__dict__.get("_lora_names", {})
+        comps = dict(self._lora_components())
+        for n in adapter_names:
+            if n not in names:
+                raise ValueError(f"Adapter {n!r} is not loaded")
+            for c in names.pop(n):
+                comps[c].delete_adapters(n)
+        self.__dict__.pop("_prompt_memo", None)
+
+    def unload_lora_weights(self):
+        self.delete_adapters(list(self.__dict__.get("_lora_names", {})))
+        self.unfuse_lora()
+        self._merge_lora(None)
+
+    def fuse_lora(self, fuse_unet=True, fuse_text_encoder=True, lora_scale: float = 1.0, **kwargs):
+        """Kept for source compatibility: every adapter is merged anyway; this only fixes the scale (a later
+        `cross_attention_kwargs["scale"]` then has no effect, as after diffusers' fuse_lora)."""
+        self._lora_fused = float(lora_scale)
+        for _, m in self._lora_components():
+            m.__dict__["lora_scale_fixed"] = self._lora_fused      # (holds for direct calls of the models too)
+        self._merge_lora(None)
+
+    def unfuse_lora(self, **kwargs):
+        self.__dict__.pop("_lora_fused", None)
+        for _, m in self._lora_components():
+            m.__dict__.pop("lora_scale_fixed", None)
+
+    def _merge_lora(self, cross_attention_kwargs):
+        """Bring unet / text encoder to the call's LoRA scale and return it (a no-op for a model without adapters)."""
+        s = self.__dict__.get("_lora_fused")
+        if s is None:
+            s = (cross_attention_kwargs or {}).get("scale", 1.0)
+        for c, m in self._lora_components():
+            changed = m.merge_adapters(s)
+            if c == "text_encoder" and changed:
+                self.__dict__.pop("_prompt_memo", None)        # embeddings of the previous weights
+        return s
+
     def prepare_extra_step_kwargs(self, generator, eta):
         """pipeline_PowerPaint.py:536-551."""
         kw = {}
@@ -242,6 +351,9 @@ class PipelineBase(PipelinePretrainedMixin):
                        negative_promptA=None, negative_promptB=None, t_nag=None, prompt_embeds=None,
                        negative_prompt_embeds=None, lora_scale=None, text_encoder=None):
         text_encoder = text_encoder or getattr(self, "text_encoder", None)
+        if lora_scale is not None and text_encoder is getattr(self, "text_encoder", None) and \
+                hasattr(text_encoder, "merge_adapters") and text_encoder.merge_adapters(lora_scale):
+            self.__dict__.pop("_prompt_memo", None)
         # A call that passes the SAME embedding tensors as the previous one (unchanged storage and version counter) gets the
         # same result OBJECT: the networks then recognise their context and skip the per-prompt set-up (hoisted cross-attention
         # K / V, the folded projections: ~2 ms per call) instead of redoing it for an identical tensor.

@@ -91,9 +91,11 @@ class StableDiffusionInpaintPipeline(PipelineBase):
             batch_size = prompt_embeds.shape[0]
         device = self._execution_device
         do_cfg = guidance_scale > 1.0
+        lora_scale = self._merge_lora(cross_attention_kwargs)       # adapters folded into the weights before the loop
         prompt_embeds = self._encode_prompt(promptA, promptB, tradoff, device, num_images_per_prompt, do_cfg,
                                             negative_promptA, negative_promptB, tradoff_nag,
-                                            prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds)
+                                            prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
+                                            lora_scale=lora_scale)
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         timesteps, num_inference_steps = self.get_timesteps(num_inference_steps, strength, device)
         if num_inference_steps < 1:

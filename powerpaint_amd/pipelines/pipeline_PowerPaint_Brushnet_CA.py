@@ -137,12 +137,14 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
             batch_size = prompt_embeds.shape[0]
         device = self._execution_device
         do_cfg = self.do_classifier_free_guidance
+        lora_scale = self._merge_lora(cross_attention_kwargs)       # adapters folded into the weights before the loop
         prompt_embeds = self._encode_prompt(promptA, promptB, tradoff, device, num_images_per_prompt, do_cfg,
                                             negative_promptA, negative_promptB, tradoff_nag,
                                             prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                                             text_encoder=self.text_encoder_brushnet)
         prompt_embedsU = self.encode_prompt(promptU, device, num_images_per_prompt, do_cfg, negative_promptU,
-                                            prompt_embeds=prompt_embedsU, negative_prompt_embeds=negative_prompt_embedsU)
+                                            prompt_embeds=prompt_embedsU, negative_prompt_embeds=negative_prompt_embedsU,
+                                            lora_scale=lora_scale)
         nb = batch_size * num_images_per_prompt
         # 4./6.1 conditioning latents: [VAE latents of the masked image | latent-resolution keep-mask]
         if conditioning_latents is None:
