@@ -50,6 +50,41 @@ class PPGemmArgs(C.Structure):
     ]
 
 
+def gemm_args(dtype: int, M: int, N: int, K: int, x, w, out, x2=None, K2: int = 0, ldx=None, ldx2: int = 0, ldo: int = 0,
+              ldres1: int = 0, ldres2: int = 0, rows_per_batch: int = 0, scale: float = 1.0) -> PPGemmArgs:
+    """The geometry of a PP_X_PLAIN request, out[M][N] = epilogue(concat(x[M][K], x2[M][K2]) @ w[N][K + K2]^T), from raw
+    pointers and integers; leading dimensions default to dense rows.  The caller adds what is its own: epilogue operands,
+    tile / split wishes, subscriptions, workspace."""
+    a = PPGemmArgs()
+    a.dtype = dtype
+    a.M, a.N, a.K, a.x_mode = M, N, K + K2, PP_X_PLAIN
+    a.x1, a.x2, a.c1, a.c2 = x, x2 or None, K, K2
+    a.ldx1, a.ldx2 = (K if ldx is None else ldx), (ldx2 or K2)
+    a.w, a.out = w, out
+    a.ldo, a.ldres1, a.ldres2 = ldo or N, ldres1 or N, ldres2 or N
+    a.rows_per_batch, a.scale = rows_per_batch, scale
+    return a
+
+
+def conv3x3_args(dtype: int, B: int, H: int, W: int, c1: int, cout: int, x, x2=None, c2: int = 0, x3=None, c3: int = 0,
+                 x4=None, c4: int = 0, stride: int = 1, up: bool = False, w=None, out=None, scale: float = 1.0) -> PPGemmArgs:
+    """The geometry of a PP_X_CONV3X3 request: conv3x3 (padding 1) over concat(x, x2) NHWC [B][H][W][c1 + c2], after a nearest
+    2x upsample if `up`, + a 1x1 tail over concat(x3, x4) at the output pixel -> NHWC [B][hout][wout][cout] (a.hout / a.wout:
+    a caller that sizes `out` from them sets a.out afterwards)."""
+    hv, wv = (2 * H, 2 * W) if up else (H, W)
+    ho, wo = (hv - 1) // stride + 1, (wv - 1) // stride + 1
+    a = PPGemmArgs()
+    a.dtype = dtype
+    a.M, a.N, a.K, a.x_mode = B * ho * wo, cout, 9 * (c1 + c2) + c3 + c4, PP_X_CONV3X3
+    a.x1, a.x2, a.c1, a.c2 = x, x2 or None, c1, c2
+    a.x3, a.x4, a.c3, a.c4 = x3 or None, x4 or None, c3, c4
+    a.batch, a.hin, a.win, a.hout, a.wout, a.stride, a.up = B, H, W, ho, wo, stride, int(up)
+    a.w, a.out = w, out
+    a.ldo, a.ldres1, a.ldres2 = cout, cout, cout
+    a.rows_per_batch, a.scale = ho * wo, scale
+    return a
+
+
 PP_LORA_MAX_ADAPTERS, PP_LORA_MAX_RANK = 8, 128
 PP_LORA_ROWS_PLAIN, PP_LORA_ROWS_GEGLU = 0, 1
 PP_LORA_COLS_PLAIN, PP_LORA_COLS_IGEMM, PP_LORA_COLS_KPERM, PP_LORA_COLS_KPERM_GEGLU = 0, 1, 2, 3

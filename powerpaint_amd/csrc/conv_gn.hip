@@ -657,7 +657,7 @@ __global__ void __launch_bounds__(CG_T, 2) pp_conv_gn_kernel(const PPGemmArgs a,
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     gn_flush(a, slots, m_blk, n_blk, ncols, tid);
   }
-  // (ABI v21) the split-K combine by the workgroup that arrives last at its tile (gemm_combine.h)
+  // (ABI v21) the split-K combine inside this kernel: every split combines its own share of the tile (gemm_combine.h)
   if (splitk && a.tile_ctr) {
     static_assert(fc_lds_bytes(BM) <= CG_LDS, "fused combine staging must fit in the kernel's LDS");
     splitk_fused_combine<BM, T, EDT>(a, smem, m_blk, n_blk, blockIdx.x, blockIdx.y, splits, tid);
@@ -665,10 +665,6 @@ __global__ void __launch_bounds__(CG_T, 2) pp_conv_gn_kernel(const PPGemmArgs a,
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-struct CGChoice {
-  int bm, splitk;
-};
-
 // the loader's geometry: stride 1, no upsample, tiles of whole image rows inside one image, halo tile <= 384 pixels
 bool cg_shape_ok(const PPGemmArgs& a, int bm) {
   const int hw = a.hout * a.wout;
@@ -715,7 +711,6 @@ bool cg_raw_ok(const PPGemmArgs& a) {
   if (a.gn_in_acc || a.gn_in_gb || a.tile != PP_TILE_AUTO || min_w <= 0 || a.wout < min_w) return false;
   return cg_geometry_ok(a);
 }
-bool cg_supported(const PPGemmArgs& a) { return a.gn_in_acc ? cg_fused_ok(a) : cg_raw_ok(a); }
 
 CGChoice cg_choose(const PPGemmArgs& a) {
   const int tn = (a.N + 159) / 160;
@@ -843,15 +838,19 @@ int cg_dispatch(const PPGemmArgs& a, const CGChoice& c, hipStream_t st) {
 
 }  // namespace
 
-// entry points used by gemm.hip's pp_gemm_bf16 / pp_gemm_workspace_bytes (one C-ABI call per conv, whichever kernel runs)
-// does this conv3x3 request run on the halo-tile kernel: the fused norm (asked for by gn_in_*; pp_gemm_bf16 refuses what the
-// kernel cannot do, never a silent fallback) or a plain conv the library routes there (cg_raw_ok)
-bool pp_conv_gn_wanted(const PPGemmArgs& a) { return a.x_mode == PP_X_CONV3X3 && (a.gn_in_acc != nullptr || cg_raw_ok(a)); }
-int pp_conv_gn_splitk(const PPGemmArgs& a) { return cg_supported(a) ? cg_choose(a).splitk : 0; }
-int pp_conv_gn_bm(const PPGemmArgs& a) { return cg_supported(a) ? cg_choose(a).bm : 0; }
-int pp_conv_gn_run(const PPGemmArgs& a, hipStream_t st) {
-  if (!cg_supported(a)) return PP_ERR_UNSUPPORTED;
-  const CGChoice c = cg_choose(a);
+// pp_common.h: the one place a request is routed to this kernel and its form chosen -- the fused norm (asked for by gn_in_*)
+// or a plain conv the library sends here (cg_raw_ok)
+int pp_conv_gn_form(const PPGemmArgs& a, CGChoice* c) {
+  if (a.x_mode != PP_X_CONV3X3) return 0;
+  if (a.gn_in_acc) {
+    if (!cg_fused_ok(a)) return PP_ERR_UNSUPPORTED;
+  } else if (!cg_raw_ok(a)) {
+    return 0;
+  }
+  *c = cg_choose(a);
+  return 1;
+}
+int pp_conv_gn_run(const PPGemmArgs& a, const CGChoice& c, hipStream_t st) {
   if (c.splitk > 1 && !a.workspace) return PP_ERR_WORKSPACE;
   return a.dtype == PP_DT_F16 ? cg_dispatch<PP_DT_F16>(a, c, st) : cg_dispatch<PP_DT_BF16>(a, c, st);
 }

@@ -1213,8 +1213,8 @@ pp_gemm_kernel_v2(const PPGemmArgs a, const GemmDerived d) {   // 2nd bound = wa
   }
   if (GNS && !splitk && !gn_per_pass) gn_fold_block(m_blk, true);
   if constexpr (EPI == 0 && PP) {
-    // (ABI v21) the split-K combine by the workgroup that arrives last at its tile (gemm_combine.h); a.tile_ctr is set by
-    // the host only where every split of a tile runs on one XCD and the epilogue is the lean combine's
+    // (ABI v21) the split-K combine inside this kernel: every split combines its own share of the tile (gemm_combine.h);
+    // a.tile_ctr is set by the host only where every split of a tile runs on one XCD and the epilogue is the lean combine's
     if (splitk && a.tile_ctr) {
       static_assert(fc_lds_bytes(BM) <= NS * STAGE, "fused combine staging must fit in the pipeline stages");
       splitk_fused_combine<BM, T, EDT>(a, smem, m_blk, n_blk, blockIdx.x, blockIdx.y, gridDim.y, tid);
@@ -1485,6 +1485,40 @@ bool reduce_lean_ok(const PPGemmArgs& a) {
          (!a.res1 || a.ldres1 % 8 == 0) && (!a.res2 || a.ldres2 % 8 == 0);
 }
 
+// Every tile form pp_gemm_bf16 can run, once: X(id, BM, WM, NS, PP, V2) -- rows of the tile (160 columns always), waves along
+// M (two along N), pipeline stages, ping-pong main loop, LDS-direct v2 kernel (else the register-staged v1 kernel, which has
+// two stages).  Ids 1 .. 3 are PP_TILE_* of the header; the others are internal: choose() emits them, tests and tools pass
+// them in PPGemmArgs.tile.  dispatch() and tile_form() are generated from this list.
+#define PP_TILE_FORMS(X)                                                                                         \
+  X(PP_TILE_128x160, 128, 2, 2, false, false)                                                                    \
+  X(PP_TILE_64x160, 64, 2, 2, false, false)                                                                      \
+  X(PP_TILE_256x160, 256, 4, 2, false, false)                                                                    \
+  X(21, 128, 2, 2, false, true)                                                                                  \
+  X(31, 128, 2, 3, false, true)                                                                                  \
+  X(22, 64, 2, 2, false, true)                                                                                   \
+  X(32, 64, 2, 3, false, true)                                                                                   \
+  X(42, 64, 2, 4, false, true)                                                                                   \
+  X(62, 64, 2, 5, false, true) /* five stages: 140 KB, one block per CU */                                       \
+  X(23, 256, 4, 2, false, true)                                                                                  \
+  X(33, 256, 4, 3, false, true)                                                                                  \
+  X(24, 128, 4, 2, false, true) /* 8-wave 128x160 (wave tile 32x80): 4 waves / SIMD, two co-resident blocks */   \
+  X(53, 256, 4, 3, true, true)  /* ping-pong 8-wave tiles (one block per CU) */                                  \
+  X(44, 128, 4, 3, true, true)                                                                                   \
+  X(54, 128, 4, 4, true, true)
+
+struct TileForm {
+  int id, bm;
+  bool pp, v2;
+};
+#define PP_ROW(ID, BM_, WM_, NS_, PP_, V2_) {ID, BM_, PP_, V2_},
+constexpr TileForm TILE_FORMS[] = {PP_TILE_FORMS(PP_ROW)};
+#undef PP_ROW
+const TileForm* tile_form(int id) {
+  for (const TileForm& t : TILE_FORMS)
+    if (t.id == id) return &t;
+  return nullptr;
+}
+
 struct Choice {
   int tile, splitk;
 };
@@ -1631,19 +1665,24 @@ int launch_combine(const PPGemmArgs& a, int splitk, hipStream_t st) {
   return PP_OK;
 }
 
+GemmDerived derive(const PPGemmArgs& a, int bm, int bn, int splitk) {
+  GemmDerived d;
+  d.tiles_m = (a.M + bm - 1) / bm;
+  d.tiles_n = (a.N + bn - 1) / bn;
+  d.kt_total = a.K / 64;
+  d.kt_per_split = (d.kt_total + splitk - 1) / splitk;
+  d.ctiles = (a.c1 + a.c2) / 64;
+  d.n_major = (gemm_n_major() && d.tiles_m < d.tiles_n && d.tiles_m <= 8) ? 1 : 0;
+  return d;
+}
+
 template <int BM, int BN, int WM, int WN, int XMODE, int EDT>
 int launch(const PPGemmArgs& a, int splitk, hipStream_t st) {
   constexpr int T = WM * WN * 64;
   constexpr int LDS = 2 * (BM + BN) * 128;
   auto kern = pp_gemm_kernel<BM, BN, WM, WN, XMODE, EDT>;
   if (pp_func_lds(reinterpret_cast<const void*>(kern), LDS, "hipFuncSetAttribute(gemm)") != PP_OK) return PP_ERR_LAUNCH;
-  GemmDerived d;
-  d.tiles_m = (a.M + BM - 1) / BM;
-  d.tiles_n = (a.N + BN - 1) / BN;
-  d.kt_total = a.K / 64;
-  d.kt_per_split = (d.kt_total + splitk - 1) / splitk;
-  d.ctiles = (a.c1 + a.c2) / 64;
-  d.n_major = (gemm_n_major() && d.tiles_m < d.tiles_n && d.tiles_m <= 8) ? 1 : 0;
+  const GemmDerived d = derive(a, BM, BN, splitk);
   dim3 grid(d.tiles_m * d.tiles_n, splitk, 1);
   hipLaunchKernelGGL(kern, grid, dim3(T), LDS, st, a, d);
   PP_CHECK_LAUNCH("pp_gemm_kernel");
@@ -1700,17 +1739,11 @@ int launch2(const PPGemmArgs& a, int splitk, hipStream_t st) {
   auto kern = pp_gemm_kernel_v2<BM, BN, WM, WN, XMODE, NS, EPI, (NS >= 3 && !PP), PP, EDT>;
 #endif
   if (pp_func_lds(reinterpret_cast<const void*>(kern), LDS, "hipFuncSetAttribute(gemm v2)") != PP_OK) return PP_ERR_LAUNCH;
-  GemmDerived d;
-  d.tiles_m = (a.M + BM - 1) / BM;
-  d.tiles_n = (a.N + BN - 1) / BN;
-  d.kt_total = a.K / 64;
-  d.kt_per_split = (d.kt_total + splitk - 1) / splitk;
-  d.ctiles = (a.c1 + a.c2) / 64;
-  d.n_major = (gemm_n_major() && d.tiles_m < d.tiles_n && d.tiles_m <= 8) ? 1 : 0;
+  const GemmDerived d = derive(a, BM, BN, splitk);
   dim3 grid(d.tiles_m * d.tiles_n, splitk, 1);
   hipLaunchKernelGGL(kern, grid, dim3(T), LDS, st, a, d);
   PP_CHECK_LAUNCH("pp_gemm_kernel_v2");
-  if (splitk > 1 && !a.tile_ctr) return launch_combine<EDT>(a, splitk, st);   // (tile_ctr: combined by the last arriver)
+  if (splitk > 1 && !a.tile_ctr) return launch_combine<EDT>(a, splitk, st);   // (tile_ctr: every split combined its share in-kernel)
   return PP_OK;
   }
 }
@@ -1794,33 +1827,66 @@ int validate(const PPGemmArgs& a) {
   return PP_OK;
 }
 
+// ---- the launch form ----------------------------------------------------------------------------------------------------
+// In what form does a validated request run?  Resolved ONCE per call, by resolve_form(): pp_gemm_bf16 and the six queries
+// around it (workspace size, statistics / consumer-norm eligibility, counters and verdict of the in-kernel combine) read
+// this and nothing else, so what a planner is told is what is launched.
+enum class Family { V1, V2, HALO };   // register-staged kernel / LDS-direct kernel / halo-tile conv kernel (conv_gn.hip)
+struct LaunchForm {
+  Family family;
+  int tile;        // id in PP_TILE_FORMS (V1 / V2), 0 on the halo-tile kernel
+  int bm, tiles;   // rows of an output tile, output tiles of the launch
+  int splitk;      // K splits that run (> 1: fp32 slabs in the workspace, combined in-kernel or by a launch behind it)
+  bool pp_tile;    // an 8-wave ping-pong tile (every halo-tile kernel that ships is one)
+  // A V1 launch splits K and combines with the separate kernels like the others, but its register-staged epilogue has no
+  // GroupNorm statistics, no row moments and no in-kernel combine, and pp_gemm_bf16 hands its combine no consumer norm.
+  bool staged_epilogue() const { return family != Family::V1; }
+};
+
+// PP_OK, or why nothing runs: PP_ERR_UNSUPPORTED = gn_in_* asks for the fused-norm conv and conv_gn.hip cannot do the shape;
+// PP_ERR_BAD_ARG = PPGemmArgs.tile names no tile form
+int resolve_form(const PPGemmArgs& a, LaunchForm* f) {
+  const int tn = (a.N + 159) / 160;
+  CGChoice cg;
+  const int halo = pp_conv_gn_form(a, &cg);
+  if (halo < 0) return halo;
+  if (halo) {
+    *f = LaunchForm{Family::HALO, 0, cg.bm, (a.M / cg.bm) * tn, cg.splitk, true};
+    return PP_OK;
+  }
+  const Choice c = choose(a);
+  const TileForm* t = tile_form(c.tile);
+  if (!t) return PP_ERR_BAD_ARG;
+  *f = LaunchForm{t->v2 ? Family::V2 : Family::V1, t->id, t->bm, ((a.M + t->bm - 1) / t->bm) * tn, c.splitk, t->pp};
+  return PP_OK;
+}
+
+// can the combine behind this launch apply the consumer GroupNorm of subscription `sub` (PPGemmArgs.gn_next_*)?
+bool gn_next_ok(const PPGemmArgs& a, const LaunchForm& f, int sub) {
+  return f.staged_epilogue() && f.splitk > 1 && gn_next_shape_ok(a, sub);
+}
+
+// can this launch combine its slabs in-kernel?  (with_consumers / advice: see fused_combine_shape_ok)
+bool combine_fusable(const PPGemmArgs& a, const LaunchForm& f, bool with_consumers, bool advice) {
+  return f.staged_epilogue() && fused_combine_shape_ok(a, f.bm, f.tiles, f.splitk, f.pp_tile, with_consumers, advice);
+}
+
+template <bool V2, int BM, int WM, int NS, bool PP, int XMODE, int EDT>
+int launch_tile(const PPGemmArgs& a, int splitk, hipStream_t st) {
+  if constexpr (V2) return launch2<BM, 160, WM, 2, XMODE, NS, 0, PP, EDT>(a, splitk, st);
+  else return launch<BM, 160, WM, 2, XMODE, EDT>(a, splitk, st);
+}
+
 template <int EDT>
-int dispatch(const PPGemmArgs& a, const Choice& c, hipStream_t st) {
+int dispatch(const PPGemmArgs& a, const LaunchForm& f, hipStream_t st) {
   const bool conv = a.x_mode == PP_X_CONV3X3;
-  switch (c.tile) {
-    case PP_TILE_128x160:
-      return conv ? launch<128, 160, 2, 2, PP_X_CONV3X3, EDT>(a, c.splitk, st) : launch<128, 160, 2, 2, PP_X_PLAIN, EDT>(a, c.splitk, st);
-    case PP_TILE_64x160:
-      return conv ? launch<64, 160, 2, 2, PP_X_CONV3X3, EDT>(a, c.splitk, st) : launch<64, 160, 2, 2, PP_X_PLAIN, EDT>(a, c.splitk, st);
-    case PP_TILE_256x160:
-      return conv ? launch<256, 160, 4, 2, PP_X_CONV3X3, EDT>(a, c.splitk, st) : launch<256, 160, 4, 2, PP_X_PLAIN, EDT>(a, c.splitk, st);
-#define PP_V2(ID, BM_, WM_, NS_, PP_)                                                                     \
-    case ID:                                                                                             \
-      return conv ? launch2<BM_, 160, WM_, 2, PP_X_CONV3X3, NS_, 0, PP_, EDT>(a, c.splitk, st)           \
-                  : launch2<BM_, 160, WM_, 2, PP_X_PLAIN, NS_, 0, PP_, EDT>(a, c.splitk, st);
-      PP_V2(21, 128, 2, 2, false)
-      PP_V2(31, 128, 2, 3, false)
-      PP_V2(22, 64, 2, 2, false)
-      PP_V2(32, 64, 2, 3, false)
-      PP_V2(42, 64, 2, 4, false)
-      PP_V2(62, 64, 2, 5, false)    // (five stages: 140 KB, one block per CU)
-      PP_V2(23, 256, 4, 2, false)
-      PP_V2(33, 256, 4, 3, false)
-      PP_V2(24, 128, 4, 2, false)   // 8-wave 128x160 (wave tile 32x80): 4 waves / SIMD with two co-resident blocks
-      PP_V2(53, 256, 4, 3, true)    // ping-pong 8-wave tiles (one block per CU)
-      PP_V2(44, 128, 4, 3, true)
-      PP_V2(54, 128, 4, 4, true)
-#undef PP_V2
+  switch (f.tile) {
+#define PP_CASE(ID, BM_, WM_, NS_, PP_, V2_)                                                         \
+    case ID:                                                                                         \
+      return conv ? launch_tile<V2_, BM_, WM_, NS_, PP_, PP_X_CONV3X3, EDT>(a, f.splitk, st)         \
+                  : launch_tile<V2_, BM_, WM_, NS_, PP_, PP_X_PLAIN, EDT>(a, f.splitk, st);
+    PP_TILE_FORMS(PP_CASE)
+#undef PP_CASE
     default:
       return PP_ERR_BAD_ARG;
   }
@@ -1828,113 +1894,74 @@ int dispatch(const PPGemmArgs& a, const Choice& c, hipStream_t st) {
 
 }  // namespace
 
-// conv_gn.hip: GroupNorm + SiLU of the conv input fused into the loader (PPGemmArgs.gn_in_acc)
-bool pp_conv_gn_wanted(const PPGemmArgs& a);
-int pp_conv_gn_splitk(const PPGemmArgs& a);       // 0 = shape not supported by the fused kernel
-int pp_conv_gn_bm(const PPGemmArgs& a);           // rows of the tile it runs on (0 = not supported)
-int pp_conv_gn_run(const PPGemmArgs& a, hipStream_t st);
+// validate + resolve_form for a query: false = the request does not run (every query then answers 0)
+static bool query_form(const PPGemmArgs* args, LaunchForm* f) {
+  return args && validate(*args) == PP_OK && resolve_form(*args, f) == PP_OK;
+}
 
 extern "C" int pp_gemm_gn_stats_ok(const PPGemmArgs* args) {
   if (!args) return 0;
-  PPGemmArgs a = *args;
+  PPGemmArgs a = *args;                      // (asked BEFORE the subscription is patched in, or with another one in place)
   a.gn_acc[0] = a.gn_acc[1] = nullptr;
   a.gn_dup_mask = 0;
-  if (validate(a) != PP_OK || !gn_stats_supported(a)) return 0;
-  if (pp_conv_gn_wanted(a)) return pp_conv_gn_splitk(a) > 0 ? 1 : 0;
-  const Choice c = choose(a);
-  return c.tile > 10 ? 1 : 0;
-}
-
-// the split-K factor pp_gemm_bf16 will run this launch with (1 = no combine launch behind it)
-static int planned_splitk(const PPGemmArgs& a) {
-  if (pp_conv_gn_wanted(a)) return pp_conv_gn_splitk(a);
-  const Choice c = choose(a);
-  return c.tile > 10 ? c.splitk : 1;
+  LaunchForm f;
+  return (query_form(&a, &f) && gn_stats_supported(a) && f.staged_epilogue()) ? 1 : 0;
 }
 
 extern "C" int pp_gemm_gn_next_ok(const PPGemmArgs* args, int sub) {
-  if (!args || validate(*args) != PP_OK) return 0;
-  return (planned_splitk(*args) > 1 && gn_next_shape_ok(*args, sub)) ? 1 : 0;
+  LaunchForm f;
+  return (query_form(args, &f) && gn_next_ok(*args, f, sub)) ? 1 : 0;
 }
 
-// the form pp_gemm_bf16 runs this request in, as the fused-combine predicate sees it
-struct PlannedForm {
-  int bm, tiles, splitk;
-  bool pp_tile;
-};
-static PlannedForm planned_form(const PPGemmArgs& a) {
-  PlannedForm f{0, 0, 1, false};
-  const int tn = (a.N + 159) / 160;
-  if (pp_conv_gn_wanted(a)) {
-    f.splitk = pp_conv_gn_splitk(a);
-    f.bm = pp_conv_gn_bm(a);
-    f.pp_tile = f.bm > 0;                        // (the shipping fused-norm kernels are all 8-wave ping-pong tiles)
-  } else {
-    const Choice c = choose(a);
-    f.splitk = c.tile > 10 ? c.splitk : 1;
-    f.pp_tile = c.tile == 53 || c.tile == 44 || c.tile == 54;
-    f.bm = c.tile == 53 ? 256 : 128;
-  }
-  if (f.bm > 0) f.tiles = ((a.M + f.bm - 1) / f.bm) * tn;
-  return f;
-}
-
+// advice to a planner: the tile counters to hand over where the in-kernel combine wins
 extern "C" size_t pp_gemm_combine_ctr_bytes(const PPGemmArgs* args) {
-  if (!args || validate(*args) != PP_OK) return 0;
-  const PlannedForm f = planned_form(*args);
-  if (!fused_combine_shape_ok(*args, f.bm, f.tiles, f.splitk, f.pp_tile, false, true)) return 0;
+  LaunchForm f;
+  if (!query_form(args, &f) || !combine_fusable(*args, f, false, true)) return 0;
   if (!pp_xcd_placement_ok()) return 0;
   return (size_t)f.tiles * FC_CTR_BYTES;
 }
 
-static bool combine_fused(const PPGemmArgs& a) {
-  if (!a.tile_ctr) return false;
-  const PlannedForm f = planned_form(a);
-  return fused_combine_shape_ok(a, f.bm, f.tiles, f.splitk, f.pp_tile, true, false);
-}
+// (ADVICE round 6, item 2 -- the cached placement verdict as part of this decision -- would go here)
+static bool combine_fused(const PPGemmArgs& a, const LaunchForm& f) { return a.tile_ctr && combine_fusable(a, f, true, false); }
 
 extern "C" int pp_gemm_combine_fused(const PPGemmArgs* args) {
-  return (args && validate(*args) == PP_OK && combine_fused(*args)) ? 1 : 0;
+  LaunchForm f;
+  return (query_form(args, &f) && combine_fused(*args, f)) ? 1 : 0;
 }
 
-// the fp32 slabs of a split-K launch + (behind them) the per-tile scratch of the in-kernel combine (gemm_combine.h)
+// the fp32 slabs of a split-K launch + (behind them) the per-tile scratch of the in-kernel combine (gemm_combine.h), counted
+// wherever the launch COULD fuse: consumers are patched in and counters handed out after the workspace is sized
 extern "C" size_t pp_gemm_workspace_bytes(const PPGemmArgs* args) {
-  if (!args || validate(*args) != PP_OK) return 0;
-  const PlannedForm f = planned_form(*args);
-  const int sk = pp_conv_gn_wanted(*args) ? f.splitk : choose(*args).splitk;
-  if (sk <= 1) return 0;
-  const size_t scratch = fused_combine_shape_ok(*args, f.bm, f.tiles, f.splitk, f.pp_tile, false, false) ? (size_t)f.tiles * FC_SCR_BYTES : 0;
-  return (size_t)sk * args->M * args->N * sizeof(float) + scratch;
+  LaunchForm f;
+  if (!query_form(args, &f) || f.splitk <= 1) return 0;
+  const size_t scratch = combine_fusable(*args, f, false, false) ? (size_t)f.tiles * FC_SCR_BYTES : 0;
+  return (size_t)f.splitk * args->M * args->N * sizeof(float) + scratch;
 }
-
 
 extern "C" int pp_gemm_bf16(const PPGemmArgs* args, void* stream) {
   if (!args) return PP_ERR_BAD_ARG;
   const int v = validate(*args);
   if (v != PP_OK) return v;
+  LaunchForm f;
+  const int rf = resolve_form(*args, &f);
+  if (rf != PP_OK) return rf;
   // tile_ctr is a permission: the kernels see it only where the launch is eligible for the in-kernel combine
   PPGemmArgs a_ = *args;
-  const bool fused = combine_fused(a_);
+  const bool fused = combine_fused(a_, f);
   if (!fused) a_.tile_ctr = nullptr;
   const PPGemmArgs& a = a_;
-  if (a.gn_next_out && !(planned_splitk(a) > 1 && gn_next_shape_ok(a, a.gn_next_sub))) return PP_ERR_UNSUPPORTED;
-  if (pp_conv_gn_wanted(a)) {      // norm -> SiLU -> conv3x3 as one launch (no silent fallback: pp_conv_gn_supported() tells)
-    const int sk = pp_conv_gn_splitk(a);
-    if (sk <= 0) return PP_ERR_UNSUPPORTED;
-    if ((a.gn_acc[0] || a.gn_acc[1]) && !gn_stats_supported(a)) return PP_ERR_UNSUPPORTED;
-    const int rc = pp_conv_gn_run(a, (hipStream_t)stream);
-    if (rc != PP_OK || sk == 1 || fused) return rc;
-    return a.dtype == PP_DT_F16 ? launch_combine<PP_DT_F16>(a, sk, (hipStream_t)stream)
-                                : launch_combine<PP_DT_BF16>(a, sk, (hipStream_t)stream);
-  }
-  const Choice c = choose(a);
-  if (c.splitk > 1 && !a.workspace) return PP_ERR_WORKSPACE;
-  if (c.tile > 10 && !v2_ok(a)) return PP_ERR_BAD_ARG;
-  if (a.out_dup_rows > 0 && (c.tile < 10 || c.splitk > 1)) return PP_ERR_UNSUPPORTED;   // single-pass staged epilogue only
-  if ((a.row_stats_out || a.gn_acc[0] || a.gn_acc[1] || (a.x_mode == PP_X_CONV3X3 && a.c3 > 0)) &&
-      c.tile < 10)
-    return PP_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  if (a.dtype == PP_DT_F16) return dispatch<PP_DT_F16>(a, c, st);
-  return dispatch<PP_DT_BF16>(a, c, st);
+  if (a.gn_next_out && !gn_next_ok(a, f, a.gn_next_sub)) return PP_ERR_UNSUPPORTED;
+  if (f.family == Family::HALO) {      // norm -> SiLU -> conv3x3 (or the plain conv) as one launch of the halo-tile kernel
+    if ((a.gn_acc[0] || a.gn_acc[1]) && !gn_stats_supported(a)) return PP_ERR_UNSUPPORTED;
+    const int rc = pp_conv_gn_run(a, CGChoice{f.bm, f.splitk}, st);
+    if (rc != PP_OK || f.splitk == 1 || fused) return rc;
+    return a.dtype == PP_DT_F16 ? launch_combine<PP_DT_F16>(a, f.splitk, st) : launch_combine<PP_DT_BF16>(a, f.splitk, st);
+  }
+  if (f.splitk > 1 && !a.workspace) return PP_ERR_WORKSPACE;
+  if (f.family == Family::V2 && !v2_ok(a)) return PP_ERR_BAD_ARG;
+  if (a.out_dup_rows > 0 && (!f.staged_epilogue() || f.splitk > 1)) return PP_ERR_UNSUPPORTED;   // single-pass staged epilogue only
+  if ((a.row_stats_out || a.gn_acc[0] || a.gn_acc[1] || (a.x_mode == PP_X_CONV3X3 && a.c3 > 0)) && !f.staged_epilogue())
+    return PP_ERR_UNSUPPORTED;
+  return a.dtype == PP_DT_F16 ? dispatch<PP_DT_F16>(a, f, st) : dispatch<PP_DT_BF16>(a, f, st);
 }

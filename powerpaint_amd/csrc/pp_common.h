@@ -133,6 +133,14 @@ void pp_set_last_error(const char* what, hipError_t e);
 int pp_func_lds(const void* kern, int bytes, const char* what);
 // compute units of the current device (pp_api.cpp; cached)
 int pp_cu_count();
+// The halo-tile conv kernel (conv_gn.hip) as pp_gemm_bf16 and the queries around it (gemm.hip) see it.  pp_conv_gn_form: does
+// this validated request run on it -- 1, *c = the tile rows and K splits it runs with; 0, the tap-major implicit GEMM runs it;
+// PP_ERR_UNSUPPORTED, gn_in_* asks for the fused norm and the kernel cannot do the shape (never a silent fallback).
+struct CGChoice {
+  int bm, splitk;
+};
+int pp_conv_gn_form(const PPGemmArgs& a, CGChoice* c);
+int pp_conv_gn_run(const PPGemmArgs& a, const CGChoice& c, hipStream_t st);
 #define PP_CHECK_LAUNCH(what)                         \
   do {                                                \
     hipError_t e__ = hipGetLastError();               \

@@ -44,7 +44,7 @@ FUSE_GN_CONV = _lab_switch("PP_FUSE_GN_CONV")
 # round 5: the CFG-identical prefix of a forward pass (conv_in .. first self-attention) on ONE half of the batch where the
 # caller vouches for identical halves (SDNet.build_step(twin=True)).  (lab) PP_TWIN=0: the whole batch everywhere
 TWIN_PREFIX = _lab_switch("PP_TWIN")
-# round 6: the split-K combine inside the producing kernel, by the workgroup that arrives last at its tile
+# round 6: the split-K combine inside the producing kernel, every split combining its own share of the tile
 # (csrc/gemm_combine.h, PPGemmArgs.tile_ctr).  (lab) PP_FUSED_COMBINE=0: the separate combine launches
 FUSED_COMBINE = _lab_switch("PP_FUSED_COMBINE")
 
@@ -292,18 +292,11 @@ class Builder:
         if not out:
             out = self.alloc(rows * ldo * (4 if out_f32 else 2))
         m = self.mark()
-        a = L.PPGemmArgs()
-        a.M, a.N, a.K, a.x_mode = rows, N, K + K2, L.PP_X_PLAIN
-        a.x1, a.x2, a.c1, a.c2 = x, x2 or None, K, K2
-        a.ldx1, a.ldx2 = (ldx if ldx is not None else K), (ldx2 or K2)
-        a.w, a.bias = w, bias or None
-        a.w_batch_stride, a.vec_batch_stride = w_batch_stride, vec_batch_stride
-        a.rowvec, a.ld_rowvec, a.rows_per_batch = rowvec or None, ld_rowvec, rows_per_batch
-        a.res1, a.ldres1 = res1 or None, ldres1 or N
-        a.res1_wrap_rows = res1_wrap
-        a.res2, a.ldres2 = res2 or None, ldres2 or N
-        a.scale, a.act = scale, act
-        a.out, a.ldo, a.out_f32 = out, ldo, int(out_f32)
+        a = L.gemm_args(self.dt, rows, N, K, x, w, out, x2=x2, K2=K2, ldx=ldx, ldx2=ldx2, ldo=ldo, ldres1=ldres1, ldres2=ldres2,
+                        rows_per_batch=rows_per_batch, scale=scale)
+        a.bias, a.rowvec, a.ld_rowvec, a.res1, a.res2 = bias or None, rowvec or None, ld_rowvec, res1 or None, res2 or None
+        a.w_batch_stride, a.vec_batch_stride, a.res1_wrap_rows = w_batch_stride, vec_batch_stride, res1_wrap
+        a.act, a.out_f32 = act, int(out_f32)
         a.out_vt, a.vt_col0, a.vt_ld = out_vt or None, vt_col0, vt_ld
         a.row_stats_out = row_stats_out or None
         if ln_stats:
@@ -331,8 +324,12 @@ class Builder:
                 x, x2 = self.groupnorm(x, gamma, beta, eps, True, x2=x2, groups=groups), None
         else:
             fused = None
-        hv, wv = (x.H * 2, x.W * 2) if up else (x.H, x.W)
-        ho, wo = (hv + 2 - 3) // stride + 1, (wv + 2 - 3) // stride + 1
+        c2 = x2.C if x2 is not None else 0
+        ptr = lambda t: t.ptr if t is not None else None      # noqa: E731
+        # (x3, x4: the 1x1 tail over concat(x3, x4) at the output pixel -- the merged conv_shortcut)
+        a = L.conv3x3_args(self.dt, x.B, x.H, x.W, x.C, cout, x.ptr, ptr(x2), c2, ptr(x3), x3.C if x3 is not None else 0,
+                           ptr(x4), x4.C if x4 is not None else 0, stride, up, w=w, scale=scale)
+        ho, wo = a.hout, a.wout
         if dup:
             assert out is None and gn_in is None
             out = self.new_act(2 * x.B, ho, wo, cout)
@@ -340,30 +337,13 @@ class Builder:
         if out is None:
             out = self.new_act(x.B, ho, wo, cout)
         m = self.mark()
-        a = L.PPGemmArgs()
-        c2 = x2.C if x2 is not None else 0
-        c3 = x3.C if x3 is not None else 0
-        c4 = x4.C if x4 is not None else 0
-        a.M, a.N, a.K, a.x_mode = x.B * ho * wo, cout, 9 * (x.C + c2) + c3 + c4, L.PP_X_CONV3X3
-        a.x1, a.x2, a.c1, a.c2 = x.ptr, (x2.ptr if x2 is not None else None), x.C, c2
-        if x3 is not None:          # 1x1 tail over concat(x3, x4) at the output pixel (merged conv_shortcut)
-            a.x3, a.c3 = x3.ptr, c3
-            if x4 is not None:
-                a.x4, a.c4 = x4.ptr, c4
-        a.batch, a.hin, a.win, a.hout, a.wout, a.stride, a.up = x.B, x.H, x.W, ho, wo, stride, int(up)
-        a.w, a.bias = w, bias or None
-        a.rowvec, a.ld_rowvec, a.rows_per_batch = rowvec or None, 0, ho * wo
-        a.res1, a.ldres1, a.res2, a.ldres2 = res1 or None, cout, res2 or None, cout
-        a.scale, a.act = scale, 0
-        a.out, a.ldo, a.out_f32 = out.ptr, cout, 0
+        a.out, a.bias, a.rowvec, a.res1, a.res2 = out.ptr, bias or None, rowvec or None, res1 or None, res2 or None
         if dup:
             a.out_dup_rows = a.M
-            a.dtype = self.dt
             if self.lib.pp_gemm_workspace_bytes(C.byref(a)):      # (split-K: the combine does not write twins)
                 raise L.PPError("twin-prefix conv would run split-K; the caller must not request dup for this shape")
         if fused is not None:
             a.gn_in_acc, a.gn_in_gb, a.gn_in_groups, a.gn_in_eps, a.gn_in_silu = fused[0], fused[1], fused[2], fused[3], 1
-            a.dtype = self.dt
             if not self.lib.pp_conv_gn_preferred(C.byref(a)):
                 # (the statistics subscription stays: the apply launch reads the same accumulators)
                 a.gn_in_acc, a.gn_in_gb, a.gn_in_groups, a.gn_in_silu = None, None, 0, 0
@@ -497,18 +477,10 @@ class Builder:
         [rows][4C] GEGLU tensor is never written.  The launch record is the PPGemmArgs of the SECOND GEMM (what the two-launch
         plan hands pp_gemm_bf16 for `[g | hs] [W_po W_ff2 | W_po]^T`), so GroupNorm-statistics subscriptions of the consumer
         patch it exactly as they patch a GEMM.  Returns that record."""
-        a = L.PPGemmArgs()
-        a.M, a.N, a.K, a.x_mode = rows, Cc, 5 * Cc, L.PP_X_PLAIN
-        a.x1, a.x2, a.c1, a.c2 = hs, hs, 4 * Cc, Cc          # (x1 is never read: the tensor it would name does not exist)
-        a.ldx1, a.ldx2 = 4 * Cc, Cc
-        a.w, a.bias = w2, bias2 or None
-        a.res1, a.ldres1, a.res1_wrap_rows = res1 or None, Cc, res1_wrap
-        a.res2, a.ldres2 = res2 or None, Cc
-        a.scale, a.act = 1.0, 0
-        a.out, a.ldo, a.out_f32 = out, Cc, 0
-        a.rows_per_batch = hw
-        a.splitk, a.tile = 1, 0
-        a.dtype = self.dt
+        # (x1 is never read: the tensor it would name does not exist)
+        a = L.gemm_args(self.dt, rows, Cc, 4 * Cc, hs, w2, out, x2=hs, K2=Cc, rows_per_batch=hw)
+        a.bias, a.res1, a.res2, a.res1_wrap_rows = bias2 or None, res1 or None, res2 or None, res1_wrap
+        a.splitk = 1
         a._fused_ff = True                  # (no split-K combine behind this launch: _apply_in_producer_combine keeps off)
         self.plan.keep.append(a)
         self.last_gemm = a

@@ -98,28 +98,21 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias=None, x2=None, res1=None, res2=N
     M, K1 = x.shape
     K2 = x2.shape[1] if x2 is not None else 0
     N = w.shape[-2]
-    a = L.PPGemmArgs()
-    if w.dim() == 3:
-        a.w_batch_stride = w.stride(0)
-        if bias is not None and bias.dim() == 2:
-            a.vec_batch_stride = bias.stride(0)
-    a.M, a.N, a.K, a.x_mode = M, N, K1 + K2, L.PP_X_PLAIN
-    a.x1, a.x2, a.c1, a.c2, a.ldx1, a.ldx2 = _p(x), _p(x2), K1, K2, x.stride(0), (x2.stride(0) if x2 is not None else 0)
-    a.w, a.bias = _p(w), _p(bias)
-    a.rowvec = _p(rowvec)
-    a.ld_rowvec = rowvec.stride(0) if (rowvec is not None and rowvec.dim() == 2 and rowvec.shape[0] > 1) else 0
-    a.rows_per_batch = rows_per_batch
-    a.res1, a.ldres1 = _p(res1), (res1.stride(0) if res1 is not None else N)
-    a.res1_wrap_rows = res1_wrap
-    a.res2, a.ldres2 = _p(res2), (res2.stride(0) if res2 is not None else N)
-    a.scale, a.act = scale, act
     n_out = N // 2 if act == L.PP_ACT_GEGLU else (vt_col0 if vt_col0 else N)
     if out is None:
         out = torch.empty(M, n_out, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
     elif tuple(out.shape) != (M, n_out) or not out.is_contiguous() or out.dtype != (torch.float32 if out_f32 else x.dtype):
         raise L.PPError(f"gemm: `out` must be a contiguous [{M}, {n_out}] tensor of the output format")
-    a.dtype = L.dtype_code(x.dtype)
-    a.out, a.ldo, a.out_f32 = _p(out), n_out, int(out_f32)
+    a = L.gemm_args(L.dtype_code(x.dtype), M, N, K1, _p(x), _p(w), _p(out), x2=_p(x2), K2=K2, ldx=x.stride(0),
+                    ldx2=x2.stride(0) if x2 is not None else 0, ldo=n_out, ldres1=res1.stride(0) if res1 is not None else 0,
+                    ldres2=res2.stride(0) if res2 is not None else 0, rows_per_batch=rows_per_batch, scale=scale)
+    if w.dim() == 3:
+        a.w_batch_stride = w.stride(0)
+        if bias is not None and bias.dim() == 2:
+            a.vec_batch_stride = bias.stride(0)
+    a.bias, a.rowvec, a.res1, a.res2 = _p(bias), _p(rowvec), _p(res1), _p(res2)
+    a.ld_rowvec = rowvec.stride(0) if (rowvec is not None and rowvec.dim() == 2 and rowvec.shape[0] > 1) else 0
+    a.res1_wrap_rows, a.act, a.out_f32 = res1_wrap, act, int(out_f32)
     vt = None
     if vt_col0:
         nb = M // rows_per_batch
@@ -150,7 +143,7 @@ def gn_gamma_beta(gamma: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
 
 def conv_gn_supported(x: torch.Tensor, cout: int, x2=None, x3=None, x4=None, groups: int = 32) -> bool:
     """Would conv3x3(..., gn_in=...) run as the fused GroupNorm + SiLU + conv launch for these shapes?"""
-    a, _ = _conv_args(x, cout, 1, False, x2, x3, x4)
+    a = _conv_request(x, cout, 1, False, x2, x3, x4)
     a.gn_in_acc, a.gn_in_gb, a.gn_in_groups, a.gn_in_silu, a.gn_in_eps = 1, 1, groups, 1, 1e-5   # (non-null placeholders)
     return bool(L.lib().pp_conv_gn_supported(C.byref(a)))
 
@@ -159,26 +152,17 @@ def conv_halo_routed(x: torch.Tensor, cout: int, x2=None, x3=None, x4=None, stri
                      tile: int = 0) -> bool:
     """Does a PLAIN conv3x3 of these shapes run on the halo-tile loop (pp_conv_gn_supported() == 2) rather than the tap-major
     implicit GEMM?"""
-    a, _ = _conv_args(x, cout, stride, up, x2, x3, x4)
+    a = _conv_request(x, cout, stride, up, x2, x3, x4)
     a.tile = tile
     return L.lib().pp_conv_gn_supported(C.byref(a)) == 2
 
 
-def _conv_args(x, cout, stride, up, x2, x3, x4):
+def _conv_request(x, cout, stride, up, x2, x3, x4) -> L.PPGemmArgs:
+    """L.conv3x3_args of NHWC tensors (x2 rides beside x; x3 / x4: the 1x1 tail over concat(x3, x4) at the output pixel)"""
     B, H, W, C1 = x.shape
-    C2 = x2.shape[3] if x2 is not None else 0
-    hv, wv = (2 * H, 2 * W) if up else (H, W)
-    ho, wo = (hv - 1) // stride + 1, (wv - 1) // stride + 1
-    a = L.PPGemmArgs()
-    a.dtype = L.dtype_code(x.dtype)
-    C3 = x3.shape[3] if x3 is not None else 0
-    C4 = x4.shape[3] if x4 is not None else 0
-    a.M, a.N, a.K, a.x_mode = B * ho * wo, cout, 9 * (C1 + C2) + C3 + C4, L.PP_X_CONV3X3
-    a.x1, a.x2, a.c1, a.c2 = _p(x), _p(x2), C1, C2
-    a.x3, a.x4, a.c3, a.c4 = _p(x3), _p(x4), C3, C4     # 1x1 tail over concat(x3, x4) at the output pixel
-    a.batch, a.hin, a.win, a.hout, a.wout, a.stride, a.up = B, H, W, ho, wo, stride, int(up)
-    a.rows_per_batch, a.ldres1, a.ldres2, a.ldo, a.scale = ho * wo, cout, cout, cout, 1.0
-    return a, (B, ho, wo)
+    ch = lambda t: t.shape[3] if t is not None else 0      # noqa: E731
+    return L.conv3x3_args(L.dtype_code(x.dtype), B, H, W, C1, cout, _p(x), _p(x2), ch(x2), _p(x3), ch(x3), _p(x4), ch(x4),
+                          stride, up)
 
 
 def conv3x3(x: torch.Tensor, w: torch.Tensor, bias=None, stride: int = 1, up: bool = False, x2=None, rowvec=None,
@@ -193,30 +177,19 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, bias=None, stride: int = 1, up: bo
     False.  gn_next = (gamma, beta, eps, silu, sub): the GroupNorm that consumes the OUTPUT (its statistics subscription
     is gn[sub]) applied by the split-K combine (PPGemmArgs.gn_next_*) -> returns (out, normalised)."""
     lib = L.lib()
-    B, H, W, C1 = x.shape
-    C2 = x2.shape[3] if x2 is not None else 0
-    cout = w.shape[0]
-    hv, wv = (2 * H, 2 * W) if up else (H, W)
-    ho, wo = (hv - 1) // stride + 1, (wv - 1) // stride + 1
+    B, C1, C2, cout = x.shape[0], x.shape[3], (x2.shape[3] if x2 is not None else 0), w.shape[0]
+    a = _conv_request(x, cout, stride, up, x2, x3, x4)
+    ho, wo = a.hout, a.wout
     out = torch.empty(2 * B if dup else B, ho, wo, cout, dtype=x.dtype, device=x.device)
-    a = L.PPGemmArgs()
-    a.dtype = L.dtype_code(x.dtype)
-    C3 = x3.shape[3] if x3 is not None else 0
-    C4 = x4.shape[3] if x4 is not None else 0
-    a.M, a.N, a.K, a.x_mode = B * ho * wo, cout, 9 * (C1 + C2) + C3 + C4, L.PP_X_CONV3X3
-    a.x1, a.x2, a.c1, a.c2 = _p(x), _p(x2), C1, C2
-    a.x3, a.x4, a.c3, a.c4 = _p(x3), _p(x4), C3, C4     # 1x1 tail over concat(x3, x4) at the output pixel
-    a.batch, a.hin, a.win, a.hout, a.wout, a.stride, a.up = B, H, W, ho, wo, stride, int(up)
-    a.w, a.bias, a.rowvec, a.ld_rowvec, a.rows_per_batch = _p(w), _p(bias), _p(rowvec), 0, ho * wo
+    a.w, a.out, a.scale = _p(w), _p(out), scale
+    a.bias, a.rowvec, a.res1, a.res2 = _p(bias), _p(rowvec), _p(res1), _p(res2)
     if rowvec is not None and rowvec.dim() == 2 and rowvec.shape[0] > 1:
         a.ld_rowvec = rowvec.stride(0)
-    a.res1, a.ldres1, a.res2, a.ldres2 = _p(res1), cout, _p(res2), cout
     a.res1_wrap_rows = res1_wrap
     if dup:
         a.out_dup_rows = a.M
         if gn_dup_mask:
             a.gn_dup_batch, a.gn_dup_mask = B, gn_dup_mask
-    a.scale, a.act, a.out, a.ldo = scale, 0, _p(out), cout
     a.tile, a.splitk = tile, splitk
     _set_gn(a, gn, ho * wo)
     ynext = None
@@ -349,16 +322,11 @@ def ff_fused(hs: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2kp: torch.T
     permuted (engine._kperm_geglu; the 4-wave kernel that chains the GEGLU in registers), False -> natural order (the 8-wave
     kernel, activations exchanged through LDS); ln_stats [M, 2, 2] row moments of hs or None; gn: as ops.gemm takes them."""
     M, Cc = hs.shape
-    a = L.PPGemmArgs()
-    a.M, a.N, a.K, a.x_mode = M, Cc, 5 * Cc, L.PP_X_PLAIN
-    a.x1, a.x2, a.c1, a.c2, a.ldx1, a.ldx2 = _p(hs), _p(hs), 4 * Cc, Cc, 4 * Cc, hs.stride(0)
-    a.w, a.bias = _p(w2kp), _p(bias2)
-    a.res1, a.ldres1, a.res1_wrap_rows = _p(res1), (res1.stride(0) if res1 is not None else Cc), res1_wrap
-    a.res2, a.ldres2 = _p(res2), (res2.stride(0) if res2 is not None else Cc)
-    a.scale, a.act = 1.0, 0
     out = torch.empty(M, Cc, dtype=hs.dtype, device=hs.device)
-    a.out, a.ldo, a.dtype = _p(out), Cc, L.dtype_code(hs.dtype)
-    a.rows_per_batch = rows_per_batch
+    a = L.gemm_args(L.dtype_code(hs.dtype), M, Cc, 4 * Cc, _p(hs), _p(w2kp), _p(out), x2=_p(hs), K2=Cc, ldx2=hs.stride(0),
+                    ldres1=res1.stride(0) if res1 is not None else 0, ldres2=res2.stride(0) if res2 is not None else 0,
+                    rows_per_batch=rows_per_batch)
+    a.bias, a.res1, a.res2, a.res1_wrap_rows = _p(bias2), _p(res1), _p(res2), res1_wrap
     _set_gn(a, gn, rows_per_batch)
     L.check(L.lib().pp_ff_fused(C.byref(a), _p(w1), _p(b1), _p(cs1), _p(ln_stats),
                                 ln_stats.shape[1] if ln_stats is not None else 0, ln_eps, int(w2_kperm), _s()), "pp_ff_fused")

@@ -100,19 +100,9 @@ def test_build_id_names_the_sources_the_library_was_built_from():
 def _conv_args(B, H, W, c1, c2, cout, c3=0, c4=0, gn_in=True, splitk=0):
     """A PP_X_CONV3X3 request with dummy (non-null) pointers: the host-side queries only look at shapes and flags."""
     from powerpaint_amd import _lib as L
-    a = L.PPGemmArgs()
-    a.dtype = L.PP_DT_BF16
-    a.M, a.N, a.K, a.x_mode = B * H * W, cout, 9 * (c1 + c2) + c3 + c4, L.PP_X_CONV3X3
-    a.x1, a.c1 = 0x1000, c1
-    if c2:
-        a.x2, a.c2 = 0x2000, c2
-    if c3:
-        a.x3, a.c3 = 0x3000, c3
-    if c4:
-        a.x4, a.c4 = 0x4000, c4
-    a.batch, a.hin, a.win, a.hout, a.wout, a.stride, a.up = B, H, W, H, W, 1, 0
-    a.w, a.out, a.ldo, a.ldres1, a.ldres2 = 0x5000, 0x6000, cout, cout, cout
-    a.rows_per_batch, a.scale, a.splitk = H * W, 1.0, splitk
+    a = L.conv3x3_args(L.PP_DT_BF16, B, H, W, c1, cout, 0x1000, 0x2000 if c2 else None, c2, 0x3000 if c3 else None, c3,
+                       0x4000 if c4 else None, c4, w=0x5000, out=0x6000)
+    a.splitk = splitk
     if gn_in:
         a.gn_in_acc, a.gn_in_gb, a.gn_in_groups, a.gn_in_silu, a.gn_in_eps = 0x7000, 0x8000, 32, 1, 1e-5
     return a

@@ -42,6 +42,27 @@ def test_workgroup_placement_is_what_the_combine_rests_on():
     assert L.lib().pp_xcd_placement_ok() == 1
 
 
+def test_advised_tile_counters_answer_as_the_pinned_table():
+    """The pp_gemm_combine_ctr_bytes column of tests/golden/launch_forms.json (tests/test_launch_forms.py checks the others
+    without a device): the advice consults the placement probe, the only thing this test launches."""
+    import json
+    from tools import launch_forms as LF
+    lib = L.lib()
+    assert lib.pp_xcd_placement_ok() == 1
+    fx, reqs = json.load(open(LF.FIXTURE)), LF.requests()
+    assert fx["grid"] == LF.grid_digest(reqs) and len(fx["rows"]) == len(reqs)
+    got = [row[-1] for row in LF.table(lib, reqs, with_ctr=True)]
+    # whatever was recorded: counters are advised only where the pinned table says the launch splits and would fuse with them
+    # (the advice is the permission narrowed by measurements), two 64-bit words per tile, and both answers occur
+    odd = [(LF.describe(r), row, g) for r, row, g in zip(reqs, fx["rows"], got) if g and (g % 16 or not row[0] or not row[4])]
+    assert not odd and len(set(map(bool, got))) == 2, odd[:5]
+    # the column itself, where the fixture was written on a device (tools/launch_forms.py stores null without one)
+    bad = [(LF.describe(r), row[-1], g) for r, row, g in zip(reqs, fx["rows"], got) if row[-1] is not None and row[-1] != g]
+    for d, w, g in bad[:20]:
+        print("%s\n  pinned %s library %s" % (d, w, g))
+    assert not bad, "%d of %d requests are advised other counters" % (len(bad), len(reqs))
+
+
 def _after(fused_expected=True):
     torch.cuda.synchronize()
     assert ops.last_combine["fused"] == fused_expected, ops.last_combine
