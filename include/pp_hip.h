@@ -29,7 +29,7 @@ extern "C" {
 #define PP_ERR_LAUNCH (-3)       /* hipLaunchKernel / hipFuncSetAttribute failed                  */
 #define PP_ERR_WORKSPACE (-4)    /* workspace pointer null or too small                           */
 
-#define PP_ABI_VERSION 23
+#define PP_ABI_VERSION 24
 /* 16-bit storage format of activations and matrix weights ("dtype" arguments; the same codes pp_nchw_to_nhwc uses for
  * its source): bf16 or fp16 -- the reference's default is fp16 (/root/reference/app.py:548,559).  MFMA accumulation,
  * norm statistics, softmax, biases and latents are fp32 with either. */
@@ -626,6 +626,26 @@ typedef struct PPLoraMergeArgs {
   float* bias;
 } PPLoraMergeArgs;
 int pp_lora_merge(const PPLoraMergeArgs* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * (ABI v24) FreeU in front of an up-block resnet (diffusers-0.27 apply_freeu / fourier_filter with threshold = 1, called
+ * per resnet by the reference's first two up blocks, powerpaint/models/unet_2d_blocks.py:2563-2587, 2706-2730), ONE launch:
+ *     hidden_out[b][p][c] = hidden[b][p][c] * (c < ch / 2 ? bs[0] : 1)
+ *     skip_out = fourier_filter(skip, scale = bs[1]): per channel plane, with X(u,v) = sum_{h,w} x[h,w] e^{-2 pi i (uh/H + vw/W)},
+ *         y[h,w] = x[h,w] + (bs[1] - 1) / (H W) * Re sum_{(u,v) in {-1,0}^2} X(u,v) e^{+2 pi i (uh/H + vw/W)}
+ *     (the four bins the mask of the shifted spectrum scales; the set is not Hermitian-symmetric, Re is part of the definition)
+ *   hidden / skip : 16-bit NHWC [batch][h][w][ch] / [batch][h][w][cs], 4-byte aligned; ch % 4 == 0 (ch / 2 even), cs % 2 == 0,
+ *                   h, w >= 2 (h + w <= 512, else PP_ERR_UNSUPPORTED)
+ *   hidden_out    : may BE hidden (only the scaled half is then written); skip_out may BE skip; the two tensors must not
+ *                   alias each other
+ *   bs            : DEVICE pointer to (b, s), fp32 -- read by the kernel, so a captured graph follows new values
+ *   acc           : NULL, or int64 [batch][groups][2], 8-byte aligned, (ch + cs) % groups == 0, groups <= 64: the launch ADDS the
+ *                   (sum, sum of squares) of concat(hidden_out, skip_out) per group, of the values as stored, in the fixed point
+ *                   of PPGemmArgs.gn_acc -- what pp_groupnorm_apply_acc / gn_in_acc of the resnet's norm1 read (the sums the
+ *                   producers' epilogues took describe the tensors before FreeU)
+ * Arithmetic fp32, one rounding to `dtype` (bf16 / fp16). */
+int pp_freeu(const void* hidden, void* hidden_out, int ch, const void* skip, void* skip_out, int cs, int batch, int h, int w,
+             const float* bs, int64_t* acc, int groups, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -154,6 +154,8 @@ class Act:
     producer: object = None   # PPGemmArgs of the launch that writes this tensor (GroupNorm statistics subscribe to it)
     dup_half: int = 0         # > 0: the producer computed batch items [0, dup_half) and stored every row twice (the CFG twin
     #                           prefix, PPGemmArgs.out_dup_rows); this Act is the full-batch view of that tensor
+    gn_filled: object = None  # (acc, groups) shared by the (hidden, skip) pair a pp_freeu launch wrote: that launch has
+    #                           already added the statistics of concat(hidden, skip) to `acc` (Builder.freeu)
 
     @property
     def rows(self) -> int:
@@ -422,6 +424,11 @@ class Builder:
         statistics, patch those launches (PPGemmArgs.gn_acc slot) and return the accumulator pointer, else 0."""
         if not (GN_STATS_IN_EPILOGUE and self.gn_acc_cap):
             return 0
+        if x.gn_filled is not None or (x2 is not None and x2.gn_filled is not None):
+            # written by a pp_freeu launch: it summed the pair it wrote, for the norm over exactly that pair (the producers'
+            # epilogues saw the tensors before FreeU and must not be asked)
+            f = x.gn_filled
+            return f[0] if (f is not None and x2 is not None and x2.gn_filled is f and f[1] == groups) else 0
         hw = x.H * x.W
         parts = [(x, 0)] + ([(x2, x.C)] if x2 is not None else [])
         Ct = x.C + (x2.C if x2 is not None else 0)
@@ -450,6 +457,23 @@ class Builder:
             if t.dup_half:       # this consumer sees the full (twice-stored) tensor: both halves' accumulators get the sums
                 a.gn_dup_batch, a.gn_dup_mask = t.dup_half, a.gn_dup_mask | (1 << k)
         return acc
+
+    def freeu(self, h: Act, sk: Act, bs: int, groups: int) -> Tuple[Act, Act]:
+        """FreeU in front of an up-block resnet, ONE launch (csrc/freeu.hip): the first half of the hidden tensor's channels
+        times b, the skip tensor through the four-bin Fourier filter with scale s; `bs` = device pointer to (b, s).  Both
+        tensors are rewritten IN PLACE: inside a UNet step neither has another reader behind this point (the hidden tensor
+        is the previous block's output, the skip tensor's down-path consumer ran long before), every replay recomputes them,
+        and neither is an output or a residual slot.  The launch also adds the statistics of concat(hidden', skip') to a
+        fresh accumulator, which the returned Acts carry for the resnet's norm1 (_subscribe_gn_stats)."""
+        assert (h.B, h.H, h.W) == (sk.B, sk.H, sk.W)
+        Ct, nbytes, acc = h.C + sk.C, h.B * groups * 2 * 8, 0
+        if GN_STATS_IN_EPILOGUE and self.gn_acc_cap and Ct % groups == 0 and self.gn_acc_used + nbytes <= self.gn_acc_cap:
+            acc = self.gn_acc_base + self.gn_acc_used
+            self.gn_acc_used += nbytes
+        self.plan.add("freeu", self.lib.pp_freeu, h.ptr, h.ptr, h.C, sk.ptr, sk.ptr, sk.C, h.B, h.H, h.W, bs, acc or None,
+                      groups, self.dt)
+        filled = (acc, groups) if acc else None
+        return (Act(h.ptr, h.B, h.H, h.W, h.C, gn_filled=filled), Act(sk.ptr, sk.B, sk.H, sk.W, sk.C, gn_filled=filled))
 
     def layernorm(self, x: int, rows: int, Cc: int, gamma: int, beta: int, eps: float = 1e-5) -> int:
         out = self.alloc(rows * Cc * 2)
@@ -1364,7 +1388,8 @@ class SDNet:
 
     def build_step(self, pb: Builder, x_in: Act, t_dev: int, add_down: Optional[List[int]] = None,
                    add_mid: int = 0, add_up: Optional[List[int]] = None, ctrl_down: Optional[List[int]] = None,
-                   ctrl_mid: int = 0, scale: float = 1.0, pad_uncond: bool = False, twin: bool = False) -> Dict[str, object]:
+                   ctrl_mid: int = 0, scale: float = 1.0, pad_uncond: bool = False, twin: bool = False,
+                   freeu: int = 0) -> Dict[str, object]:
         """Append one forward pass.  x_in: NHWC bf16 input (already channel-concatenated).  Returns outputs:
         unet -> {"eps": ptr fp32 NCHW}; brushnet -> {"down": [Act], "mid": Act, "up": [Act]}; controlnet likewise.
         pad_uncond (side networks): the pipelines' guess mode runs the side branch on the conditional half of a CFG pair
@@ -1377,7 +1402,11 @@ class SDNet:
         first cross-attention (unet_2d_condition.py:1183-1236): conv_in, down_blocks.0.resnets.0 and the first transformer's
         norm / proj_in / self-attention run on ONE half (conv_in stores its rows twice -- the skip tensor's consumers in the
         up path see the full batch -- and the fused cross-attention block and the transformer's last GEMM read the half
-        batch with wrap addressing).  Where twin_prefix_ok() says no, the flag changes nothing."""
+        batch with wrap addressing).  Where twin_prefix_ok() says no, the flag changes nothing.
+        freeu (unet): device pointer to fp32 (b1, s1, b2, s2) -- FreeU (unet_2d_blocks.py:2563-2587, 2706-2730 of the
+        reference) runs in front of every resnet of up blocks 0 and 1, one pp_freeu launch each (Builder.freeu); it sees the
+        hidden tensor with the BrushNet adds in (they ride the producers' epilogues, unet_2d_blocks.py:2629-2630) and the skip
+        tensors with the ControlNet residuals on (unet_2d_condition.py:1263-1272).  0: no FreeU, the plan of a UNet without it."""
         P, lib = self.P, pb.lib
         B, H, W = x_in.B, x_in.H, x_in.W
         boc = self.boc
@@ -1418,6 +1447,8 @@ class SDNet:
             pb.plan.count("conv3x3", -2.0 * x.B * H * W * boc[0] * 9 * (x_in.C - self.cin0))   # (count the real MACs)
             return o
 
+        if freeu and self.kind != "unet":
+            raise L.PPError("FreeU is a feature of the UNet's up blocks (the side networks have no such method)")
         if self.kind == "controlnet":
             s = conv_in(self.cond_emb.ptr)
             skips = [s]
@@ -1488,6 +1519,8 @@ class SDNet:
                 sk = skips.pop()
                 assert sk.H == s.H and sk.W == s.W, "skip / hidden size mismatch (odd latent size?)"
                 r2 = pop(add_up)
+                if freeu and i < 2:         # (resolution_idx 0 takes (b1, s1), 1 takes (b2, s2); later up blocks are untouched)
+                    s, sk = pb.freeu(s, sk, freeu + 8 * i, self.groups)
                 s = self._resnet(pb, f"up_blocks.{i}.resnets.{j}", s, rev[i], temb_all, x2=sk,
                                  res2=0 if has_attn else r2)
                 if has_attn:

@@ -164,6 +164,24 @@ class UNet2DConditionModel(_HipModel):
         self.params_changed()
         return self
 
+    # ------------------------------------------------------------------ FreeU (DESIGN.md "FreeU")
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU (https://arxiv.org/abs/2309.11497), the reference's `UNet2DConditionModel.enable_freeu`
+        (unet_2d_condition.py:835-857): in front of every resnet of the first two up blocks the first half of the backbone
+        channels is scaled by b1 / b2 and the skip tensor's four lowest frequency bins by s1 / s2 (one pp_freeu launch each).
+        As in the reference's up blocks (unet_2d_blocks.py:2563-2568) the mechanism is on only while all four are truthy."""
+        self._freeu = (s1, s2, b1, b2)
+        return self
+
+    def disable_freeu(self):
+        """The reference's `disable_freeu` (unet_2d_condition.py:859-865): the plan and the outputs of a UNet that never had it."""
+        self._freeu = (None, None, None, None)
+        return self
+
+    def _freeu_values(self):
+        v = self.__dict__.get("_freeu")
+        return tuple(float(x) for x in v) if v is not None and all(v) else None
+
     # ------------------------------------------------------------------
     def _wiring(self, down_add, mid_add, up_add, ctrl_down, ctrl_mid):
         def ptrs(lst):
@@ -190,7 +208,7 @@ class UNet2DConditionModel(_HipModel):
             raise ValueError(f"sample has {Cin} channels, unet.config.in_channels = {self.config.in_channels}")
         wiring = self._wiring(down_block_add_samples, mid_block_add_sample, up_block_add_samples,
                               down_block_additional_residuals, mid_block_additional_residual)
-        self.rt.ensure(B, H, W, self._nctx(encoder_hidden_states), Cin, wiring, twin=twin)
+        self.rt.ensure(B, H, W, self._nctx(encoder_hidden_states), Cin, wiring, twin=twin, freeu=self._freeu_values())
         if wiring[0] != "plain":
             groups = {"down": down_block_add_samples if wiring[0] == "brushnet" else down_block_additional_residuals,
                       "mid": [mid_block_add_sample if wiring[0] == "brushnet" else mid_block_additional_residual]}

@@ -390,6 +390,20 @@ def add(a: torch.Tensor, b: torch.Tensor):
     return out
 
 
+def freeu(hidden: torch.Tensor, skip: torch.Tensor, b: float, s: float, acc: Optional[torch.Tensor] = None,
+          groups: int = 32, inplace: bool = False):
+    """FreeU in front of an up-block resnet (pp_freeu): hidden [B,H,W,Ch] with its first Ch/2 channels times b, skip
+    [B,H,W,Cs] through the four-bin Fourier filter with scale s.  acc: int64 [B][groups][2] (zeroed by the caller) receives
+    the GroupNorm statistics of concat(hidden', skip').  inplace: both tensors are rewritten (what the launch plans do).
+    Returns (hidden', skip')."""
+    B, H, W, Ch = hidden.shape
+    ho, so = (hidden, skip) if inplace else (torch.empty_like(hidden), torch.empty_like(skip))
+    bs = torch.tensor([b, s], dtype=torch.float32, device=hidden.device)
+    L.check(L.lib().pp_freeu(_p(hidden), _p(ho), Ch, _p(skip), _p(so), skip.shape[3], B, H, W, _p(bs), _p(acc), groups,
+                             L.dtype_code(hidden.dtype), _s()), "pp_freeu")
+    return ho, so
+
+
 def timestep_embedding(t: torch.Tensor, rows: int, dim: int):
     out = torch.empty(rows, dim, dtype=torch.float32, device=t.device)
     L.check(L.lib().pp_timestep_embedding(_p(t), rows, dim, _p(out), _s()), "pp_timestep_embedding")

@@ -36,7 +36,8 @@ class NetRuntime:
         self.gemm_splitk = 0
 
     # ------------------------------------------------------------------ build
-    def _build(self, arena: Arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond=False, twin=False):
+    def _build(self, arena: Arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond=False, twin=False,
+               freeu=False):
         net = self.net
         pb_setup = Builder(arena, dtype=net.dtype)
         pb_setup.gemm_tile, pb_setup.gemm_splitk = self.gemm_tile, self.gemm_splitk
@@ -83,6 +84,11 @@ class NetRuntime:
             dn = [p if p else s.ptr for p, s in zip(ptrs["down"], slots["down"])]
             md = ptrs["mid"][0] if ptrs["mid"][0] else slots["mid"][0].ptr
             kw = dict(ctrl_down=dn, ctrl_mid=md)
+        if freeu:
+            # FreeU's (b1, s1, b2, s2), fp32: the pp_freeu launches READ them, so new values reach a captured graph as a
+            # 16-byte write (set_freeu), with no re-capture
+            lay["freeu"] = arena.alloc(256)
+            kw["freeu"] = lay["freeu"]
         if pad_uncond:
             if net.kind == "unet":
                 raise L.PPError("pad_uncond is an output layout of the side networks (BrushNet / ControlNet)")
@@ -117,8 +123,10 @@ class NetRuntime:
         return out
 
     def ensure(self, B: int, H: int, W: int, nctx: int, cin_total: int, wiring=("plain",), cond_hw=None,
-               scale: float = 1.0, pad_uncond: bool = False, twin: bool = False):
-        """twin: the caller vouches that the second half of every network input (x_in, ControlNet conditioning) equals the
+               scale: float = 1.0, pad_uncond: bool = False, twin: bool = False, freeu=None):
+        """freeu: None, or (s1, s2, b1, b2) of UNet2DConditionModel.enable_freeu -- on / off is part of the plan key (the
+        plan gains one pp_freeu launch per resnet of up blocks 0 and 1), the values live in device memory the launches read.
+        twin: the caller vouches that the second half of every network input (x_in, ControlNet conditioning) equals the
         first -- a CFG pair built from one tensor; the step plan then runs the prompt-independent prefix on one half
         (SDNet.build_step)."""
         def freeze(w):
@@ -127,12 +135,13 @@ class NetRuntime:
             return (w[0], tuple((k, tuple(v)) for k, v in sorted(w[1].items())))
 
         key = (B, H, W, nctx, cin_total, freeze(wiring), cond_hw, self.gemm_tile, self.gemm_splitk, bool(pad_uncond),
-               bool(twin))
+               bool(twin)) + (("freeu",) if freeu is not None else ())      # (without FreeU: the key of a plan that never had it)
         if isinstance(scale, (list, tuple)):
             scale = tuple(float(v) for v in scale)       # (one representation: a list never equals the stored tuple)
         if key == self.key:
             if scale != self._scale:
                 self._patch_scale(scale)
+            self.set_freeu(freeu)
             return
         if H % (2 ** (len(self.net.boc) - 1)) or W % (2 ** (len(self.net.boc) - 1)):
             raise L.PPError(f"latent size {H}x{W} must be divisible by {2 ** (len(self.net.boc) - 1)}")
@@ -140,10 +149,10 @@ class NetRuntime:
         #  workgroups placed on the XCDs round-robin by linear id?  Plans combine split-K in-kernel only if so.)
         self.xcd_placement_ok = bool(self.lib.pp_xcd_placement_ok())
         dry = Arena()
-        self._build(dry, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin)
+        self._build(dry, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None)
         self.arena = Arena(_align(dry.peak, 4096), self.device)
         self.lay, self.setup_plan, self.step_plan, self.outputs = self._build(
-            self.arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin)
+            self.arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None)
         self.twin = bool(twin)
         self.pad_uncond = bool(pad_uncond)
         self.key = key
@@ -155,6 +164,19 @@ class NetRuntime:
         self._ctx_keep = self._cond_keep = None
         self.graph = None
         self.B, self.H, self.W, self.nctx = B, H, W, nctx
+        self._freeu = None
+        self.set_freeu(freeu)
+
+    def set_freeu(self, values):
+        """Write FreeU's (s1, s2, b1, b2) where the plan's pp_freeu launches read them, if they changed (stream-ordered:
+        eager runs and replays of a captured graph queued after this call see the new values)."""
+        if values is None or "freeu" not in self.lay:
+            return
+        values = tuple(float(v) for v in values)
+        if values != self._freeu:
+            s1, s2, b1, b2 = values
+            self.arena.view(self.lay["freeu"], (4,), torch.float32).copy_(torch.tensor([b1, s1, b2, s2], dtype=torch.float32))
+            self._freeu = values
 
     def _patch_scale(self, scale):
         """conditioning_scale is baked into the zero-conv GEMM launches; patch it in place (float or per-output list)."""
