@@ -29,7 +29,7 @@ extern "C" {
 #define PP_ERR_LAUNCH (-3)       /* hipLaunchKernel / hipFuncSetAttribute failed                  */
 #define PP_ERR_WORKSPACE (-4)    /* workspace pointer null or too small                           */
 
-#define PP_ABI_VERSION 24
+#define PP_ABI_VERSION 25
 /* 16-bit storage format of activations and matrix weights ("dtype" arguments; the same codes pp_nchw_to_nhwc uses for
  * its source): bf16 or fp16 -- the reference's default is fp16 (/root/reference/app.py:548,559).  MFMA accumulation,
  * norm statistics, softmax, biases and latents are fp32 with either. */
@@ -424,6 +424,19 @@ int pp_cfg_sched_step(const float* eps2, int cfg, float guidance, float* latents
  * sqrt(1-a_prev-std_dev_t^2)) and `noise` fp32 [n] drawn by the host from the caller's generator, once per step. */
 int pp_ddim_variance_noise(float* latents, const float* noise, int n, const float* coef_table, const int32_t* step_dev,
                            void* stream);
+/* (ABI v25) Fused classifier-free guidance + LCMScheduler.step (diffusers 0.27 `LCMScheduler`, few-step latent
+ * consistency sampling) on fp32 NCHW latents; replaces the guidance combine and `self.scheduler.step(...)` of
+ * pipeline_PowerPaint_Brushnet_CA.py:1449 (and the same line of the other two loops) when the scheduler is an LCMScheduler.
+ * Table row coef[step][8] = {sqrt(1-a_t), sqrt(a_t), c_out, c_skip, sqrt(a_prev), sqrt(1-a_prev), 0, 0}:
+ *     x0  = (x - sqrt(1-a_t) eps) / sqrt(a_t)
+ *     den = c_out x0 + c_skip x                       (boundary condition, s = t * timestep_scaling:
+ *                                                      c_skip = 0.25 / (s^2 + 0.25), c_out = s / sqrt(s^2 + 0.25))
+ *     x'  = sqrt(a_prev) den + sqrt(1-a_prev) noise   (every row but the last of the full schedule)
+ *     x'  = den                                       (last row: columns 4, 5 = (1, 0); `noise` is NOT read there)
+ * eps2 / cfg / guidance / step_dev / advance_ticket as pp_cfg_sched_step; `noise` fp32 [n], drawn by the host from the
+ * caller's generator before every step but the last.  n need not be a multiple of 4. */
+int pp_cfg_lcm_step(const float* eps2, int cfg, float guidance, float* latents, const float* noise, int n,
+                    const float* coef_table, int32_t* step_dev, uint32_t* advance_ticket, void* stream);
 
 /* (ABI v18) Front end of Transformer2DModel at C = 320 in one launch (csrc/tfront.hip):
  *     hs = proj_in(GroupNorm(x)),   q | k | v = to_q / to_k / to_v(LayerNorm1(hs))

@@ -407,6 +407,42 @@ __global__ void __launch_bounds__(256) cfg_sched_step_kernel(const float* __rest
   }
 }
 
+// LCM (diffusers 0.27 LCMScheduler.step; reference loop site pipeline_PowerPaint_Brushnet_CA.py:1449): CFG combine, the
+// consistency transition, the noise term and the counter advance in ONE launch.  Row (8 floats) = sqrt(1-a_t), sqrt(a_t),
+// c_out, c_skip, sqrt(a_prev), sqrt(1-a_prev); the last row of the full schedule carries (1, 0) in columns 4 and 5 and
+// then `z` is NOT read (a stale or uninitialised noise buffer never reaches the output).  Ticket: as cfg_sched_step_kernel.
+__global__ void __launch_bounds__(256) cfg_lcm_step_kernel(const float* __restrict__ eps2, int cfg, float g,
+                                                          float* __restrict__ x, const float* __restrict__ z, int n,
+                                                          const float* __restrict__ coef, int32_t* step_dev,
+                                                          unsigned* ticket) {
+  const float* c = coef + (size_t)step_dev[0] * 8;
+  const float c0 = c[0], c1 = c[1], c_out = c[2], c_skip = c[3], c4 = c[4], c5 = c[5];
+  const bool noisy = c5 != 0.f;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    float e;
+    if (cfg) {
+      const float eu = eps2[i], ec = eps2[n + i];
+      e = eu + g * (ec - eu);
+    } else {
+      e = eps2[i];
+    }
+    const float xv = x[i];
+    const float x0 = (xv - c0 * e) / c1;
+    const float den = c_out * x0 + c_skip * xv;
+    x[i] = noisy ? c4 * den + c5 * z[i] : den;
+  }
+  if (ticket) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      __threadfence();      // this block's reads of the counter are performed before its ticket becomes visible
+      if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+        *ticket = 0u;
+        step_dev[0] += 1;
+      }
+    }
+  }
+}
+
 // stochastic DDIM (eta > 0): x += std_dev_t * z, std_dev_t = column 4 of the step's table row, z drawn by the host
 __global__ void __launch_bounds__(256) ddim_variance_noise_kernel(float* __restrict__ x, const float* __restrict__ z, int n,
                                                                  const float* __restrict__ coef,
@@ -594,6 +630,15 @@ extern "C" int pp_cfg_sched_step(const float* eps2, int cfg, float guidance, flo
   hipLaunchKernelGGL(cfg_sched_step_kernel, dim3(grid_for_host(n)), dim3(256), 0, (hipStream_t)stream, eps2, cfg,
                      guidance, latents, m_prev, n, kind, coef_table, step_dev, (unsigned*)advance_ticket);
   PP_CHECK_LAUNCH("cfg_sched_step_kernel");
+  return PP_OK;
+}
+
+extern "C" int pp_cfg_lcm_step(const float* eps2, int cfg, float guidance, float* latents, const float* noise, int n,
+                               const float* coef_table, int32_t* step_dev, uint32_t* advance_ticket, void* stream) {
+  if (!eps2 || !latents || !noise || !coef_table || !step_dev || n <= 0) return PP_ERR_BAD_ARG;
+  hipLaunchKernelGGL(cfg_lcm_step_kernel, dim3(grid_for_host(n)), dim3(256), 0, (hipStream_t)stream, eps2, cfg, guidance,
+                     latents, noise, n, coef_table, step_dev, (unsigned*)advance_ticket);
+  PP_CHECK_LAUNCH("cfg_lcm_step_kernel");
   return PP_OK;
 }
 

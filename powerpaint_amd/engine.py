@@ -660,8 +660,12 @@ class SDNet:
                  down_block_types=("CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"),
                  up_block_types=("UpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D"),
                  conditioning_channels: int = 0, cond_embed_channels=(16, 32, 96, 256), out_channels: int = 4,
-                 dtype: torch.dtype = torch.bfloat16):
+                 dtype: torch.dtype = torch.bfloat16, time_cond_proj_dim: Optional[int] = None):
         assert kind in ("unet", "brushnet", "controlnet")
+        # guidance-embedded (LCM-distilled) UNet: TimestepEmbedding.cond_proj [boc[0]][d], no bias (diffusers 0.27)
+        if time_cond_proj_dim is not None and (kind != "unet" or int(time_cond_proj_dim) <= 0 or int(time_cond_proj_dim) % 8):
+            raise L.PPError(f"time_cond_proj_dim={time_cond_proj_dim!r}: a positive multiple of 8, on the UNet only")
+        self.time_cond_proj_dim = int(time_cond_proj_dim) if time_cond_proj_dim is not None else None
         L.dtype_code(dtype)              # bf16 | fp16 (raises otherwise)
         self.dtype = dtype
         self.kind = kind
@@ -768,6 +772,8 @@ class SDNet:
         conv("conv_in_condition" if self.kind == "brushnet" else "conv_in", boc[0], self.cin0, 3)
         lin("time_embedding.linear_1", te, boc[0])
         lin("time_embedding.linear_2", te, te)
+        if self.time_cond_proj_dim:
+            lin("time_embedding.cond_proj", boc[0], self.time_cond_proj_dim, False)
         for pre, cin, cout in self._resnet_specs():
             norm(pre + ".norm1", cin); conv(pre + ".conv1", cout, cin, 3); lin(pre + ".time_emb_proj", cout, te)
             norm(pre + ".norm2", cout); conv(pre + ".conv2", cout, cout, 3)
@@ -848,6 +854,8 @@ class SDNet:
         for n in ("linear_1", "linear_2"):
             T.append(R(f"time_embedding.{n}.weight", [f"time_embedding.{n}"]))
             vec(f"time_embedding.{n}.bias")
+        if self.time_cond_proj_dim:
+            T.append(R("time_embedding.cond_proj.weight", ["time_embedding.cond_proj"]))
         # resnets
         tw, off = [], 0
         temb_off: Dict[str, int] = {}
@@ -1389,7 +1397,7 @@ class SDNet:
     def build_step(self, pb: Builder, x_in: Act, t_dev: int, add_down: Optional[List[int]] = None,
                    add_mid: int = 0, add_up: Optional[List[int]] = None, ctrl_down: Optional[List[int]] = None,
                    ctrl_mid: int = 0, scale: float = 1.0, pad_uncond: bool = False, twin: bool = False,
-                   freeu: int = 0) -> Dict[str, object]:
+                   freeu: int = 0, b1_eff: int = 0) -> Dict[str, object]:
         """Append one forward pass.  x_in: NHWC bf16 input (already channel-concatenated).  Returns outputs:
         unet -> {"eps": ptr fp32 NCHW}; brushnet -> {"down": [Act], "mid": Act, "up": [Act]}; controlnet likewise.
         pad_uncond (side networks): the pipelines' guess mode runs the side branch on the conditional half of a CFG pair
@@ -1406,7 +1414,11 @@ class SDNet:
         freeu (unet): device pointer to fp32 (b1, s1, b2, s2) -- FreeU (unet_2d_blocks.py:2563-2587, 2706-2730 of the
         reference) runs in front of every resnet of up blocks 0 and 1, one pp_freeu launch each (Builder.freeu); it sees the
         hidden tensor with the BrushNet adds in (they ride the producers' epilogues, unet_2d_blocks.py:2629-2630) and the skip
-        tensors with the ControlNet residuals on (unet_2d_condition.py:1263-1272).  0: no FreeU, the plan of a UNet without it."""
+        tensors with the ControlNet residuals on (unet_2d_condition.py:1263-1272).  0: no FreeU, the plan of a UNet without it.
+        b1_eff (a UNet with time_cond_proj_dim): device pointer to the fp32 effective bias of time_embedding.linear_1,
+        b1 + W1 (Wc c) for the call's guidance embedding c -- `linear_1(t_emb + cond_proj(c))` of diffusers' TimestepEmbedding
+        (unet_2d_condition.py:1156) with the c-dependent term, constant over a call, taken out of the step
+        (NetRuntime.set_timestep_cond fills it).  0: the parameter's own bias."""
         P, lib = self.P, pb.lib
         B, H, W = x_in.B, x_in.H, x_in.W
         boc = self.boc
@@ -1429,7 +1441,7 @@ class SDNet:
         te = boc[0] * 4
         pb.plan.add("timestep_embedding", lib.pp_timestep_embedding, t_dev, 1, boc[0], tsin)
         pb.plan.add("linear_skinny", lib.pp_linear_skinny, tsin, 1, boc[0], P["time_embedding.linear_1.weight"],
-                    P["time_embedding.linear_1.bias"], te, t1, te, 0, L.PP_ACT_SILU, pb.dt)
+                    b1_eff or P["time_embedding.linear_1.bias"], te, t1, te, 0, L.PP_ACT_SILU, pb.dt)
         pb.plan.add("linear_skinny", lib.pp_linear_skinny, t1, 1, te, P["time_embedding.linear_2.weight"],
                     P["time_embedding.linear_2.bias"], te, temb, te, 0, 0, pb.dt)
         pb.plan.add("linear_skinny", lib.pp_linear_skinny, temb, 1, te, P["temb_all.weight"], P["temb_all.bias"],

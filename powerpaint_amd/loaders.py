@@ -113,7 +113,7 @@ def _keeps(model) -> bool:
 
 
 def load_scheduler(d: str):
-    """`<dir>/scheduler_config.json` -> the fused scheduler of the same `_class_name` (DDIM / PNDM / DPM-Solver++ / UniPC);
+    """`<dir>/scheduler_config.json` -> the fused scheduler of the same `_class_name` (DDIM / PNDM / DPM-Solver++ / UniPC / LCM);
     other classes are refused by name -- pass a scheduler object (any duck-typed one works) instead."""
     from .schedulers import SCHEDULERS
     f = os.path.join(d, "scheduler_config.json")

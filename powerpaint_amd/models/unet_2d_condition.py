@@ -22,17 +22,17 @@ class UNet2DConditionModel(_HipModel):
                  down_block_types=SD15_DOWN, up_block_types=SD15_UP, block_out_channels=(320, 640, 1280, 1280),
                  layers_per_block: int = 2, norm_num_groups: int = 32, norm_eps: float = 1e-5,
                  cross_attention_dim: int = 768, attention_head_dim: int = 8, device="cuda",
-                 dtype=torch.bfloat16, **unused):
+                 dtype=torch.bfloat16, time_cond_proj_dim: Optional[int] = None, **unused):
         self._extra_config = unused         # validated in the base constructor (check_fixed_config)
         super().__init__(in_channels, block_out_channels, layers_per_block, attention_head_dim, cross_attention_dim,
                          norm_num_groups, norm_eps, down_block_types, up_block_types, device, dtype,
-                         out_channels=out_channels)
+                         out_channels=out_channels, time_cond_proj_dim=time_cond_proj_dim)
         self.config = SimpleNamespace(
             sample_size=sample_size, in_channels=in_channels, out_channels=out_channels,
             down_block_types=tuple(down_block_types), up_block_types=tuple(up_block_types),
             block_out_channels=tuple(block_out_channels), layers_per_block=layers_per_block,
             norm_num_groups=norm_num_groups, norm_eps=norm_eps, cross_attention_dim=cross_attention_dim,
-            attention_head_dim=attention_head_dim, time_cond_proj_dim=None, addition_embed_type=None,
+            attention_head_dim=attention_head_dim, time_cond_proj_dim=time_cond_proj_dim, addition_embed_type=None,
             flip_sin_to_cos=True, freq_shift=0, act_fn="silu", only_cross_attention=False,
             use_linear_projection=False, class_embed_type=None, num_class_embeds=None, upcast_attention=False,
             resnet_time_scale_shift="default", mid_block_scale_factor=1, downsample_padding=1,
@@ -198,8 +198,11 @@ class UNet2DConditionModel(_HipModel):
 
     def prepare(self, sample_shape, encoder_hidden_states, down_block_add_samples=None, mid_block_add_sample=None,
                 up_block_add_samples=None, down_block_additional_residuals=None, mid_block_additional_residual=None,
-                twin: bool = False):
-        """Compile (or reuse) the launch plan for this shape / residual wiring and bind the inputs.  twin: the caller (the
+                twin: bool = False, timestep_cond: Optional[torch.Tensor] = None):
+        """Compile (or reuse) the launch plan for this shape / residual wiring and bind the inputs.  timestep_cond: the
+        guidance embedding of a UNet with `time_cond_proj_dim` ([B or 1, d], one value over the batch; None = no term, as
+        in diffusers) -- constant over a denoising call, folded into the time embedding's first bias once
+        (NetRuntime.set_timestep_cond).  twin: the caller (the
         fused denoising loop) vouches that the second half of the batch is a copy of the first (`torch.cat([latents] * 2)`
         over CFG-duplicated mask / masked-image latents, pipeline_PowerPaint.py:990-996): the prompt-independent prefix of
         the forward pass then runs on one half (NetRuntime.ensure).  `forward` never sets it."""
@@ -222,7 +225,22 @@ class UNet2DConditionModel(_HipModel):
                     if not p:
                         self.rt.load_residual(g, i, t)
         self.rt.set_context(encoder_hidden_states)
+        self.rt.set_timestep_cond(self._check_timestep_cond(timestep_cond, B))
         return self.rt
+
+    def _check_timestep_cond(self, c, B):
+        d = self.config.time_cond_proj_dim
+        if c is None:
+            return None
+        if d is None:
+            raise NotImplementedError("timestep_cond needs a UNet with config.time_cond_proj_dim (a guidance-embedded, "
+                                      "LCM-distilled UNet); this one has none")
+        if c.dim() != 2 or c.shape[1] != d or c.shape[0] not in (1, B):
+            raise ValueError(f"timestep_cond must be [{B} or 1, {d}], got {tuple(c.shape)}")
+        if c.shape[0] > 1 and not bool(torch.equal(c, c[:1].expand_as(c))):
+            raise ValueError("timestep_cond differs over the batch: the HIP path computes ONE time embedding per step "
+                             "(one guidance scale per call, as the pipelines build it)")
+        return c[:1]
 
     @torch.no_grad()
     def forward(self, sample: torch.Tensor, timestep: Union[torch.Tensor, float, int],
@@ -234,8 +252,7 @@ class UNet2DConditionModel(_HipModel):
                 down_block_add_samples: Optional[List[torch.Tensor]] = None,
                 mid_block_add_sample: Optional[torch.Tensor] = None,
                 up_block_add_samples: Optional[List[torch.Tensor]] = None, **kwargs):
-        for name, v in (("class_labels", class_labels), ("timestep_cond", timestep_cond),
-                        ("attention_mask", attention_mask), ("encoder_attention_mask", encoder_attention_mask),
+        for name, v in (("class_labels", class_labels), ("attention_mask", attention_mask), ("encoder_attention_mask", encoder_attention_mask),
                         ("down_intrablock_additional_residuals", down_intrablock_additional_residuals)):
             if v is not None:
                 raise NotImplementedError(f"{name} is outside the PowerPaint hot path (never set by the pipelines)")
@@ -243,7 +260,8 @@ class UNet2DConditionModel(_HipModel):
         # runs; with no adapter loaded a scale is a no-op, as in the reference
         self.merge_adapters((cross_attention_kwargs or {}).get("scale", 1.0))
         rt = self.prepare(tuple(sample.shape), encoder_hidden_states, down_block_add_samples, mid_block_add_sample,
-                          up_block_add_samples, down_block_additional_residuals, mid_block_additional_residual)
+                          up_block_add_samples, down_block_additional_residuals, mid_block_additional_residual,
+                          timestep_cond=timestep_cond)
         # the reference consumes the BrushNet lists destructively (.pop(0), unet_2d_condition.py:1223,1234,1318)
         for lst in (down_block_add_samples, up_block_add_samples):
             if isinstance(lst, list):

@@ -12,7 +12,8 @@ pipeline_PowerPaint_Brushnet_CA.py:1384-1466, pipeline_PowerPaint_ControlNet.py:
     x_in[:, 0:4] <- cat([latents] * 2)                                (pp_nchw_to_nhwc with batch wrap, no copy of the cat)
     [BrushNet | ControlNet forward]                                   (own launch plan, residuals stay in HBM as NHWC)
     eps          <- UNet(x_in, t, ctx, residuals)
-    latents      <- scheduler.step(eps_u + g (eps_c - eps_u), t, latents)   (pp_cfg_sched_step, fp32)
+    latents      <- scheduler.step(eps_u + g (eps_c - eps_u), t, latents)   (pp_cfg_sched_step, fp32; an LCMScheduler:
+                                                                       pp_cfg_lcm_step, which adds the step's noise as well)
     [latents     <- (1 - m) add_noise(x0, noise, t_next) + m latents]       (pp_latent_blend; ppt-v1 with a 4-channel UNet)
     step         <- step + 1                                          (pp_step_advance; round 5: by the last block of
                                                                        pp_cfg_sched_step when nothing behind it reads the counter)
@@ -72,7 +73,8 @@ class DenoiseLoop:
     # ------------------------------------------------------------------
     def bind(self, latents_shape, do_cfg: bool, guidance_scale: float, prompt_embeds, prompt_embeds_side=None,
              static_inputs=(), side_static_inputs=(), controlnet_cond=None, side_scale: float = 1.0,
-             guess_mode: bool = False, eta: float = 0.0, generator=None, noise_dtype=torch.float32, blend=None):
+             guess_mode: bool = False, eta: float = 0.0, generator=None, noise_dtype=torch.float32, blend=None,
+             timestep_cond=None):
         """Compile the per-step program.  latents_shape = (B, 4, h, w) of the *un-duplicated* latents.
         blend = (image_latents [1,4,h,w], mask [1,1,h,w], noise [B,4,h,w]): the `num_channels_unet == 4` branch of the
         ppt-v1 loop body (pipeline_PowerPaint.py:1025-1039) -- after every scheduler step the unmasked region is
@@ -80,6 +82,11 @@ class DenoiseLoop:
         eta > 0 with this package's DDIM (the only scheduler whose `step` takes it, pipeline_PowerPaint.py:536-551):
         the step program gains `latents += std_dev_t * z`; `run` draws z from `generator` before every step, in
         `noise_dtype`, exactly where the reference's `scheduler.step` calls `randn_tensor`.
+        An LCMScheduler (which ignores eta, as `prepare_extra_step_kwargs` never hands it over) consumes such a z on every
+        step but the last of its schedule, inside its own step launch (pp_cfg_lcm_step).
+        timestep_cond ([B or 1, d], pipeline_PowerPaint_Brushnet_CA.py:1351-1357,1434): the guidance embedding of a UNet with
+        `time_cond_proj_dim`; the UNet only (the side network gets none, :1411-1419).  The rows of the time-embedding table
+        depend on it: they are refilled when it changes.
         guess_mode (pipeline_PowerPaint_Brushnet_CA.py:1394-1425, pipeline_PowerPaint_ControlNet.py:1669-1702): the
         side network sees only the conditional half of a CFG pair (its inputs -- `prompt_embeds_side`, conditioning
         latents / control image -- arrive un-duplicated) with its residual scales log-spaced from 0.1 to 1; the
@@ -105,6 +112,8 @@ class DenoiseLoop:
             self._extra_step_kwargs = {k: v for k, v in (("eta", eta), ("generator", generator)) if k in names}
         else:
             sch.set_eta(self._eta)
+        # does the bound scheduler's step consume noise the host draws per step?  (stochastic DDIM, LCM)
+        self._noisy = (not self.foreign) and bool(sch.step_noise)
         self._blend = None
         if blend is not None:
             # loop-owned fp32 copies at stable addresses (a captured graph reads them); first image / first mask only
@@ -182,6 +191,8 @@ class DenoiseLoop:
                 wiring_kw = dict(down_block_additional_residuals=d, mid_block_additional_residual=m)
         if side_rt is not None:
             side_rts = [side_rt]
+        if timestep_cond is not None:
+            wiring_kw["timestep_cond"] = timestep_cond
         rt = self.unet.prepare((Be, cin, h, w), prompt_embeds, twin=twin_u, **wiring_kw)
         # one-time (per call) static channels of the UNet / side inputs
         rt.load_input(list(static_inputs))
@@ -203,9 +214,10 @@ class DenoiseLoop:
             self._do_cfg, self._g = bool(do_cfg), float(guidance_scale)
         else:
             ts, step = sch.timesteps_f32(), sch.step_counter()
-            mp = sch.m_prev(lat) if sch.kind >= 1 else None  # scheduler state: DPM m_{i-1}; PNDM history + saved sample
+            mp = sch.m_prev(lat) if 1 <= sch.kind <= 3 else None  # scheduler state: DPM m_{i-1}; PNDM history + saved
+                                                                    # sample; UniPC (DDIM and LCM keep none)
             kind, src = sch.kind, lat
-        key = (tuple(latents_shape), bool(do_cfg), bool(guess_mode), self._eta > 0, float(guidance_scale), id(rt.step_plan),
+        key = (tuple(latents_shape), bool(do_cfg), bool(guess_mode), self._noisy, float(guidance_scale), id(rt.step_plan),
                tuple(id(r.step_plan) for r in side_rts) if side_rts else None, kind, ts.data_ptr(), step.data_ptr(),
                0 if self.foreign else sch.coef_table().data_ptr(), mp.data_ptr() if mp is not None else 0, src.data_ptr(),
                _temb_table_enabled(), int(ts.numel()), tuple(getattr(r.net.params, "version", 0) for r in [rt] + side_rts),
@@ -259,12 +271,19 @@ class DenoiseLoop:
         if not self.foreign:
             if fold_advance and (getattr(self, "_ticket", None) is None or self._ticket.device != lat.device):
                 self._ticket = torch.zeros(1, dtype=torch.int32, device=lat.device)
-            prog.add("cfg_sched_step", lib.pp_cfg_sched_step, rt.outputs["eps"], int(do_cfg), float(guidance_scale),
-                     lat.data_ptr(), mp.data_ptr() if mp is not None else None, lat.numel(), sch.kind,
-                     sch.coef_table().data_ptr(), step.data_ptr(), self._ticket.data_ptr() if fold_advance else None)
+            if self._noisy and (getattr(self, "_var_noise", None) is None or
+                                tuple(self._var_noise.shape) != tuple(latents_shape)):
+                self._var_noise = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
+            ticket = self._ticket.data_ptr() if fold_advance else None
+            if sch.kind == 4:    # LCM: guidance combine, consistency transition, noise term and counter advance in one launch
+                prog.add("cfg_lcm_step", lib.pp_cfg_lcm_step, rt.outputs["eps"], int(do_cfg), float(guidance_scale),
+                         lat.data_ptr(), self._var_noise.data_ptr(), lat.numel(), sch.coef_table().data_ptr(),
+                         step.data_ptr(), ticket)
+            else:
+                prog.add("cfg_sched_step", lib.pp_cfg_sched_step, rt.outputs["eps"], int(do_cfg), float(guidance_scale),
+                         lat.data_ptr(), mp.data_ptr() if mp is not None else None, lat.numel(), sch.kind,
+                         sch.coef_table().data_ptr(), step.data_ptr(), ticket)
             if self._eta > 0:
-                if getattr(self, "_var_noise", None) is None or tuple(self._var_noise.shape) != tuple(latents_shape):
-                    self._var_noise = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
                 prog.add("ddim_variance_noise", lib.pp_ddim_variance_noise, lat.data_ptr(), self._var_noise.data_ptr(),
                          lat.numel(), sch.coef_table().data_ptr(), step.data_ptr())
             if self._blend is not None:
@@ -322,6 +341,9 @@ class DenoiseLoop:
             ent, r = info["ent"], info["rt"]
             # (this package's schedulers keep the timesteps on the host: compare there -- a device compare synchronises)
             host = getattr(self.scheduler, "_ts_host", None) if not self.foreign else None
+            cver = getattr(r, "tcond_version", 0)          # (guidance-embedded UNet: the rows depend on the call's embedding)
+            if ent.get("cver", 0) != cver:
+                ent["ts"], ent["hkey"], ent["cver"] = None, None, cver
             hkey = tuple(host.tolist()) if host is not None else None
             if hkey is not None and ent.get("hkey") == hkey:
                 continue
@@ -449,7 +471,7 @@ class DenoiseLoop:
         self.scheduler.reset()
         if getattr(self, "_ticket", None) is not None:
             self._ticket.zero_()       # (an aborted launch must not leave the step counter's ticket mid-count)
-        if self.scheduler.kind >= 1:
+        if self._keep[2] is not None:
             self._keep[2].zero_()
         self._fill_temb_tables()
         self.latents.copy_(latents.to(self.latents.device, torch.float32))
@@ -473,7 +495,8 @@ class DenoiseLoop:
         for i in range(num_steps):
             if varying and self.side_rt is not None:
                 self.side_rt._patch_scale(self._side_scale(scale_schedule[i]))
-            if self._eta > 0:         # this step's variance noise (stream-ordered before the step that consumes it)
+            # this step's noise (stream-ordered before the step that consumes it); LCM: none on the schedule's last step
+            if self._noisy and self.scheduler.draws_noise_at(self.scheduler.begin_index + i):
                 self._var_noise.copy_(variance_noise(self._var_noise.shape, self._gen, self._var_noise.device,
                                                      self._noise_dtype))
             if ents is not None:

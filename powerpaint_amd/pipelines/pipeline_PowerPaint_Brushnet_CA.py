@@ -18,8 +18,8 @@ from .image_processor import VaeImageProcessor
 
 def retrieve_timesteps(scheduler, num_inference_steps=None, device=None, timesteps=None, **kwargs):
     """pipeline_PowerPaint_Brushnet_CA.py:87-128: a custom `timesteps` list goes to schedulers whose `set_timesteps`
-    takes one and is a ValueError for the others -- which, as in diffusers 0.27, is all four of this package
-    (DDIM / DPM-Solver++ / PNDM / UniPC take a step count only)."""
+    takes one -- of this package LCMScheduler, which validates it (descending integers below num_train_timesteps) -- and is
+    a ValueError for the others, as in diffusers 0.27 (DDIM / DPM-Solver++ / PNDM / UniPC take a step count only)."""
     if timesteps is not None:
         if "timesteps" not in set(inspect.signature(scheduler.set_timesteps).parameters.keys()):
             raise ValueError(f"The current scheduler class {scheduler.__class__}'s `set_timesteps` does not support custom"
@@ -59,6 +59,21 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
     @property
     def do_classifier_free_guidance(self):
         return self._guidance_scale > 1 and self.unet.config.time_cond_proj_dim is None
+
+    def get_guidance_scale_embedding(self, w, embedding_dim=512, dtype=torch.float32):
+        """pipeline_PowerPaint_Brushnet_CA.py:973-999: the sinusoidal embedding [len(w), embedding_dim] of 1000 w that a
+        guidance-embedded (LCM-distilled) UNet takes as `timestep_cond` -- sines then cosines over half_dim frequencies
+        exp(-k ln(10000) / (half_dim - 1)), one zero column behind them when embedding_dim is odd."""
+        if w.dim() != 1:
+            raise ValueError(f"w must be one-dimensional, got shape {tuple(w.shape)}")
+        half_dim = embedding_dim // 2
+        rate = torch.log(torch.tensor(10000.0)) / (half_dim - 1)
+        freqs = torch.exp(torch.arange(half_dim, dtype=dtype) * -rate)
+        arg = (w * 1000.0).to(dtype)[:, None] * freqs[None, :]
+        emb = torch.cat([torch.sin(arg), torch.cos(arg)], dim=1)
+        if embedding_dim % 2 == 1:
+            emb = torch.nn.functional.pad(emb, (0, 1))
+        return emb
 
     def encode_prompt(self, prompt, device, num_images_per_prompt, do_cfg, negative_prompt=None, prompt_embeds=None,
                       negative_prompt_embeds=None, lora_scale=None, clip_skip=None):
@@ -182,6 +197,13 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
         if latents is None:
             latents = randn_tensor(shape, generator=generator, device=device, dtype=self._noise_dtype(prompt_embeds))
         latents = latents.to(device=device, dtype=torch.float32) * self.scheduler.init_noise_sigma
+        # 6.5 (:1351-1357) a guidance-embedded UNet: the guidance scale enters through the time embedding, not through CFG.
+        # Built on the host and rounded to the dtype the reference's latents have (`.to(dtype=latents.dtype)`)
+        timestep_cond = None
+        if self.unet.config.time_cond_proj_dim is not None:
+            gs = torch.tensor(self.guidance_scale - 1).repeat(nb)
+            timestep_cond = self.get_guidance_scale_embedding(gs, embedding_dim=self.unet.config.time_cond_proj_dim).to(
+                dtype=self._noise_dtype(prompt_embeds))
         n = len(timesteps)
         keep = [1.0 - float(i / n < control_guidance_start or (i + 1) / n > control_guidance_end) for i in range(n)]
         scales = [brushnet_conditioning_scale * k for k in keep]                              # :1370-1376,1405-1409
@@ -191,7 +213,7 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
         self._loop.bind(shape, do_cfg, guidance_scale, prompt_embedsU, prompt_embeds_side=prompt_embeds,
                         side_static_inputs=[(conditioning_latents, self.unet.config.in_channels)],
                         side_scale=scales[0], guess_mode=guess_mode, eta=eta, generator=generator,
-                        noise_dtype=self._noise_dtype(prompt_embeds))
+                        noise_dtype=self._noise_dtype(prompt_embeds), timestep_cond=timestep_cond)
         cb = None
         bad = [k for k in callback_on_step_end_tensor_inputs if k not in self._callback_tensor_inputs]
         if bad:                                                                              # check_inputs, :775-780

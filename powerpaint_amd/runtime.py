@@ -89,6 +89,12 @@ class NetRuntime:
             # 16-byte write (set_freeu), with no re-capture
             lay["freeu"] = arena.alloc(256)
             kw["freeu"] = lay["freeu"]
+        if getattr(net, "time_cond_proj_dim", None):
+            # guidance embedding c, Wc c and the effective linear_1 bias b1 + W1 (Wc c), fp32 (set_timestep_cond)
+            lay["tcond"] = arena.alloc(net.time_cond_proj_dim * 4)
+            lay["tcond_mid"] = arena.alloc(net.boc[0] * 4)
+            lay["b1_eff"] = arena.alloc(net.boc[0] * 4 * 4)
+            kw["b1_eff"] = lay["b1_eff"]
         if pad_uncond:
             if net.kind == "unet":
                 raise L.PPError("pad_uncond is an output layout of the side networks (BrushNet / ControlNet)")
@@ -166,6 +172,7 @@ class NetRuntime:
         self.B, self.H, self.W, self.nctx = B, H, W, nctx
         self._freeu = None
         self.set_freeu(freeu)
+        self._tcond_key = self._tcond_keep = None      # (a fresh arena: the effective bias is recomputed by the next set_timestep_cond)
 
     def set_freeu(self, values):
         """Write FreeU's (s1, s2, b1, b2) where the plan's pp_freeu launches read them, if they changed (stream-ordered:
@@ -177,6 +184,47 @@ class NetRuntime:
             s1, s2, b1, b2 = values
             self.arena.view(self.lay["freeu"], (4,), torch.float32).copy_(torch.tensor([b1, s1, b2, s2], dtype=torch.float32))
             self._freeu = values
+
+    tcond_version = 0      # moves whenever the effective linear_1 bias changed: rows of a time-embedding table made before are stale
+
+    def set_timestep_cond(self, c: Optional[torch.Tensor]):
+        """`timestep_cond` of a guidance-embedded UNet (config.time_cond_proj_dim = d): c [1 or B, d], every row the same
+        (the pipelines repeat one guidance scale over the batch).  diffusers' TimestepEmbedding computes
+        linear_1(t_emb + cond_proj(c)) = W1 t_emb + (b1 + W1 (Wc c)); c is constant over a call, so the bracket is computed
+        HERE, once per distinct c, by two pp_linear_skinny launches into a buffer at a stable address that the step plan's
+        linear_1 launch reads as its bias.  None: the plain bias (diffusers skips cond_proj without a `timestep_cond`)."""
+        net = self.net
+        d = getattr(net, "time_cond_proj_dim", None)
+        if not d:
+            if c is not None:
+                raise ValueError("timestep_cond needs a UNet with config.time_cond_proj_dim")
+            return
+        pver = getattr(net.params, "version", 0)
+        if c is not None:
+            if c.dim() != 2 or c.shape[1] != d:
+                raise ValueError(f"timestep_cond must be [B or 1, {d}], got {tuple(c.shape)}")
+            c = c.detach()[:1].to(torch.float32)
+            # a host tensor is compared by value (the pipelines build a new one per call); a device tensor by identity
+            ident = tuple(c.flatten().tolist()) if c.device.type == "cpu" else (c.data_ptr(), c._version)
+        else:
+            ident = None
+        key = (ident, pver)
+        if self._tcond_key is not None and key == self._tcond_key:
+            return
+        te = net.boc[0] * 4
+        eff = self.arena.view(self.lay["b1_eff"], (te,), torch.float32)
+        if c is None:
+            eff.copy_(net.params.tensor("time_embedding.linear_1.bias"))
+        else:
+            self.arena.view(self.lay["tcond"], (d,), torch.float32).copy_(c.reshape(-1).to(self.device))
+            P, dt, st = net.P, L.dtype_code(net.dtype), _stream()
+            L.check(self.lib.pp_linear_skinny(self.lay["tcond"], 1, d, P["time_embedding.cond_proj.weight"], None, net.boc[0],
+                                              self.lay["tcond_mid"], net.boc[0], 0, 0, dt, st), "pp_linear_skinny")
+            L.check(self.lib.pp_linear_skinny(self.lay["tcond_mid"], 1, net.boc[0], P["time_embedding.linear_1.weight"],
+                                              P["time_embedding.linear_1.bias"], te, self.lay["b1_eff"], te, 0, 0, dt, st),
+                    "pp_linear_skinny")
+        self._tcond_key, self._tcond_keep = key, c      # (an identity only holds while the tensor lives, as _ctx_keep)
+        self.tcond_version = self.tcond_version + 1
 
     def _patch_scale(self, scale):
         """conditioning_scale is baked into the zero-conv GEMM launches; patch it in place (float or per-output list)."""

@@ -177,6 +177,17 @@ class _SchedulerBase:
         ignore it -- as `prepare_extra_step_kwargs` never hands it to them."""
         return self
 
+    # -- per-step host noise (the loop draws it before the step that consumes it, into a buffer at a stable address)
+    @property
+    def step_noise(self) -> bool:
+        """Does this scheduler's step, as configured now, consume Gaussian noise drawn by the host?  (stochastic DDIM:
+        eta > 0; LCM: always).  Part of the loop's program key."""
+        return False
+
+    def draws_noise_at(self, row: int) -> bool:
+        """Does the step at table row `row` draw noise?  (LCM: every row but the last of the full schedule.)"""
+        return self.step_noise
+
     def step(self, model_output, timestep, sample, eta: float = 0.0, generator=None, return_dict: bool = True, **kw):
         """x_t -> x_{t-1} on the HIP kernel (fp32 math).  Returns a NEW tensor in sample's dtype.  `eta` / `generator`:
         stochastic DDIM (kind 0 only), the variance noise drawn like diffusers' `randn_tensor(model_output.shape, ...)`."""
@@ -240,6 +251,10 @@ class DDIMScheduler(_SchedulerBase):
             self._upload(self._device)
             self._begin = begin
         return self
+
+    @property
+    def step_noise(self) -> bool:
+        return self.eta > 0
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         T = self.config.num_train_timesteps
@@ -575,5 +590,138 @@ class UniPCMultistepScheduler(_SchedulerBase):
         self._coef = torch.from_numpy(coef.astype(np.float32))
 
 
+class LCMScheduler(_SchedulerBase):
+    """Latent consistency sampling (arXiv:2310.04378) as diffusers-0.27 `LCMScheduler` runs it: the sampler LCM-LoRA and
+    LCM-distilled UNets are trained for, 1 to 8 network evaluations per image.  Epsilon prediction, scaled-linear betas, no
+    clipping or thresholding.  `steps_offset`, `timestep_spacing` and `set_alpha_to_one` are kept in `config` and have no
+    effect on the arithmetic, as in the library (its schedule never reaches a previous timestep below 0).
+
+    One step (fp32):  x0 = (x - sqrt(1-a_t) e) / sqrt(a_t);  den = c_out x0 + c_skip x  with the boundary scalings at
+    s = t * timestep_scaling, c_skip = 0.25 / (s^2 + 0.25), c_out = s / sqrt(s^2 + 0.25);  x' = sqrt(a_prev) den +
+    sqrt(1-a_prev) z with fresh Gaussian z, a_prev at the NEXT entry of `timesteps` -- on the last step of the full schedule
+    x' = den and nothing is drawn.  Table row = (sqrt(1-a_t), sqrt(a_t), c_out, c_skip, sqrt(a_prev), sqrt(1-a_prev), 0, 0),
+    the last row with (1, 0) in columns 4 and 5; the tensor math runs in `pp_cfg_lcm_step`."""
+    kind = 4
+
+    # arithmetic options of diffusers-0.27 `LCMScheduler.__init__` that the fused step does not implement
+    _CHECKED = ("prediction_type", "beta_schedule", "clip_sample", "thresholding", "rescale_betas_zero_snr", "trained_betas")
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, original_inference_steps=50,
+                 set_alpha_to_one=True, steps_offset=0, timestep_spacing="leading", timestep_scaling=10.0, **kw):
+        _check_config("LCMScheduler", kw, self._CHECKED)
+        super().__init__(num_train_timesteps, beta_start, beta_end, original_inference_steps=original_inference_steps,
+                         set_alpha_to_one=set_alpha_to_one, steps_offset=steps_offset, timestep_spacing=timestep_spacing,
+                         timestep_scaling=timestep_scaling, prediction_type="epsilon", clip_sample=False)
+        self.custom_timesteps = False
+
+    @classmethod
+    def from_config(cls, config, **kw):
+        """`LCMScheduler.from_config(pipe.scheduler.config)`: the keys this class's constructor names are taken over; of the
+        donor's other keys only those the library's LCM constructor names as well can change the arithmetic and are
+        checked (a PNDM config's `skip_prk_steps`, a DPM config's `algorithm_type` ... never reach it)."""
+        import inspect
+        src = dict(config) if isinstance(config, dict) else dict(vars(config))
+        src.update(kw)
+        _check_config(cls.__name__, src, cls._CHECKED)
+        names = set(inspect.signature(cls.__init__).parameters) - {"self", "kw"}
+        return cls(**{k: v for k, v in src.items() if k in names or k in cls._CHECKED})
+
+    @property
+    def step_noise(self) -> bool:
+        return True
+
+    def draws_noise_at(self, row: int) -> bool:
+        return int(row) != len(self._ts_host) - 1
+
+    def set_timesteps(self, num_inference_steps=None, device=None, original_inference_steps=None, timesteps=None,
+                      strength: float = 1.0):
+        T = self.config.num_train_timesteps
+        if num_inference_steps is None and timesteps is None:
+            raise ValueError("Must pass exactly one of `num_inference_steps` or `custom_timesteps`.")
+        if num_inference_steps is not None and timesteps is not None:
+            raise ValueError("Can only pass one of `num_inference_steps` or `custom_timesteps`.")
+        original_steps = original_inference_steps if original_inference_steps is not None else \
+            self.config.original_inference_steps
+        if original_steps > T:
+            raise ValueError(f"`original_steps`: {original_steps} cannot be larger than `num_train_timesteps`: {T}")
+        k = T // original_steps
+        origin = np.asarray(list(range(1, int(original_steps * strength) + 1)), dtype=np.int64) * k - 1
+        if timesteps is not None:
+            ts = [int(t) for t in timesteps]
+            if any(float(a) != b for a, b in zip(timesteps, ts)):
+                raise ValueError("`custom_timesteps` must be integers.")
+            if len(ts) == 0 or any(b >= a for a, b in zip(ts, ts[1:])):
+                raise ValueError("`custom_timesteps` must be in descending order.")
+            if ts[0] >= T or ts[-1] < 0:
+                raise ValueError(f"`timesteps` must start before `num_train_timesteps`: {T} and stay non-negative.")
+            n = len(ts)
+            ts = np.array(ts, dtype=np.int64)
+            ts = ts[max(n - min(int(n * strength), n), 0) * self.order:]
+            if len(ts) == 0:
+                raise ValueError(f"strength {strength} leaves none of the {n} custom timesteps")
+            self.custom_timesteps = True
+        else:
+            if num_inference_steps > T:
+                raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than "
+                                 f"`num_train_timesteps`: {T}")
+            if num_inference_steps < 1:
+                raise ValueError(f"`num_inference_steps`: {num_inference_steps} must be at least 1")
+            if len(origin) // num_inference_steps < 1:
+                raise ValueError(f"The combination of `original_steps x strength`: {original_steps} x {strength} is smaller"
+                                 f" than `num_inference_steps`: {num_inference_steps}")
+            if num_inference_steps > original_steps:
+                raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than "
+                                 f"`original_inference_steps`: {original_steps}")
+            origin = origin[::-1].copy()
+            idx = np.floor(np.linspace(0, len(origin), num=num_inference_steps, endpoint=False)).astype(np.int64)
+            ts = origin[idx]
+            self.custom_timesteps = False
+        self.num_inference_steps = len(ts)
+        self._ts_host = torch.from_numpy(np.ascontiguousarray(ts))
+        self.timesteps = self._ts_host.clone()
+        self._begin = 0
+        self._fill_table()
+        self._upload(device)
+
+    def _fill_table(self):
+        """(rows do not depend on where the loop enters: LCM keeps no history.  fp32 torch in the library's operation order.)"""
+        ts = self._ts_host.tolist()
+        n = len(ts)
+        coef = torch.zeros(n, 8, dtype=torch.float32)
+        for i, t in enumerate(ts):
+            a_t = self.alphas_cumprod[t]
+            s = torch.tensor(t) * self.config.timestep_scaling           # get_scalings_for_boundary_condition_discrete,
+            c_skip = 0.5 ** 2 / (s ** 2 + 0.5 ** 2)                      # sigma_data = 0.5
+            c_out = s / (s ** 2 + 0.5 ** 2) ** 0.5
+            coef[i, 0], coef[i, 1] = (1 - a_t).sqrt(), a_t.sqrt()
+            coef[i, 2], coef[i, 3] = c_out, c_skip
+            if i < n - 1:
+                a_p = self.alphas_cumprod[ts[i + 1]]
+                coef[i, 4], coef[i, 5] = a_p.sqrt(), (1 - a_p).sqrt()
+            else:
+                coef[i, 4], coef[i, 5] = 1.0, 0.0                        # prev_sample = denoised, no noise drawn
+        self._coef = coef
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, **kw):
+        """x_t -> x_{t-1} in `pp_cfg_lcm_step` (fp32 math).  Returns a NEW tensor in sample's dtype.  The noise is drawn like
+        diffusers' `randn_tensor(model_output.shape, generator=generator, ...)`, and not on the schedule's last step."""
+        if not sample.is_cuda:
+            raise L.PPError("scheduler.step needs CUDA tensors: the step runs in the HIP kernel, no CPU fallback")
+        i = self._index_of(timestep)
+        x = sample.detach().to(torch.float32).contiguous().clone()
+        e = model_output.detach().to(torch.float32).contiguous()
+        step = torch.full((1,), i, dtype=torch.int32, device=x.device)
+        # (the last row never reads the noise: any valid address does)
+        z = variance_noise(model_output.shape, generator, x.device, model_output.dtype) if self.draws_noise_at(i) else x
+        L.check(L.lib().pp_cfg_lcm_step(e.data_ptr(), 0, 0.0, x.data_ptr(), z.data_ptr(), x.numel(),
+                                         self._coef_dev.data_ptr(), step.data_ptr(), None,
+                                         torch.cuda.current_stream().cuda_stream), "pp_cfg_lcm_step")
+        out = x.to(sample.dtype)
+        if not return_dict:
+            return (out,)
+        return SimpleNamespace(prev_sample=out, denoised=None)
+
+
 SCHEDULERS = {"DDIMScheduler": DDIMScheduler, "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
-              "PNDMScheduler": PNDMScheduler, "UniPCMultistepScheduler": UniPCMultistepScheduler}
+              "PNDMScheduler": PNDMScheduler, "UniPCMultistepScheduler": UniPCMultistepScheduler,
+              "LCMScheduler": LCMScheduler}
