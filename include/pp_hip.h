@@ -29,7 +29,7 @@ extern "C" {
 #define PP_ERR_LAUNCH (-3)       /* hipLaunchKernel / hipFuncSetAttribute failed                  */
 #define PP_ERR_WORKSPACE (-4)    /* workspace pointer null or too small                           */
 
-#define PP_ABI_VERSION 25
+#define PP_ABI_VERSION 26
 /* 16-bit storage format of activations and matrix weights ("dtype" arguments; the same codes pp_nchw_to_nhwc uses for
  * its source): bf16 or fp16 -- the reference's default is fp16 (/root/reference/app.py:548,559).  MFMA accumulation,
  * norm statistics, softmax, biases and latents are fp32 with either. */
@@ -437,6 +437,16 @@ int pp_ddim_variance_noise(float* latents, const float* noise, int n, const floa
  * caller's generator before every step but the last.  n need not be a multiple of 4. */
 int pp_cfg_lcm_step(const float* eps2, int cfg, float guidance, float* latents, const float* noise, int n,
                     const float* coef_table, int32_t* step_dev, uint32_t* advance_ticket, void* stream);
+/* (ABI v26) Fused classifier-free guidance + the step of a sigma-space sampler (EulerDiscreteScheduler at s_churn = 0,
+ * EulerAncestralDiscreteScheduler; Karras et al., arXiv:2206.00364, k-diffusion sample_euler / sample_euler_ancestral) on
+ * fp32 NCHW latents held in sigma space (x = x0 + sigma eps).  Table row coef[step][8] = {sigma, dt, s_up, 0, 0, 0, 0, 0}:
+ *     e  = cfg ? eps_u + guidance (eps_c - eps_u) : eps        (the derivative (x - x0) / sigma of epsilon prediction)
+ *     x' = x + dt e                                            (Euler: dt = sigma_next - sigma;  ancestral: s_down - sigma)
+ *     x' = x' + s_up noise                                     (rows with s_up != 0 only; `noise` is NOT read otherwise)
+ * eps2 / cfg / guidance / step_dev / advance_ticket as pp_cfg_sched_step; `noise` fp32 [n] drawn by the host.  n need not
+ * be a multiple of 4. */
+int pp_cfg_sigma_step(const float* eps2, int cfg, float guidance, float* latents, const float* noise, int n,
+                      const float* coef_table, int32_t* step_dev, uint32_t* advance_ticket, void* stream);
 
 /* (ABI v18) Front end of Transformer2DModel at C = 320 in one launch (csrc/tfront.hip):
  *     hs = proj_in(GroupNorm(x)),   q | k | v = to_q / to_k / to_v(LayerNorm1(hs))
@@ -545,6 +555,14 @@ int pp_latent_blend(float* latents, const float* image_latents, const float* mas
 int pp_step_head(const float* temb_table, const int32_t* step_dev, float* temb_out, int row_floats, const float* latents,
                  int batch, int c, int hw, int src_batch_mod, void* x_in, int ldc, int c0, int dtype, void* zero_dst,
                  long long n_zero, void* stream);
+/* (ABI v26) pp_step_head for a sigma-space scheduler (Euler, Euler ancestral): the same launch, the latents branch writing
+ * x_in[b][p][c0 + j] = to16(latents[b mod src_batch_mod][j][p] / in_div[step]) -- `scheduler.scale_model_input`
+ * (pipeline_PowerPaint.py:993, pipeline_PowerPaint_Brushnet_CA.py:1391) with in_div[i] = sqrt(sigma_i^2 + 1), a device table
+ * of one fp32 per schedule row indexed by step_dev[0].  The division is in fp32, the value is converted to 16 bits once.
+ * Time-embedding row and zeroing exactly as pp_step_head. */
+int pp_step_head_scaled(const float* temb_table, const int32_t* step_dev, float* temb_out, int row_floats, const float* latents,
+                        int batch, int c, int hw, int src_batch_mod, void* x_in, int ldc, int c0, int dtype, void* zero_dst,
+                        long long n_zero, const float* in_div, void* stream);
 /* t_out[0] = timesteps[step]; used at the top of a captured step.  advance: ++step. */
 int pp_step_select_t(const float* timesteps, const int32_t* step_dev, float* t_out, void* stream);
 int pp_step_advance(int32_t* step_dev, void* stream);

@@ -443,6 +443,41 @@ __global__ void __launch_bounds__(256) cfg_lcm_step_kernel(const float* __restri
   }
 }
 
+// Sigma-space samplers (ABI v26: Euler, Euler ancestral as k-diffusion's sample_euler / sample_euler_ancestral and diffusers
+// 0.27 run them; reference loop site pipeline_PowerPaint.py:1018-1023): CFG combine, the Euler step on the derivative
+// (x - x0) / sigma = eps, the ancestral noise and the counter advance in ONE launch.  Row (8 floats) = sigma, dt, s_up, 0...;
+// x' = x + dt e (+ s_up z).  Where s_up == 0 (plain Euler; the last ancestral row) `z` is NOT read.  Ticket: as
+// cfg_sched_step_kernel.
+__global__ void __launch_bounds__(256) cfg_sigma_step_kernel(const float* __restrict__ eps2, int cfg, float g,
+                                                            float* __restrict__ x, const float* __restrict__ z, int n,
+                                                            const float* __restrict__ coef, int32_t* step_dev,
+                                                            unsigned* ticket) {
+  const float* c = coef + (size_t)step_dev[0] * 8;
+  const float dt = c[1], s_up = c[2];
+  const bool noisy = s_up != 0.f;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    float e;
+    if (cfg) {
+      const float eu = eps2[i], ec = eps2[n + i];
+      e = eu + g * (ec - eu);
+    } else {
+      e = eps2[i];
+    }
+    const float xn = x[i] + dt * e;
+    x[i] = noisy ? xn + s_up * z[i] : xn;
+  }
+  if (ticket) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      __threadfence();      // this block's reads of the counter are performed before its ticket becomes visible
+      if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+        *ticket = 0u;
+        step_dev[0] += 1;
+      }
+    }
+  }
+}
+
 // stochastic DDIM (eta > 0): x += std_dev_t * z, std_dev_t = column 4 of the step's table row, z drawn by the host
 __global__ void __launch_bounds__(256) ddim_variance_noise_kernel(float* __restrict__ x, const float* __restrict__ z, int n,
                                                                  const float* __restrict__ coef,
@@ -642,6 +677,15 @@ extern "C" int pp_cfg_lcm_step(const float* eps2, int cfg, float guidance, float
   return PP_OK;
 }
 
+extern "C" int pp_cfg_sigma_step(const float* eps2, int cfg, float guidance, float* latents, const float* noise, int n,
+                                 const float* coef_table, int32_t* step_dev, uint32_t* advance_ticket, void* stream) {
+  if (!eps2 || !latents || !noise || !coef_table || !step_dev || n <= 0) return PP_ERR_BAD_ARG;
+  hipLaunchKernelGGL(cfg_sigma_step_kernel, dim3(grid_for_host(n)), dim3(256), 0, (hipStream_t)stream, eps2, cfg, guidance,
+                     latents, noise, n, coef_table, step_dev, (unsigned*)advance_ticket);
+  PP_CHECK_LAUNCH("cfg_sigma_step_kernel");
+  return PP_OK;
+}
+
 extern "C" int pp_ddim_variance_noise(float* latents, const float* noise, int n, const float* coef_table,
                                       const int32_t* step_dev, void* stream) {
   if (!latents || !noise || !coef_table || !step_dev || n <= 0) return PP_ERR_BAD_ARG;
@@ -710,45 +754,68 @@ extern "C" int pp_zero_u64(void* dst, long long n, void* stream) {
 //   blocks [nb_t, nb_t + nb_x)  x_in[b][p][c0 + j] = latents[b mod wrap][j][p]   (fp32 NCHW -> 16-bit NHWC, CFG duplication)
 //   the rest                    acc[:] = 0                                    (GroupNorm-statistics accumulators)
 namespace {
-template <int EDT>
+// SCALED (ABI v26, sigma-space samplers): the latents branch divides by in_div[step] in fp32 before the one conversion to
+// 16 bits -- `scheduler.scale_model_input`, x / sqrt(sigma_i^2 + 1), on the way into the network's input layout.
+template <int EDT, bool SCALED>
 __global__ void __launch_bounds__(256) step_head_kernel(const float* __restrict__ table, const int32_t* __restrict__ step_dev,
                                                        float* __restrict__ temb_out, int row_floats, int nb_t,
                                                        const float* __restrict__ lat, int batch, int c, int hw, int bmod,
                                                        uint16_t* __restrict__ dst, int ldc, int c0, int nb_x,
-                                                       unsigned long long* __restrict__ zdst, long long nz) {
+                                                       unsigned long long* __restrict__ zdst, long long nz,
+                                                       const float* __restrict__ in_div) {
   const int bid = blockIdx.x;
   if (bid < nb_t) {
     const float* row = table + (size_t)step_dev[0] * row_floats;
     for (int i = bid * 256 + threadIdx.x; i < row_floats; i += nb_t * 256) temb_out[i] = row[i];
   } else if (bid < nb_t + nb_x) {
     const long long total = (long long)batch * hw;
+    const float d = SCALED ? in_div[step_dev[0]] : 1.f;
     for (long long i = (long long)(bid - nb_t) * 256 + threadIdx.x; i < total; i += (long long)nb_x * 256) {
       const int b = (int)(i / hw), p = (int)(i - (long long)b * hw);
       const int sb = bmod > 0 ? b % bmod : b;
-      for (int j = 0; j < c; ++j) dst[(size_t)i * ldc + c0 + j] = E16<EDT>::from_f(lat[((size_t)sb * c + j) * hw + p]);
+      for (int j = 0; j < c; ++j) {
+        const float v = lat[((size_t)sb * c + j) * hw + p];
+        dst[(size_t)i * ldc + c0 + j] = E16<EDT>::from_f(SCALED ? v / d : v);
+      }
     }
   } else {
     const int nb_z = gridDim.x - nb_t - nb_x;
     for (long long i = (long long)(bid - nb_t - nb_x) * 256 + threadIdx.x; i < nz; i += (long long)nb_z * 256) zdst[i] = 0ull;
   }
 }
-}  // namespace
 
-extern "C" int pp_step_head(const float* temb_table, const int32_t* step_dev, float* temb_out, int row_floats,
-                            const float* latents, int batch, int c, int hw, int src_batch_mod, void* x_in, int ldc, int c0,
-                            int dtype, void* zero_dst, long long n_zero, void* stream) {
+template <bool SCALED>
+int step_head_launch(const float* temb_table, const int32_t* step_dev, float* temb_out, int row_floats, const float* latents,
+                     int batch, int c, int hw, int src_batch_mod, void* x_in, int ldc, int c0, int dtype, void* zero_dst,
+                     long long n_zero, const float* in_div, void* stream) {
   if (!temb_table || !step_dev || !temb_out || row_floats <= 0 || !latents || !x_in || batch <= 0 || c <= 0 || hw <= 0 ||
-      c0 < 0 || c0 + c > ldc || !pp_dt_ok(dtype) || !zero_dst || n_zero <= 0)
+      c0 < 0 || c0 + c > ldc || !pp_dt_ok(dtype) || !zero_dst || n_zero <= 0 || (SCALED && !in_div))
     return PP_ERR_BAD_ARG;
   int nb_t = (row_floats + 255) / 256, nb_x = (int)(((long long)batch * hw + 255) / 256), nb_z = (int)((n_zero + 255) / 256);
   if (nb_t > 64) nb_t = 64;
   if (nb_x > 256) nb_x = 256;
   if (nb_z > 256) nb_z = 256;
-  PP_DT_SWITCH(dtype, hipLaunchKernelGGL(step_head_kernel<EDT>, dim3(nb_t + nb_x + nb_z), dim3(256), 0, (hipStream_t)stream,
-                                         temb_table, step_dev, temb_out, row_floats, nb_t, latents, batch, c, hw, src_batch_mod,
-                                         (uint16_t*)x_in, ldc, c0, nb_x, (unsigned long long*)zero_dst, n_zero));
+  PP_DT_SWITCH(dtype, hipLaunchKernelGGL((step_head_kernel<EDT, SCALED>), dim3(nb_t + nb_x + nb_z), dim3(256), 0,
+                                         (hipStream_t)stream, temb_table, step_dev, temb_out, row_floats, nb_t, latents, batch, c,
+                                         hw, src_batch_mod, (uint16_t*)x_in, ldc, c0, nb_x, (unsigned long long*)zero_dst, n_zero,
+                                         in_div));
   PP_CHECK_LAUNCH("step_head_kernel");
   return PP_OK;
+}
+}  // namespace
+
+extern "C" int pp_step_head(const float* temb_table, const int32_t* step_dev, float* temb_out, int row_floats,
+                            const float* latents, int batch, int c, int hw, int src_batch_mod, void* x_in, int ldc, int c0,
+                            int dtype, void* zero_dst, long long n_zero, void* stream) {
+  return step_head_launch<false>(temb_table, step_dev, temb_out, row_floats, latents, batch, c, hw, src_batch_mod, x_in, ldc, c0,
+                                 dtype, zero_dst, n_zero, nullptr, stream);
+}
+
+extern "C" int pp_step_head_scaled(const float* temb_table, const int32_t* step_dev, float* temb_out, int row_floats,
+                                   const float* latents, int batch, int c, int hw, int src_batch_mod, void* x_in, int ldc,
+                                   int c0, int dtype, void* zero_dst, long long n_zero, const float* in_div, void* stream) {
+  return step_head_launch<true>(temb_table, step_dev, temb_out, row_floats, latents, batch, c, hw, src_batch_mod, x_in, ldc, c0,
+                                dtype, zero_dst, n_zero, in_div, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ embedding splice

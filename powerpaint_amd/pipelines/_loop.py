@@ -13,7 +13,10 @@ pipeline_PowerPaint_Brushnet_CA.py:1384-1466, pipeline_PowerPaint_ControlNet.py:
     [BrushNet | ControlNet forward]                                   (own launch plan, residuals stay in HBM as NHWC)
     eps          <- UNet(x_in, t, ctx, residuals)
     latents      <- scheduler.step(eps_u + g (eps_c - eps_u), t, latents)   (pp_cfg_sched_step, fp32; an LCMScheduler:
-                                                                       pp_cfg_lcm_step, which adds the step's noise as well)
+                                                                       pp_cfg_lcm_step, which adds the step's noise as well;
+                                                                       Euler / Euler ancestral: pp_cfg_sigma_step, and the
+                                                                       head launch is pp_step_head_scaled -- the networks see
+                                                                       latents / sqrt(sigma^2 + 1), `scale_model_input`)
     [latents     <- (1 - m) add_noise(x0, noise, t_next) + m latents]       (pp_latent_blend; ppt-v1 with a 4-channel UNet)
     step         <- step + 1                                          (pp_step_advance; round 5: by the last block of
                                                                        pp_cfg_sched_step when nothing behind it reads the counter)
@@ -114,6 +117,12 @@ class DenoiseLoop:
             sch.set_eta(self._eta)
         # does the bound scheduler's step consume noise the host draws per step?  (stochastic DDIM, LCM)
         self._noisy = (not self.foreign) and bool(sch.step_noise)
+        # a sigma-space scheduler (Euler, Euler ancestral): the networks' input is scaled per step, at the head of the step
+        sigma = (not self.foreign) and sch.kind in (5, 6)
+        in_div = sch.in_div_table() if sigma else None
+        if sigma and not _temb_table_enabled():
+            raise L.PPError(f"{type(sch).__name__} needs the time-embedding table: without it (PP_TEMB_TABLE=0) the step has "
+                            f"no head launch to scale the network input in")
         self._blend = None
         if blend is not None:
             # loop-owned fp32 copies at stable addresses (a captured graph reads them); first image / first mask only
@@ -215,14 +224,15 @@ class DenoiseLoop:
         else:
             ts, step = sch.timesteps_f32(), sch.step_counter()
             mp = sch.m_prev(lat) if 1 <= sch.kind <= 3 else None  # scheduler state: DPM m_{i-1}; PNDM history + saved
-                                                                    # sample; UniPC (DDIM and LCM keep none)
+                                                                    # sample; UniPC (DDIM, LCM and the Euler classes keep none)
             kind, src = sch.kind, lat
         key = (tuple(latents_shape), bool(do_cfg), bool(guess_mode), self._noisy, float(guidance_scale), id(rt.step_plan),
                tuple(id(r.step_plan) for r in side_rts) if side_rts else None, kind, ts.data_ptr(), step.data_ptr(),
                0 if self.foreign else sch.coef_table().data_ptr(), mp.data_ptr() if mp is not None else 0, src.data_ptr(),
                _temb_table_enabled(), int(ts.numel()), tuple(getattr(r.net.params, "version", 0) for r in [rt] + side_rts),
                tuple(b.data_ptr() for b in self._blend) if self._blend is not None else None,
-               sch.renoise_table().data_ptr() if (self._blend is not None and not self.foreign) else 0)
+               sch.renoise_table().data_ptr() if (self._blend is not None and not self.foreign) else 0,
+               in_div.data_ptr() if sigma else 0)
         if key == self._key and self.program is not None:
             # The conditioning scale is a by-value argument of the zero-conv launches: `prepare` has patched the launch
             # records (eager runs see it), but a graph captured with another value still carries the old one.
@@ -248,10 +258,16 @@ class DenoiseLoop:
                 # time-embedding row + network input + accumulator zeroing: ONE launch at the head of the step (pp_step_head)
                 self._temb[id(r)] = info
                 head_skip[id(r)] = {0}
-                prog.add("step_head", lib.pp_step_head, info["table"].data_ptr(), step.data_ptr(), info["out"], info["total"],
-                         src.data_ptr(), nb_r, Cl, hw, mod if nb_r != B else 0, x.ptr, x.C, 0, L.dtype_code(r.net.dtype),
-                         zero[1][0], zero[1][1])
+                head = (info["table"].data_ptr(), step.data_ptr(), info["out"], info["total"], src.data_ptr(), nb_r, Cl, hw,
+                        mod if nb_r != B else 0, x.ptr, x.C, 0, L.dtype_code(r.net.dtype), zero[1][0], zero[1][1])
+                if sigma:
+                    prog.add("step_head", lib.pp_step_head_scaled, *head, in_div.data_ptr())
+                else:
+                    prog.add("step_head", lib.pp_step_head, *head)
                 continue
+            if sigma:
+                raise L.PPError(f"{type(r.net).__name__}: its step plan has no fused head launch, which "
+                                f"{type(sch).__name__} needs to scale the network input")
             if info is not None:
                 self._temb[id(r)] = info
                 prog.add("temb_row", lib.pp_embed_splice, info["table"].data_ptr(), None, step.data_ptr(), info["out"], 1,
@@ -275,7 +291,11 @@ class DenoiseLoop:
                                 tuple(self._var_noise.shape) != tuple(latents_shape)):
                 self._var_noise = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
             ticket = self._ticket.data_ptr() if fold_advance else None
-            if sch.kind == 4:    # LCM: guidance combine, consistency transition, noise term and counter advance in one launch
+            if sigma:            # Euler (s_up = 0 in every row: the noise pointer is never read) / Euler ancestral
+                noise = self._var_noise if self._noisy else lat
+                prog.add("cfg_sigma_step", lib.pp_cfg_sigma_step, rt.outputs["eps"], int(do_cfg), float(guidance_scale),
+                         lat.data_ptr(), noise.data_ptr(), lat.numel(), sch.coef_table().data_ptr(), step.data_ptr(), ticket)
+            elif sch.kind == 4:  # LCM: guidance combine, consistency transition, noise term and counter advance in one launch
                 prog.add("cfg_lcm_step", lib.pp_cfg_lcm_step, rt.outputs["eps"], int(do_cfg), float(guidance_scale),
                          lat.data_ptr(), self._var_noise.data_ptr(), lat.numel(), sch.coef_table().data_ptr(),
                          step.data_ptr(), ticket)
@@ -499,6 +519,8 @@ class DenoiseLoop:
             if self._noisy and self.scheduler.draws_noise_at(self.scheduler.begin_index + i):
                 self._var_noise.copy_(variance_noise(self._var_noise.shape, self._gen, self._var_noise.device,
                                                      self._noise_dtype))
+            elif self.scheduler.discards_draw:      # (plain Euler: the library draws and does not use it)
+                self.scheduler.discard_draw(self.latents.shape, self._gen, self._noise_dtype)
             if ents is not None:
                 if use_graph:
                     ents[i][0]["graph"].replay()

@@ -8,6 +8,9 @@ The arithmetic restates diffusers==0.27.0 `DDIMScheduler` / `DPMSolverMultistepS
 fp32 torch exactly in the library's operation order and uploaded as a device table `coef[step][8]`; the tensor math
 (CFG combine + step) runs in the fused HIP kernel `pp_cfg_sched_step` on fp32 latents.  `.step()` itself launches
 that kernel, so a foreign loop calling `scheduler.step` still runs on the HIP path.
+
+`EulerDiscreteScheduler` / `EulerAncestralDiscreteScheduler` (and `use_karras_sigmas`) are the sigma-space family: latents
+x0 + sigma eps, `init_noise_sigma` > 1, a real `scale_model_input`, float timesteps; their step is `pp_cfg_sigma_step`.
 """
 from types import SimpleNamespace
 
@@ -28,7 +31,8 @@ _ONLY = {"prediction_type": ("epsilon",), "beta_schedule": ("scaled_linear",), "
          "use_lu_lambdas": (False,), "euler_at_final": (False,), "variance_type": (None,),
          "trained_betas": (None,), "algorithm_type": ("dpmsolver++",), "solver_type": ("midpoint", "bh2"),
          "final_sigmas_type": ("zero",), "lower_order_final": (True,), "lambda_min_clipped": (-float("inf"),),
-         "timestep_spacing": ("leading", "linspace", "trailing")}
+         "timestep_spacing": ("leading", "linspace", "trailing"), "interpolation_type": ("linear",),
+         "timestep_type": ("discrete",), "sigma_min": (None,), "sigma_max": (None,)}
 
 
 def variance_noise(shape, generator, device, dtype) -> torch.Tensor:
@@ -43,20 +47,43 @@ def variance_noise(shape, generator, device, dtype) -> torch.Tensor:
     return z.to(torch.float32).contiguous()
 
 
-def _check_config(cls_name, cfg, keys=None):
+def _check_config(cls_name, cfg, keys=None, allow=()):
     """`keys`: restrict the check to the options the target class's diffusers constructor names (a donor config's other
-    keys never reach it in `from_config`)."""
+    keys never reach it in `from_config`).  `allow`: options this class implements at every value (`use_karras_sigmas` of
+    DPM-Solver++ and the Euler classes)."""
     for k, ok in _ONLY.items():
-        if keys is not None and k not in keys:
+        if (keys is not None and k not in keys) or k in allow:
             continue
         if k in cfg and cfg[k] not in ok:
             raise L.PPError(f"{cls_name}: {k}={cfg[k]!r} is not implemented on the HIP path (supported: {ok})")
+
+
+def karras_sigmas(sigma_min, sigma_max, n, rho=7.0):
+    """Karras et al. (arXiv:2206.00364, eq. 5) as the library's `_convert_to_karras` evaluates it, float64: n noise levels
+    from sigma_max down to sigma_min, uniform in sigma^(1/rho)."""
+    ramp = np.linspace(0, 1, n)
+    lo, hi = float(sigma_min) ** (1 / rho), float(sigma_max) ** (1 / rho)
+    return (hi + ramp * (lo - hi)) ** rho
+
+
+def sigma_to_t(sigma, log_sigmas):
+    """The library's `_sigma_to_t`: the (fractional) training timestep whose log sigma, linearly interpolated over the
+    table, equals log `sigma`."""
+    log_sigma = np.log(np.maximum(sigma, 1e-10))
+    dists = log_sigma - log_sigmas[:, np.newaxis]
+    low_idx = np.cumsum((dists >= 0), axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+    high_idx = low_idx + 1
+    low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+    w = np.clip((low - log_sigma) / (low - high), 0, 1)
+    return ((1 - w) * low_idx + w * high_idx).reshape(np.shape(sigma))
 
 
 class _SchedulerBase:
     order = 1
     init_noise_sigma = 1.0
     kind = -1
+    _ALLOWED = ()            # options of `_ONLY` this class implements at every value
+    discards_draw = False    # the library's step draws noise it does not use (plain Euler): `_SigmaScheduler.discard_draw`
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, **cfg):
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start,
@@ -71,6 +98,7 @@ class _SchedulerBase:
         self._m_prev = None
         self._device = None
         self._begin = 0
+        self._dup_calls = {}
 
     def set_begin_index(self, begin_index: int = 0):
         """diffusers' `set_begin_index`: the loop enters the schedule at row `begin_index` (`strength < 1`: the pipelines'
@@ -98,7 +126,7 @@ class _SchedulerBase:
         import inspect
         src = dict(config) if isinstance(config, dict) else dict(vars(config))
         src.update(kw)
-        _check_config(cls.__name__, src)
+        _check_config(cls.__name__, src, allow=cls._ALLOWED)
         names = set(inspect.signature(cls.__init__).parameters) - {"self", "kw", "cfg"}
         return cls(**{k: v for k, v in src.items() if k in names})
 
@@ -123,6 +151,7 @@ class _SchedulerBase:
             self.timesteps = self.timesteps.to(self._device)
         if self._m_prev is not None:
             self._m_prev.zero_()
+        self._dup_calls = {}
 
     def coef_table(self) -> torch.Tensor:
         return self._coef_dev
@@ -138,9 +167,7 @@ class _SchedulerBase:
         `add_noise(x0, noise, timesteps[i + 1])` multiplies x0 and the noise by AFTER step i -- (sqrt(abar), sqrt(1-abar))
         of the next timestep, (1, 0) after the last one.  The ppt-v1 loop with a 4-channel UNet re-noises the known
         region with it every step (pipeline_PowerPaint.py:1025-1039; pp_latent_blend)."""
-        ts = self._ts_host.long()
-        a = self.alphas_cumprod[ts[1:]].to(torch.float32)
-        tab = torch.stack([torch.cat([a ** 0.5, torch.ones(1)]), torch.cat([(1 - a) ** 0.5, torch.zeros(1)])], 1)
+        tab = self._renoise_rows()
         dev = self._device if self._device is not None else "cpu"
         cur = getattr(self, "_renoise_dev", None)
         want = torch.device(dev)
@@ -150,6 +177,11 @@ class _SchedulerBase:
         else:
             self._renoise_dev = tab.to(dev).contiguous()
         return self._renoise_dev
+
+    def _renoise_rows(self) -> torch.Tensor:
+        ts = self._ts_host.long()
+        a = self.alphas_cumprod[ts[1:]].to(torch.float32)
+        return torch.stack([torch.cat([a ** 0.5, torch.ones(1)]), torch.cat([(1 - a) ** 0.5, torch.zeros(1)])], 1)
 
     state_slots = 1          # fp32 copies of the latents the step kernel keeps between steps (DPM: 1, PNDM: 5)
 
@@ -164,13 +196,20 @@ class _SchedulerBase:
             self._step_dev.fill_(self._begin)
         if self._m_prev is not None:
             self._m_prev.zero_()
+        self._dup_calls = {}
 
     def _index_of(self, timestep) -> int:
-        t = int(timestep)
-        idx = (self._ts_host == t).nonzero()
-        if len(idx) == 0:
+        """Row of `timestep`.  A timestep the schedule holds more than once (PLMS repeats its second entry, rounded Karras
+        timesteps can coincide) is disambiguated by call order: a foreign loop calls step() once per entry."""
+        t = float(timestep) if self._ts_host.is_floating_point() else int(timestep)
+        idx = (self._ts_host == t).nonzero().flatten().tolist()
+        if not idx:
             raise ValueError(f"timestep {t} is not in the schedule")
-        return int(idx[0])
+        if len(idx) == 1:
+            return idx[0]
+        calls = self._dup_calls.get(t, 0)
+        self._dup_calls[t] = calls + 1
+        return idx[min(calls, len(idx) - 1)]
 
     def set_eta(self, eta: float = 0.0):
         """`eta` of the pipelines (pipeline_PowerPaint.py:736-745): only DDIM's step takes it, the other schedulers
@@ -301,15 +340,20 @@ def dpm_timesteps(T, n, spacing="linspace", steps_offset=0):
 
 
 class DPMSolverMultistepScheduler(_SchedulerBase):
-    """dpmsolver++ (2M), midpoint, `linspace` spacing, final_sigmas_type = "zero", lower_order_final."""
+    """dpmsolver++ (2M), midpoint, `linspace` spacing, final_sigmas_type = "zero", lower_order_final.
+    use_karras_sigmas ("DPM++ 2M Karras"): the noise levels are Karras et al.'s rho = 7 ramp between the ends of the full
+    training table and the timesteps are their rounded `sigma_to_t` (the spacing options then have no effect, as in the
+    library); only the host table changes."""
     kind = 1
+    _ALLOWED = ("use_karras_sigmas",)
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, solver_order=2,
-                 timestep_spacing="linspace", steps_offset=0, **kw):
+                 timestep_spacing="linspace", steps_offset=0, use_karras_sigmas=False, **kw):
         _check_config("DPMSolverMultistepScheduler", kw)
         super().__init__(num_train_timesteps, beta_start, beta_end, solver_order=solver_order, steps_offset=steps_offset,
                          algorithm_type="dpmsolver++", solver_type="midpoint", final_sigmas_type="zero",
-                         timestep_spacing=timestep_spacing, prediction_type="epsilon")
+                         timestep_spacing=timestep_spacing, prediction_type="epsilon",
+                         use_karras_sigmas=bool(use_karras_sigmas))
         if solver_order != 2:
             raise NotImplementedError("only the 2M solver is on the hot path")
         if timestep_spacing not in ("linspace", "leading", "trailing"):
@@ -325,7 +369,12 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         self.num_inference_steps = num_inference_steps
         ts = dpm_timesteps(T, num_inference_steps, self.config.timestep_spacing, self.config.steps_offset)
         sig = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
-        sig = np.interp(ts, np.arange(0, len(sig)), sig)
+        if self.config.use_karras_sigmas:
+            log_sig = np.log(sig)
+            sig = karras_sigmas(sig[0], sig[-1], num_inference_steps)
+            ts = np.array([sigma_to_t(v, log_sig) for v in sig]).round().astype(np.int64)
+        else:
+            sig = np.interp(ts, np.arange(0, len(sig)), sig)
         self.sigmas = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
         self._ts_host = torch.from_numpy(ts)
         self.timesteps = self._ts_host.clone()
@@ -426,23 +475,6 @@ class PNDMScheduler(_SchedulerBase):
             coef[r, 10], coef[r, 11] = 0.0, (1.0 if k == 0 else 0.0)      # the first evaluation saves its input sample
             head = (head + 1) % 4
         self._coef = coef
-
-    def _index_of(self, timestep) -> int:
-        """The repeated timestep is disambiguated by call order (a foreign loop calls step() once per entry)."""
-        t = int(timestep)
-        idx = (self._ts_host == t).nonzero().flatten().tolist()
-        if not idx:
-            raise ValueError(f"timestep {t} is not in the schedule")
-        if len(idx) == 1:
-            return idx[0]
-        self._dup_calls = getattr(self, "_dup_calls", 0)
-        i = idx[min(self._dup_calls, len(idx) - 1)]
-        self._dup_calls += 1
-        return i
-
-    def reset(self):
-        super().reset()
-        self._dup_calls = 0
 
 
 class UniPCMultistepScheduler(_SchedulerBase):
@@ -722,6 +754,187 @@ class LCMScheduler(_SchedulerBase):
         return SimpleNamespace(prev_sample=out, denoised=None)
 
 
+class _SigmaScheduler(_SchedulerBase):
+    """The sigma-space family (Karras et al., arXiv:2206.00364; k-diffusion `sample_euler` / `sample_euler_ancestral`) as
+    diffusers 0.27 runs it on a variance-preserving checkpoint: the latents are x = x0 + sigma eps with
+    sigma = sqrt((1 - abar) / abar), the network sees x / sqrt(sigma^2 + 1) (`scale_model_input`; in the fused loop
+    pp_step_head_scaled with `in_div_table()`), and the initial noise is multiplied by `init_noise_sigma` > 1.
+
+    Grid: fp32 timesteps per `timestep_spacing`, sigmas interpolated linearly over the training table, 0 appended.
+    use_karras_sigmas: the rho = 7 ramp between the ends of that inference grid, timesteps = the fractional `sigma_to_t`.
+    Table row = (sigma_i, dt, s_up, 0 ...), evaluated in fp32 torch in the library's operation order; the tensor math
+    x' = x + dt e + s_up z runs in `pp_cfg_sigma_step`.  No state between steps."""
+    _ALLOWED = ("use_karras_sigmas",)
+    # arithmetic options of the library's constructors that the fused step does not implement at another value
+    _CHECKED = ("prediction_type", "beta_schedule", "trained_betas", "rescale_betas_zero_snr", "interpolation_type",
+                "timestep_type", "final_sigmas_type", "timestep_spacing", "sigma_min", "sigma_max")
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, timestep_spacing="linspace",
+                 steps_offset=0, use_karras_sigmas=False, **kw):
+        _check_config(type(self).__name__, dict(kw, timestep_spacing=timestep_spacing), self._CHECKED)
+        super().__init__(num_train_timesteps, beta_start, beta_end, timestep_spacing=timestep_spacing,
+                         steps_offset=steps_offset, use_karras_sigmas=bool(use_karras_sigmas), prediction_type="epsilon",
+                         interpolation_type="linear", timestep_type="discrete", final_sigmas_type="zero")
+        self._sig_all = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()        # fp32, as the library's
+        self._in_div_dev = None
+
+    @classmethod
+    def from_config(cls, config, **kw):
+        """`EulerAncestralDiscreteScheduler.from_config(pipe.scheduler.config)`: betas, `timestep_spacing` and `steps_offset`
+        of the donor (an SD-1.5 checkpoint: `leading`, 1) are taken over; of its other keys only those the library's Euler
+        constructors name as well can change the arithmetic and are checked."""
+        import inspect
+        src = dict(config) if isinstance(config, dict) else dict(vars(config))
+        src.update(kw)
+        _check_config(cls.__name__, src, cls._CHECKED)
+        names = set(inspect.signature(cls.__init__).parameters) - {"self", "kw"}
+        return cls(**{k: v for k, v in src.items() if k in names})
+
+    @property
+    def init_noise_sigma(self):
+        """The library's property: the largest sigma of the current grid (of the training table before `set_timesteps`),
+        sqrt(max^2 + 1) with `leading` spacing."""
+        m = float(self.sigmas.max()) if self.timesteps is not None else float(self._sig_all.max())
+        return m if self.config.timestep_spacing in ("linspace", "trailing") else (m ** 2 + 1) ** 0.5
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        T, n = self.config.num_train_timesteps, num_inference_steps
+        self.num_inference_steps = n
+        sp = self.config.timestep_spacing
+        if sp == "linspace":
+            ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
+        elif sp == "leading":
+            ts = (np.arange(0, n) * (T // n)).round()[::-1].copy().astype(np.float32) + self.config.steps_offset
+        else:
+            ts = np.arange(T, 0, -T / n).round().copy().astype(np.float32) - 1
+        sig = np.interp(ts, np.arange(0, len(self._sig_all)), self._sig_all)
+        if self.config.use_karras_sigmas:
+            log_sig = np.log(self._sig_all)
+            sig = karras_sigmas(sig[-1], sig[0], n)
+            ts = np.array([sigma_to_t(v, log_sig) for v in sig])
+        self.sigmas = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
+        self._ts_host = torch.from_numpy(ts.astype(np.float32))
+        self.timesteps = self._ts_host.clone()
+        self._begin = 0
+        self._fill_table()
+        self._upload(device)
+
+    def _sigma_up(self, s_from, s_to):
+        return torch.zeros(())
+
+    def _fill_table(self):
+        """(rows do not depend on where the loop enters: no history)"""
+        n = self.num_inference_steps
+        coef = torch.zeros(n, 8, dtype=torch.float32)
+        for i in range(n):
+            s_from, s_to = self.sigmas[i], self.sigmas[i + 1]
+            s_up = self._sigma_up(s_from, s_to)
+            s_down = (s_to ** 2 - s_up ** 2) ** 0.5
+            coef[i, 0], coef[i, 1], coef[i, 2] = s_from, s_down - s_from, s_up
+        self._coef = coef
+        self._in_div = (self.sigmas[:-1] ** 2 + 1) ** 0.5
+
+    def _upload(self, device):
+        super()._upload(device)
+        if self._device is not None and self._device.type == "cuda":
+            cur = self._in_div_dev
+            if cur is not None and cur.shape == self._in_div.shape and cur.device == self._coef_dev.device:
+                cur.copy_(self._in_div)            # (stable address: a captured step graph reads it)
+            else:
+                self._in_div_dev = self._in_div.to(self._coef_dev.device).contiguous()
+
+    def in_div_table(self) -> torch.Tensor:
+        """[rows] fp32 on the scheduler's device, indexed by the step counter: sqrt(sigma_i^2 + 1), what
+        `scale_model_input` divides the latents by at step i (pp_step_head_scaled)."""
+        return self._in_div_dev
+
+    def scale_model_input(self, sample, timestep=None):
+        i = self._peek_index(timestep)
+        return sample / self._in_div[i].to(sample.device)          # (the divisor of the fused head launch, to the bit)
+
+    def _peek_index(self, timestep) -> int:
+        idx = (self._ts_host == float(timestep)).nonzero().flatten().tolist()
+        if not idx:
+            raise ValueError(f"timestep {float(timestep)} is not in the schedule")
+        return idx[0]
+
+    def _renoise_rows(self) -> torch.Tensor:
+        """(1, sigma_{i+1}) after step i, (1, 0) after the last one: `add_noise(x0, noise, timesteps[i + 1])` in sigma
+        space, in the layout pp_latent_blend reads."""
+        return torch.stack([torch.ones(len(self._ts_host)), self.sigmas[1:]], 1).contiguous()
+
+    def add_noise(self, original_samples, noise, timesteps):
+        sig = self.sigmas.to(device=original_samples.device, dtype=original_samples.dtype)
+        s = sig[[self._peek_index(t) for t in timesteps.reshape(-1)]].flatten()
+        while s.dim() < original_samples.dim():
+            s = s.unsqueeze(-1)
+        return original_samples + noise * s
+
+    def draws_noise_at(self, row: int) -> bool:
+        return True          # the library's step calls randn_tensor on every step, the last one included
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, **kw):
+        """x_i -> x_{i+1} in `pp_cfg_sigma_step` (fp32 math).  Returns a NEW tensor in sample's dtype.  The noise is drawn
+        like the library's `randn_tensor(model_output.shape, generator=generator, ...)`: on every step, also where it is
+        not used (plain Euler; the last ancestral step) -- the caller's generator ends where the library leaves it."""
+        if not sample.is_cuda:
+            raise L.PPError("scheduler.step needs CUDA tensors: the step runs in the HIP kernel, no CPU fallback")
+        i = self._index_of(timestep)
+        x = sample.detach().to(torch.float32).contiguous().clone()
+        e = model_output.detach().to(torch.float32).contiguous()
+        step = torch.full((1,), i, dtype=torch.int32, device=x.device)
+        if self.step_noise:
+            z = variance_noise(model_output.shape, generator, x.device, model_output.dtype)
+        else:
+            self.discard_draw(model_output.shape, generator, model_output.dtype)
+            z = x                                       # (s_up = 0: never read, any valid address does)
+        L.check(L.lib().pp_cfg_sigma_step(e.data_ptr(), 0, 0.0, x.data_ptr(), z.data_ptr(), x.numel(),
+                                           self._coef_dev.data_ptr(), step.data_ptr(), None,
+                                           torch.cuda.current_stream().cuda_stream), "pp_cfg_sigma_step")
+        out = x.to(sample.dtype)
+        if not return_dict:
+            return (out,)
+        return SimpleNamespace(prev_sample=out, pred_original_sample=None)
+
+    @staticmethod
+    def discard_draw(shape, generator, dtype):
+        """Advance `generator` by one `randn_tensor(shape)` without keeping or uploading the numbers.  (No generator: the
+        library would use the global RNG, which nothing here has to stay in step with.)"""
+        gens = generator if isinstance(generator, (list, tuple)) else [generator]
+        sh = tuple(shape) if len(gens) == 1 else (1,) + tuple(shape[1:])
+        for g in gens:
+            if isinstance(g, torch.Generator):
+                torch.randn(sh, generator=g, device=g.device, dtype=dtype)
+
+
+class EulerDiscreteScheduler(_SigmaScheduler):
+    """diffusers-0.27 `EulerDiscreteScheduler` ("Euler", with use_karras_sigmas "Euler Karras") at s_churn = 0:
+    x' = x + (sigma_{i+1} - sigma_i) e.  The library's step draws `randn_tensor` on every step even though gamma = 0 makes
+    it unused; `discards_draw` tells the loop to advance the caller's generator the same way (host only, no upload)."""
+    kind = 5
+    discards_draw = True
+
+    def step(self, model_output, timestep, sample, s_churn: float = 0.0, s_tmin: float = 0.0,
+             s_tmax: float = float("inf"), s_noise: float = 1.0, generator=None, return_dict: bool = True, **kw):
+        if float(s_churn) != 0.0:
+            raise L.PPError(f"EulerDiscreteScheduler: s_churn={s_churn!r} is not implemented on the HIP path (0 only)")
+        return super().step(model_output, timestep, sample, generator=generator, return_dict=return_dict)
+
+
+class EulerAncestralDiscreteScheduler(_SigmaScheduler):
+    """diffusers-0.27 `EulerAncestralDiscreteScheduler` ("Euler a"): s_up = sqrt(s_to^2 (s_from^2 - s_to^2) / s_from^2),
+    s_down = sqrt(s_to^2 - s_up^2), x' = x + (s_down - s_from) e + s_up z with fresh Gaussian z on every step (on the last
+    one s_up = 0 and the drawn z is not read)."""
+    kind = 6
+
+    @property
+    def step_noise(self) -> bool:
+        return True
+
+    def _sigma_up(self, s_from, s_to):
+        return (s_to ** 2 * (s_from ** 2 - s_to ** 2) / s_from ** 2) ** 0.5
+
+
 SCHEDULERS = {"DDIMScheduler": DDIMScheduler, "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
               "PNDMScheduler": PNDMScheduler, "UniPCMultistepScheduler": UniPCMultistepScheduler,
-              "LCMScheduler": LCMScheduler}
+              "LCMScheduler": LCMScheduler, "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler}
