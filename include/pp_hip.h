@@ -325,6 +325,10 @@ int pp_layernorm(const void* x, int rows, int C, const float* gamma, const float
  *   vt : bf16 V TRANSPOSED, element (b, t, h, j) at vt[((b*heads + h)*d + j)*ldvt + t]   (ldvt >= nk, mult of 8)
  *   o  : bf16, same indexing as q with ldo.
  * head_dim d in {40, 80, 160}; nk arbitrary (keys >= nk masked).
+ * Padding: columns [nk, ldvt) of vt, and whatever follows the last row of K (item batch-1, key nk-1) in its buffer, may
+ * hold any FINITE values -- a kernel may load them but they never reach the result; non-finite padding is not supported
+ * (a masked probability is an exact 0, and 0 * NaN is NaN).  Nothing outside rows [0, batch*nq) x columns [0, heads*d)
+ * of o is written.  (tests/test_attention_exact_gpu.py runs every kernel on poisoned pads and a sentinel-filled o.)
  */
 int pp_attention_fwd(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo,
                      int batch, int heads, int nq, int nk, int d, float scale, int dtype, void* stream);

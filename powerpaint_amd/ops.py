@@ -244,12 +244,25 @@ def transpose_v(v: torch.Tensor, batch: int, nk: int, ldvt: Optional[int] = None
     return vt
 
 
+def _attn_out(out, ldo, rows: int, cols: int, like: torch.Tensor) -> torch.Tensor:
+    """The [rows, cols] output view of the attention wrappers: `out` (a caller's view, its row stride is the ldo the kernel
+    gets; elements outside the view are the caller's) or a new buffer with row stride `ldo` (default: tight)."""
+    if out is None:
+        return torch.empty(rows, ldo or cols, dtype=like.dtype, device=like.device)[:, :cols]
+    if (tuple(out.shape) != (rows, cols) or out.stride(1) != 1 or out.dtype != like.dtype or out.device != like.device
+            or (ldo is not None and ldo != out.stride(0))):
+        raise L.PPError(f"attention: `out` must be a [{rows}, {cols}] row-major view of the inputs' format (row stride = ldo)")
+    return out
+
+
 def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, heads: int, nq: int, nk: int,
-                    causal: bool = False, scale: Optional[float] = None):
-    """q [batch*nq, >=heads*64], k / v [batch*nk, ...] row-major bf16 (row strides from the tensors) -> o [batch*nq, heads*64]."""
+                    causal: bool = False, scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                    ldo: Optional[int] = None):
+    """q [batch*nq, >=heads*64], k / v [batch*nk, ...] row-major bf16 (row strides from the tensors) -> o [batch*nq, heads*64]
+    (out / ldo: see _attn_out)."""
     d = 64
-    o = torch.empty(batch * nq, heads * d, dtype=q.dtype, device=q.device)
-    L.check(L.lib().pp_attention_small(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), heads * d,
+    o = _attn_out(out, ldo, batch * nq, heads * d, q)
+    L.check(L.lib().pp_attention_small(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0),
                                        batch, heads, nq, nk, d, scale if scale is not None else d ** -0.5, int(causal),
                                        L.dtype_code(q.dtype), _s()), "pp_attention_small")
     return o
@@ -265,13 +278,14 @@ def softmax_rows(s: torch.Tensor, scale: float = 1.0, dtype=torch.bfloat16):
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, batch: int, heads: int, nq: int, nk: int, d: int,
-              scale: Optional[float] = None, variant: int = L.PP_ATTN_AUTO):
+              scale: Optional[float] = None, variant: int = L.PP_ATTN_AUTO, out: Optional[torch.Tensor] = None,
+              ldo: Optional[int] = None):
     """q [batch*nq, >=heads*d] / k [batch*nk, ...] row-major bf16 (row strides taken from the tensors);
-    vt [batch, heads*d, ldvt].  Returns o [batch*nq, heads*d].  `variant` names the kernel (L.PP_ATTN_*): AUTO is what
-    the pipelines run; a named kernel raises PP_ERR_UNSUPPORTED on a shape it does not cover."""
-    o = torch.empty(batch * nq, heads * d, dtype=q.dtype, device=q.device)
+    vt [batch, heads*d, ldvt].  Returns o [batch*nq, heads*d] (out / ldo: see _attn_out).  `variant` names the kernel
+    (L.PP_ATTN_*): AUTO is what the pipelines run; a named kernel raises PP_ERR_UNSUPPORTED on a shape it does not cover."""
+    o = _attn_out(out, ldo, batch * nq, heads * d, q)
     L.check(L.lib().pp_attention_fwd_variant(_p(q), q.stride(0), _p(k), k.stride(0), _p(vt), vt.stride(1), _p(o),
-                                             heads * d, batch, heads, nq, nk, d,
+                                             o.stride(0), batch, heads, nq, nk, d,
                                              scale if scale is not None else d ** -0.5, L.dtype_code(q.dtype),
                                              int(variant), _s()), "pp_attention_fwd")
     return o
