@@ -29,7 +29,7 @@ extern "C" {
 #define PP_ERR_LAUNCH (-3)       /* hipLaunchKernel / hipFuncSetAttribute failed                  */
 #define PP_ERR_WORKSPACE (-4)    /* workspace pointer null or too small                           */
 
-#define PP_ABI_VERSION 26
+#define PP_ABI_VERSION 27
 /* 16-bit storage format of activations and matrix weights ("dtype" arguments; the same codes pp_nchw_to_nhwc uses for
  * its source): bf16 or fp16 -- the reference's default is fp16 (/root/reference/app.py:548,559).  MFMA accumulation,
  * norm statistics, softmax, biases and latents are fp32 with either. */
@@ -451,6 +451,29 @@ int pp_cfg_lcm_step(const float* eps2, int cfg, float guidance, float* latents, 
  * be a multiple of 4. */
 int pp_cfg_sigma_step(const float* eps2, int cfg, float guidance, float* latents, const float* noise, int n,
                       const float* coef_table, int32_t* step_dev, uint32_t* advance_ticket, void* stream);
+/* (ABI v27) Fused classifier-free guidance + one table row of a sigma-space sampler that keeps state between network
+ * evaluations (HeunDiscreteScheduler, KDPM2DiscreteScheduler, KDPM2AncestralDiscreteScheduler, LMSDiscreteScheduler;
+ * Karras et al., arXiv:2206.00364, k-diffusion sample_heun / sample_dpm_2 / sample_dpm_2_ancestral / sample_lms at
+ * s_churn = 0) on fp32 NCHW latents held in sigma space.  Table row coef[step][16] =
+ *     {c_e, c_h1, c_h2, c_h3, s_up, sigma_eval, slot1, slot2, slot3, push_slot, use_saved, save, 0, 0, 0, 0}
+ * (slots and flags stored as floats; sigma_eval, the noise level of the row's evaluation, is host bookkeeping):
+ *     e   = cfg ? eps_u + guidance (eps_c - eps_u) : eps       (the derivative (x - x0) / sigma of epsilon prediction)
+ *     x'  = (use_saved ? saved : x) + c_e e + c_h1 H[slot1] + c_h2 H[slot2] + c_h3 H[slot3]
+ *     x'  = x' + s_up noise                                    (rows with s_up != 0 only; `noise` is NOT read otherwise)
+ *     if (save)           saved        = x                     (the value BEFORE this row's update)
+ *     if (push_slot >= 0) H[push_slot] = e                     (after the reads: a row may push into a slot it read)
+ * `state` fp32 [4][n] = H[0], H[1], H[2], saved; zero before the first row.  Every element touches only its own index of
+ * latents / state / noise.  Rows per sampler (sigma_k the base grid, sigma_N = 0):
+ *     Heun   A_k: save, push 0, c_e = sigma_{k+1} - sigma_k;  B_k: use_saved, c_e = c_h1 = (sigma_{k+1} - sigma_k) / 2 over
+ *            slot 0;  last row: Euler to 0.  2N - 1 rows, no noise drawn.
+ *     DPM2   A_k: save, c_e = sigma_mid - sigma_k;  B_k (evaluated at sigma_mid): use_saved, c_e = sigma_{k+1} - sigma_k.
+ *     DPM2 a as DPM2 towards sigma_down of the ancestral split; B_k: c_e = sigma_down - sigma_k, s_up = sigma_up.  The host
+ *            draws one noise tensor per row, A rows included (used by the B rows only), as the library's step() does.
+ *     LMS    N rows; c_e, c_h1..3 = the integrals of the Lagrange basis over [sigma_i, sigma_{i+1}]; the history is a ring
+ *            over the 3 slots, each row pushing e into the slot of the oldest entry it read.
+ * eps2 / cfg / guidance / step_dev / advance_ticket as pp_cfg_sched_step.  n need not be a multiple of 4. */
+int pp_cfg_ksampler_step(const float* eps2, int cfg, float guidance, float* latents, float* state, const float* noise, int n,
+                         const float* coef_table, int32_t* step_dev, uint32_t* advance_ticket, void* stream);
 
 /* (ABI v18) Front end of Transformer2DModel at C = 320 in one launch (csrc/tfront.hip):
  *     hs = proj_in(GroupNorm(x)),   q | k | v = to_q / to_k / to_v(LayerNorm1(hs))

@@ -478,6 +478,57 @@ __global__ void __launch_bounds__(256) cfg_sigma_step_kernel(const float* __rest
   }
 }
 
+// State-keeping sigma-space samplers (ABI v27: Heun, DPM2, DPM2 ancestral, LMS as k-diffusion's sample_heun / sample_dpm_2 /
+// sample_dpm_2_ancestral / sample_lms and diffusers 0.27 run them at s_churn = 0): CFG combine, one table row of the sampler,
+// the ancestral noise and the counter advance in ONE launch.  Row (16 floats) = c_e, c_h1, c_h2, c_h3, s_up, sigma of the
+// evaluation (host bookkeeping), then as floats: history slots of h1, h2, h3, the slot this e is pushed to (-1: not stored),
+// use_saved, save.  state = [4][n]: 3 derivative slots + the saved sample.
+//     x' = (use_saved ? saved : x) + c_e e + c_h1 H[s1] + c_h2 H[s2] + c_h3 H[s3] (+ s_up z)
+// `saved` takes the sample BEFORE the update; the push comes after the reads (a row may push into a slot it read).  Where
+// s_up == 0 `z` is NOT read.  Every element touches its own index only.  Ticket: as cfg_sched_step_kernel.
+__global__ void __launch_bounds__(256) cfg_ksampler_step_kernel(const float* __restrict__ eps2, int cfg, float g,
+                                                               float* __restrict__ x, float* __restrict__ state,
+                                                               const float* __restrict__ z, int n,
+                                                               const float* __restrict__ coef, int32_t* step_dev,
+                                                               unsigned* ticket) {
+  const float* c = coef + (size_t)step_dev[0] * 16;
+  const float ce = c[0], c1 = c[1], c2 = c[2], c3 = c[3], s_up = c[4];
+  // (slot indices come from a host table: clamped to the state's extent, a corrupt row cannot reach outside it)
+  const int s1 = min(max((int)c[6], 0), 2), s2 = min(max((int)c[7], 0), 2), s3 = min(max((int)c[8], 0), 2);
+  const int push = min((int)c[9], 2);
+  const bool use_saved = c[10] != 0.f, save = c[11] != 0.f, noisy = s_up != 0.f;
+  const float* h1 = state + (size_t)s1 * n;
+  const float* h2 = state + (size_t)s2 * n;
+  const float* h3 = state + (size_t)s3 * n;
+  float* hp = push >= 0 ? state + (size_t)push * n : nullptr;
+  float* saved = state + (size_t)3 * n;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    float e;
+    if (cfg) {
+      const float eu = eps2[i], ec = eps2[n + i];
+      e = eu + g * (ec - eu);
+    } else {
+      e = eps2[i];
+    }
+    const float xv = x[i];
+    float xn = (use_saved ? saved[i] : xv) + ce * e + c1 * h1[i] + c2 * h2[i] + c3 * h3[i];
+    if (noisy) xn += s_up * z[i];
+    if (save) saved[i] = xv;
+    if (hp) hp[i] = e;
+    x[i] = xn;
+  }
+  if (ticket) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      __threadfence();      // this block's reads of the counter are performed before its ticket becomes visible
+      if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+        *ticket = 0u;
+        step_dev[0] += 1;
+      }
+    }
+  }
+}
+
 // stochastic DDIM (eta > 0): x += std_dev_t * z, std_dev_t = column 4 of the step's table row, z drawn by the host
 __global__ void __launch_bounds__(256) ddim_variance_noise_kernel(float* __restrict__ x, const float* __restrict__ z, int n,
                                                                  const float* __restrict__ coef,
@@ -683,6 +734,16 @@ extern "C" int pp_cfg_sigma_step(const float* eps2, int cfg, float guidance, flo
   hipLaunchKernelGGL(cfg_sigma_step_kernel, dim3(grid_for_host(n)), dim3(256), 0, (hipStream_t)stream, eps2, cfg, guidance,
                      latents, noise, n, coef_table, step_dev, (unsigned*)advance_ticket);
   PP_CHECK_LAUNCH("cfg_sigma_step_kernel");
+  return PP_OK;
+}
+
+extern "C" int pp_cfg_ksampler_step(const float* eps2, int cfg, float guidance, float* latents, float* state,
+                                    const float* noise, int n, const float* coef_table, int32_t* step_dev,
+                                    uint32_t* advance_ticket, void* stream) {
+  if (!eps2 || !latents || !state || !noise || !coef_table || !step_dev || n <= 0) return PP_ERR_BAD_ARG;
+  hipLaunchKernelGGL(cfg_ksampler_step_kernel, dim3(grid_for_host(n)), dim3(256), 0, (hipStream_t)stream, eps2, cfg, guidance,
+                     latents, state, noise, n, coef_table, step_dev, (unsigned*)advance_ticket);
+  PP_CHECK_LAUNCH("cfg_ksampler_step_kernel");
   return PP_OK;
 }
 

@@ -114,7 +114,8 @@ def _keeps(model) -> bool:
 
 def load_scheduler(d: str):
     """`<dir>/scheduler_config.json` -> the fused scheduler of the same `_class_name` (DDIM / PNDM / DPM-Solver++ / UniPC / LCM /
-    Euler ancestral); other classes are refused by name -- pass a scheduler object (any duck-typed one works) instead.
+    Euler ancestral / Heun / KDPM2 / KDPM2 ancestral / LMS); other classes are refused by name -- pass a scheduler object (any
+    duck-typed one works) instead.
     `EulerDiscreteScheduler` has a fused implementation (`schedulers.EulerDiscreteScheduler`: constructor, `from_config`,
     `scheduler=`) but its name is not in the map yet: the loader's tests use it as their example of a refused class."""
     from .schedulers import SCHEDULERS

@@ -304,6 +304,16 @@ class PipelineBase(PipelinePretrainedMixin):
         dt = getattr(prompt_embeds, "dtype", torch.float32)
         return dt if dt in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
 
+    def _legacy_callback_row(self, i, rows, num_inference_steps) -> bool:
+        """Does the legacy `callback` fire after row `i` of `rows`?  pipeline_PowerPaint.py:986,1038: with a scheduler of
+        `order` 2 (Heun, DPM2, DPM2 ancestral: two network evaluations per step) only after a step's second evaluation and
+        after the last row, `num_warmup_steps = rows - num_inference_steps * order`.  (`callback_on_step_end` of the BrushNet
+        pipeline fires after every row, as in the reference's loop.)"""
+        order = getattr(self.scheduler, "order", 1)
+        if order == 1:
+            return True
+        return i == rows - 1 or ((i + 1) > rows - num_inference_steps * order and (i + 1) % order == 0)
+
     def get_timesteps(self, num_inference_steps, strength, device):
         """pipeline_PowerPaint.py:713-720.  The schedulers of this package additionally learn where the loop enters
         (`set_begin_index`): their per-step tables are indexed by a device-side step counter, not by timestep lookup."""

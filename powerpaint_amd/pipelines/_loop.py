@@ -16,7 +16,10 @@ pipeline_PowerPaint_Brushnet_CA.py:1384-1466, pipeline_PowerPaint_ControlNet.py:
                                                                        pp_cfg_lcm_step, which adds the step's noise as well;
                                                                        Euler / Euler ancestral: pp_cfg_sigma_step, and the
                                                                        head launch is pp_step_head_scaled -- the networks see
-                                                                       latents / sqrt(sigma^2 + 1), `scale_model_input`)
+                                                                       latents / sqrt(sigma^2 + 1), `scale_model_input`;
+                                                                       Heun / DPM2 / DPM2 ancestral / LMS: the same head and
+                                                                       pp_cfg_ksampler_step, one "step" per table row, i.e.
+                                                                       per network evaluation)
     [latents     <- (1 - m) add_noise(x0, noise, t_next) + m latents]       (pp_latent_blend; ppt-v1 with a 4-channel UNet)
     step         <- step + 1                                          (pp_step_advance; round 5: by the last block of
                                                                        pp_cfg_sched_step when nothing behind it reads the counter)
@@ -117,8 +120,13 @@ class DenoiseLoop:
             sch.set_eta(self._eta)
         # does the bound scheduler's step consume noise the host draws per step?  (stochastic DDIM, LCM)
         self._noisy = (not self.foreign) and bool(sch.step_noise)
-        # a sigma-space scheduler (Euler, Euler ancestral): the networks' input is scaled per step, at the head of the step
-        sigma = (not self.foreign) and sch.kind in (5, 6)
+        # a sigma-space scheduler (Euler, Euler ancestral; Heun, DPM2, DPM2 ancestral, LMS): the networks' input is scaled
+        # per row of the schedule, at the head of the step
+        sigma = (not self.foreign) and 5 <= sch.kind <= 10
+        ksampler = sigma and sch.kind >= 7                   # ... that keeps state between the evaluations
+        if ksampler and blend is not None and getattr(sch, "blend_refused", None):
+            raise L.PPError(f"{type(sch).__name__}: the known-region blend of a 4-channel UNet is not implemented -- "
+                            f"{sch.blend_refused}")
         in_div = sch.in_div_table() if sigma else None
         if sigma and not _temb_table_enabled():
             raise L.PPError(f"{type(sch).__name__} needs the time-embedding table: without it (PP_TEMB_TABLE=0) the step has "
@@ -223,8 +231,9 @@ class DenoiseLoop:
             self._do_cfg, self._g = bool(do_cfg), float(guidance_scale)
         else:
             ts, step = sch.timesteps_f32(), sch.step_counter()
-            mp = sch.m_prev(lat) if 1 <= sch.kind <= 3 else None  # scheduler state: DPM m_{i-1}; PNDM history + saved
-                                                                    # sample; UniPC (DDIM, LCM and the Euler classes keep none)
+            # scheduler state: DPM m_{i-1}; PNDM history + saved sample; UniPC; Heun / DPM2 / DPM2 ancestral / LMS: three
+            # derivative slots + the saved sample (DDIM, LCM and the Euler classes keep none)
+            mp = sch.m_prev(lat) if (1 <= sch.kind <= 3 or ksampler) else None
             kind, src = sch.kind, lat
         key = (tuple(latents_shape), bool(do_cfg), bool(guess_mode), self._noisy, float(guidance_scale), id(rt.step_plan),
                tuple(id(r.step_plan) for r in side_rts) if side_rts else None, kind, ts.data_ptr(), step.data_ptr(),
@@ -291,7 +300,12 @@ class DenoiseLoop:
                                 tuple(self._var_noise.shape) != tuple(latents_shape)):
                 self._var_noise = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
             ticket = self._ticket.data_ptr() if fold_advance else None
-            if sigma:            # Euler (s_up = 0 in every row: the noise pointer is never read) / Euler ancestral
+            if ksampler:         # one table row of Heun / DPM2 / DPM2 ancestral / LMS (noise: as for Euler below)
+                noise = self._var_noise if self._noisy else lat
+                prog.add("cfg_ksampler_step", lib.pp_cfg_ksampler_step, rt.outputs["eps"], int(do_cfg),
+                         float(guidance_scale), lat.data_ptr(), mp.data_ptr(), noise.data_ptr(), lat.numel(),
+                         sch.coef_table().data_ptr(), step.data_ptr(), ticket)
+            elif sigma:          # Euler (s_up = 0 in every row: the noise pointer is never read) / Euler ancestral
                 noise = self._var_noise if self._noisy else lat
                 prog.add("cfg_sigma_step", lib.pp_cfg_sigma_step, rt.outputs["eps"], int(do_cfg), float(guidance_scale),
                          lat.data_ptr(), noise.data_ptr(), lat.numel(), sch.coef_table().data_ptr(), step.data_ptr(), ticket)

@@ -144,7 +144,7 @@ class StableDiffusionInpaintPipeline(PipelineBase):
         cb = None
         if callback is not None:
             def cb(i, t, lat):
-                if i % callback_steps == 0:
+                if self._legacy_callback_row(i, len(timesteps), num_inference_steps) and i % callback_steps == 0:
                     callback(i, t, lat)
         out = self._loop.run(latents, len(timesteps), use_graph=self.use_graph, callback=cb, timesteps=timesteps)
         return self._finish(out.clone(), output_type, return_dict, prompt_embeds.dtype)

@@ -246,8 +246,9 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
                             ctx = pe.chunk(2)[1] if (guess_mode and do_cfg and pe.shape[0] == 2 * nb) else pe
                             side_rt.set_context(ctx.to(device), force=True)
                         state["negative_prompt_embeds"] = ret.pop("negative_prompt_embeds", state["negative_prompt_embeds"])
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, lat)
+                if callback is not None and self._legacy_callback_row(i, n, num_inference_steps) and \
+                        i % callback_steps == 0:
+                    callback(i // getattr(self.scheduler, "order", 1), t, lat)                   # :1462-1466
         out = self._loop.run(latents, n, use_graph=self.use_graph, callback=cb, timesteps=timesteps,
                              scale_schedule=scales)
         return self._finish(out.clone(), output_type, return_dict, prompt_embeds.dtype, generator)

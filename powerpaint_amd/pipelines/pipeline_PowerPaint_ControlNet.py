@@ -208,7 +208,7 @@ class StableDiffusionControlNetInpaintPipeline(StableDiffusionInpaintPipeline):
         cb = None
         if callback is not None:
             def cb(i, t, lat):
-                if i % callback_steps == 0:
+                if self._legacy_callback_row(i, n, num_inference_steps) and i % callback_steps == 0:
                     callback(i, t, lat)
         out = self._loop.run(latents, n, use_graph=self.use_graph, callback=cb, timesteps=timesteps,
                              scale_schedule=scales)

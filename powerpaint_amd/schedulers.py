@@ -11,6 +11,8 @@ that kernel, so a foreign loop calling `scheduler.step` still runs on the HIP pa
 
 `EulerDiscreteScheduler` / `EulerAncestralDiscreteScheduler` (and `use_karras_sigmas`) are the sigma-space family: latents
 x0 + sigma eps, `init_noise_sigma` > 1, a real `scale_model_input`, float timesteps; their step is `pp_cfg_sigma_step`.
+`HeunDiscreteScheduler`, `KDPM2DiscreteScheduler`, `KDPM2AncestralDiscreteScheduler` and `LMSDiscreteScheduler` are the
+members of that family that keep state between network evaluations; their step is `pp_cfg_ksampler_step`.
 """
 from types import SimpleNamespace
 
@@ -797,9 +799,9 @@ class _SigmaScheduler(_SchedulerBase):
         m = float(self.sigmas.max()) if self.timesteps is not None else float(self._sig_all.max())
         return m if self.config.timestep_spacing in ("linspace", "trailing") else (m ** 2 + 1) ** 0.5
 
-    def set_timesteps(self, num_inference_steps: int, device=None):
-        T, n = self.config.num_train_timesteps, num_inference_steps
-        self.num_inference_steps = n
+    def _base_grid(self, n):
+        """(timesteps [n], sigmas [n]) as numpy, before the 0 is appended: the grid every class of the family starts from."""
+        T = self.config.num_train_timesteps
         sp = self.config.timestep_spacing
         if sp == "linspace":
             ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
@@ -812,12 +814,21 @@ class _SigmaScheduler(_SchedulerBase):
             log_sig = np.log(self._sig_all)
             sig = karras_sigmas(sig[-1], sig[0], n)
             ts = np.array([sigma_to_t(v, log_sig) for v in sig])
+        return ts, sig
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        self.num_inference_steps = num_inference_steps
+        ts, sig = self._base_grid(num_inference_steps)
         self.sigmas = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
-        self._ts_host = torch.from_numpy(ts.astype(np.float32))
+        self._set_rows(ts)
         self.timesteps = self._ts_host.clone()
         self._begin = 0
         self._fill_table()
         self._upload(device)
+
+    def _set_rows(self, ts):
+        """`_ts_host`, one entry per table row, from the base grid's timesteps (the two-stage samplers interleave here)."""
+        self._ts_host = torch.from_numpy(ts.astype(np.float32))
 
     def _sigma_up(self, s_from, s_to):
         return torch.zeros(())
@@ -832,7 +843,12 @@ class _SigmaScheduler(_SchedulerBase):
             s_down = (s_to ** 2 - s_up ** 2) ** 0.5
             coef[i, 0], coef[i, 1], coef[i, 2] = s_from, s_down - s_from, s_up
         self._coef = coef
-        self._in_div = (self.sigmas[:-1] ** 2 + 1) ** 0.5
+        self._set_row_sigmas(self.sigmas[:-1])
+
+    def _set_row_sigmas(self, row_sigma):
+        """The noise level each row's evaluation happens at -> `in_div_table`, `scale_model_input`, `add_noise`."""
+        self._row_sigma = row_sigma.to(torch.float32).contiguous()
+        self._in_div = (self._row_sigma ** 2 + 1) ** 0.5
 
     def _upload(self, device):
         super()._upload(device)
@@ -859,12 +875,13 @@ class _SigmaScheduler(_SchedulerBase):
         return idx[0]
 
     def _renoise_rows(self) -> torch.Tensor:
-        """(1, sigma_{i+1}) after step i, (1, 0) after the last one: `add_noise(x0, noise, timesteps[i + 1])` in sigma
+        """(1, sigma of row i + 1) after row i, (1, 0) after the last one: `add_noise(x0, noise, timesteps[i + 1])` in sigma
         space, in the layout pp_latent_blend reads."""
-        return torch.stack([torch.ones(len(self._ts_host)), self.sigmas[1:]], 1).contiguous()
+        nxt = torch.cat([self._row_sigma[1:], torch.zeros(1)])
+        return torch.stack([torch.ones(len(self._ts_host)), nxt], 1).contiguous()
 
     def add_noise(self, original_samples, noise, timesteps):
-        sig = self.sigmas.to(device=original_samples.device, dtype=original_samples.dtype)
+        sig = self._row_sigma.to(device=original_samples.device, dtype=original_samples.dtype)
         s = sig[[self._peek_index(t) for t in timesteps.reshape(-1)]].flatten()
         while s.dim() < original_samples.dim():
             s = s.unsqueeze(-1)
@@ -935,6 +952,196 @@ class EulerAncestralDiscreteScheduler(_SigmaScheduler):
         return (s_to ** 2 * (s_from ** 2 - s_to ** 2) / s_from ** 2) ** 0.5
 
 
+class _KSampler(_SigmaScheduler):
+    """The sigma-space samplers that keep state between network evaluations (k-diffusion `sample_heun`, `sample_dpm_2`,
+    `sample_dpm_2_ancestral`, `sample_lms` at s_churn = 0, as diffusers 0.27 schedules them).  One table row per
+    evaluation, 16 floats laid out like the PLMS row:
+        (c_e, c_h1, c_h2, c_h3, s_up, sigma of the evaluation, slot1, slot2, slot3, push_slot | -1, use_saved, save, 0...)
+    evaluated in fp32 torch in the library's operation order; `pp_cfg_ksampler_step` computes
+        x' = (use_saved ? saved : x) + c_e e + c_h1 H[slot1] + c_h2 H[slot2] + c_h3 H[slot3] + s_up z
+    on the state [4][n] = three derivative slots and the saved sample.  State and table restart where the loop enters the
+    schedule (`set_begin_index`).  The two-stage classes have `order = 2`: `timesteps` interleaves both evaluations of a
+    step, 2N - 1 entries (the last step, to sigma = 0, is a single Euler row)."""
+    state_slots = 4
+
+    def _peek_index(self, timestep) -> int:
+        """Row of the NEXT `step` call that carries `timestep`: of a repeated timestep (Heun's pairs; a DPM2 ancestral
+        midpoint that lands on the next grid point) the occurrence after those `step` has consumed, counted from the row the
+        loop entered at -- at an even begin index the first call carries the SECOND occurrence of its timestep."""
+        t = float(timestep)
+        idx = [i for i in (self._ts_host == t).nonzero().flatten().tolist() if i >= self._begin]
+        if not idx:
+            raise ValueError(f"timestep {t} is not in the schedule from row {self._begin} on")
+        return idx[min(self._dup_calls.get(t, 0), len(idx) - 1)]
+
+    def _index_of(self, timestep) -> int:
+        i = self._peek_index(timestep)
+        self._dup_calls[float(timestep)] = self._dup_calls.get(float(timestep), 0) + 1
+        return i
+
+    def draws_noise_at(self, row: int) -> bool:
+        return self.step_noise   # DPM2 ancestral: the library's step draws on every call, both stages; the others never
+
+    @staticmethod
+    def _row(c_e, c_h=(0.0, 0.0, 0.0), s_up=0.0, sigma=0.0, slots=(0, 0, 0), push=-1, use_saved=False, save=False):
+        r = torch.zeros(16, dtype=torch.float32)
+        r[0], r[1], r[2], r[3], r[4], r[5] = c_e, c_h[0], c_h[1], c_h[2], s_up, sigma
+        r[6], r[7], r[8], r[9] = float(slots[0]), float(slots[1]), float(slots[2]), float(push)
+        r[10], r[11] = float(use_saved), float(save)
+        return r
+
+    def _two_stage_table(self, mid, down, up, heun=False):
+        """Rows A_k (at sigma_k: save, step to `mid[k]`) and B_k (at `mid[k]`, from the saved sample) for k < N - 1, then the
+        Euler row to 0.  Heun: B_k averages its derivative with A_k's (slot 0)."""
+        sg, n = self.sigmas, self.num_inference_steps
+        rows = []
+        for k in range(n - 1):
+            if heun:
+                dt = sg[k + 1] - sg[k]
+                rows.append(self._row(dt, sigma=sg[k], push=0, save=True))
+                rows.append(self._row(dt / 2, (dt / 2, 0.0, 0.0), sigma=sg[k + 1], use_saved=True))
+            else:
+                rows.append(self._row(mid[k] - sg[k], sigma=sg[k], save=True))
+                rows.append(self._row(down[k] - sg[k], s_up=up[k], sigma=mid[k], use_saved=True))
+        # (entered at a B row -- an odd begin index, which no pipeline produces -- that row would read an empty state)
+        rows.append(self._row(-sg[n - 1], sigma=sg[n - 1]))
+        self._coef = torch.stack(rows)
+        self._set_row_sigmas(self._coef[:, 5])
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, **kw):
+        """One table row in `pp_cfg_ksampler_step` (fp32 math).  Returns a NEW tensor in sample's dtype; the state between
+        the calls lives in the scheduler, zeroed by `set_timesteps` / `set_begin_index`.  DPM2 ancestral draws its noise
+        like the library's `randn_tensor(model_output.shape, generator=generator, ...)`: on every call, both stages."""
+        if not sample.is_cuda:
+            raise L.PPError("scheduler.step needs CUDA tensors: the step runs in the HIP kernel, no CPU fallback")
+        i = self._index_of(timestep)
+        x = sample.detach().to(torch.float32).contiguous().clone()
+        e = model_output.detach().to(torch.float32).contiguous()
+        step = torch.full((1,), i, dtype=torch.int32, device=x.device)
+        # (s_up = 0 in every row of the other three: never read, any valid address does)
+        z = variance_noise(model_output.shape, generator, x.device, model_output.dtype) if self.step_noise else x
+        L.check(L.lib().pp_cfg_ksampler_step(e.data_ptr(), 0, 0.0, x.data_ptr(), self.m_prev(x).data_ptr(), z.data_ptr(),
+                                              x.numel(), self._coef_dev.data_ptr(), step.data_ptr(), None,
+                                              torch.cuda.current_stream().cuda_stream), "pp_cfg_ksampler_step")
+        out = x.to(sample.dtype)
+        if not return_dict:
+            return (out,)
+        return SimpleNamespace(prev_sample=out, pred_original_sample=None)
+
+
+class HeunDiscreteScheduler(_KSampler):
+    """diffusers-0.27 `HeunDiscreteScheduler` ("Heun", with use_karras_sigmas "Heun Karras"; Karras et al. algorithm 1 at
+    s_churn = 0): x~ = x + (s' - s) e(x, s), then x' = x + (s' - s) (e(x, s) + e(x~, s')) / 2; the last step is Euler.
+    `timesteps` = [t_0, t_1, t_1, ..., t_{N-1}, t_{N-1}].  Nothing is drawn."""
+    kind = 7
+    order = 2
+
+    def _set_rows(self, ts):
+        t = torch.from_numpy(ts.astype(np.float32))
+        self._ts_host = torch.cat([t[:1], t[1:].repeat_interleave(2)])
+
+    def _fill_table(self):
+        self._two_stage_table(None, None, None, heun=True)
+
+
+class KDPM2DiscreteScheduler(_KSampler):
+    """diffusers-0.27 `KDPM2DiscreteScheduler` ("DPM2", "DPM2 Karras"; DPM-Solver-2 as k-diffusion's `sample_dpm_2`):
+    s_mid = exp((ln s + ln s') / 2), x~ = x + (s_mid - s) e(x, s), x' = x + (s' - s) e(x~, s_mid).  `timesteps` =
+    [t_0, tau_0, t_1, tau_1, ..., t_{N-1}] with tau_k = sigma_to_t(s_mid,k), fractional.  Karras timesteps are rounded, as
+    in the library's class.  Nothing is drawn."""
+    kind = 8
+    order = 2
+    blend_refused = "the library's add_noise at a midpoint timestep is not pinned"
+
+    def _base_grid(self, n):
+        ts, sig = super()._base_grid(n)
+        return (ts.round() if self.config.use_karras_sigmas else ts), sig
+
+    def _split(self):
+        """(mid, down, up) per step of the base grid, fp32 torch: plain DPM2 steps to sigma_{k+1} without noise."""
+        sg = self.sigmas
+        mid = sg.log().lerp(sg.roll(1).log(), 0.5).exp()[1:]      # mid[k]: between sigma_k and sigma_{k+1}
+        return mid, sg[1:], torch.zeros_like(sg[1:])
+
+    def _set_rows(self, ts):
+        mid = self._split()[0].numpy()
+        log_sig = np.log(self._sig_all)
+        tau = np.array([sigma_to_t(v, log_sig) for v in mid[:-1]]).reshape(-1)
+        t = torch.from_numpy(ts.astype(np.float32))
+        tau = torch.from_numpy(tau.astype(np.float32))
+        self._ts_host = torch.cat([t[:1], torch.stack((tau, t[1:]), dim=-1).flatten()])
+
+    def _fill_table(self):
+        self._two_stage_table(*self._split())
+
+
+class KDPM2AncestralDiscreteScheduler(KDPM2DiscreteScheduler):
+    """diffusers-0.27 `KDPM2AncestralDiscreteScheduler` ("DPM2 a", "DPM2 a Karras"; `sample_dpm_2_ancestral`): DPM2 towards
+    s_down of the ancestral split (s_up as Euler ancestral's), s_mid between s and s_down, then + s_up z.  The library's
+    step draws z on every call and uses it on the second stage only; the loop draws per row the same way, so the caller's
+    generator ends where the library leaves it.  The last step has s_down = 0: Euler, no noise added."""
+    kind = 9
+
+    @property
+    def step_noise(self) -> bool:
+        return True
+
+    _sigma_up = EulerAncestralDiscreteScheduler._sigma_up
+
+    def _split(self):
+        sg = self.sigmas
+        nxt = sg.roll(-1)
+        nxt[-1] = 0.0
+        up = self._sigma_up(sg, nxt)
+        down = (nxt ** 2 - up ** 2) ** 0.5
+        mid = sg.log().lerp(down.log(), 0.5).exp()
+        mid[-2:] = 0.0
+        return mid[:-1], down[:-1], up[:-1]
+
+
+class LMSDiscreteScheduler(_KSampler):
+    """diffusers-0.27 `LMSDiscreteScheduler` ("LMS", "LMS Karras"; k-diffusion `sample_lms`), order 4: x' = x + sum_j C_j e_{i-j}
+    with C_j the integral over [sigma_i, sigma_{i+1}] of the Lagrange basis polynomial through sigma_i, sigma_{i-1}, ... of
+    e_{i-j}'s node.  The library integrates numerically (`scipy.integrate.quad`, epsrel 1e-4); here the polynomial is
+    integrated exactly in float64.  The order follows the ABSOLUTE step index, min(i + 1, 4), while the derivative list
+    starts empty where the loop enters: entered late, the first rows use the leading coefficients of the higher-order basis
+    (the library's `zip` truncation).  History = a ring over the 3 slots, each row pushing e into the slot of the oldest
+    entry it read.  Nothing is drawn."""
+    kind = 10
+    order = 1
+    lms_order = 4
+
+    def lms_coefficient(self, order, i, j):
+        P = np.polynomial.Polynomial
+        sg = self.sigmas.numpy().astype(np.float64)
+        prod = P([1.0])
+        for k in range(order):
+            if k != j:
+                prod = prod * P([-sg[i - k], 1.0]) / (sg[i - j] - sg[i - k])
+        integ = prod.integ()
+        return float(integ(sg[i + 1]) - integ(sg[i]))
+
+    def _fill_table(self):
+        n, b0 = self.num_inference_steps, self._begin
+        rows = [self._row(0.0) for _ in range(n)]
+        for i in range(b0, n):
+            r = i - b0                                            # evaluations since the loop entered
+            order = min(i + 1, self.lms_order)
+            have = min(r + 1, order)                              # derivatives in the list, this row's included
+            c = [self.lms_coefficient(order, i, j) if j < have else 0.0 for j in range(4)]
+            rows[i] = self._row(c[0], c[1:], sigma=self.sigmas[i], slots=[(r - j) % 3 for j in (1, 2, 3)], push=r % 3)
+        self._coef = torch.stack(rows)
+        self._set_row_sigmas(self.sigmas[:-1])
+
+    def step(self, model_output, timestep, sample, order: int = 4, generator=None, return_dict: bool = True, **kw):
+        if int(order) != self.lms_order:
+            raise L.PPError(f"LMSDiscreteScheduler: step(order={order!r}) is not implemented on the HIP path (4 only)")
+        return super().step(model_output, timestep, sample, generator=generator, return_dict=return_dict)
+
+
 SCHEDULERS = {"DDIMScheduler": DDIMScheduler, "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
               "PNDMScheduler": PNDMScheduler, "UniPCMultistepScheduler": UniPCMultistepScheduler,
-              "LCMScheduler": LCMScheduler, "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler}
+              "LCMScheduler": LCMScheduler, "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler,
+              "HeunDiscreteScheduler": HeunDiscreteScheduler, "KDPM2DiscreteScheduler": KDPM2DiscreteScheduler,
+              "KDPM2AncestralDiscreteScheduler": KDPM2AncestralDiscreteScheduler,
+              "LMSDiscreteScheduler": LMSDiscreteScheduler}
