@@ -29,7 +29,7 @@ extern "C" {
 #define PP_ERR_LAUNCH (-3)       /* hipLaunchKernel / hipFuncSetAttribute failed                  */
 #define PP_ERR_WORKSPACE (-4)    /* workspace pointer null or too small                           */
 
-#define PP_ABI_VERSION 27
+#define PP_ABI_VERSION 28
 /* 16-bit storage format of activations and matrix weights ("dtype" arguments; the same codes pp_nchw_to_nhwc uses for
  * its source): bf16 or fp16 -- the reference's default is fp16 (/root/reference/app.py:548,559).  MFMA accumulation,
  * norm statistics, softmax, biases and latents are fp32 with either. */
@@ -226,6 +226,19 @@ typedef struct PPGemmArgs {
    * (/root/reference/powerpaint/models/unet_2d_blocks.py:1457-1500, 850-899, 2696-2770). */
   uint64_t* tile_ctr;
   uint32_t* combine_fault;
+  /* (ABI v28) PP_X_CONV3X3: 1 = the SUB-PIXEL form of Upsample2D's `nearest 2x -> conv3x3` (ctor site
+   * /root/reference/powerpaint/models/unet_2d_blocks.py:2542).  Output pixel (2i + a, 2j + b) of that conv reads only the 2x2
+   * source pixels (i + a - 1 + dy, j + b - 1 + dx), dy, dx in {0, 1}: the nine taps collapse onto four, with the weights of the
+   * taps that share a source pixel summed (pp_upconv_fold).  The request describes the SOURCE geometry -- hin = hout, win =
+   * wout, stride 1, up = 0, M = batch * hin * win, rows_per_batch = hin * win -- with `w` = the folded buffer of
+   * pp_upconv_fold, [4 parities 2a + b][N][2][2][c1], and K = 4 * c1; `out`, res1 and res2 are [batch][2 hout][2 wout][N]
+   * tensors (source row m of parity (a, b) is their row of pixel (2i + a, 2j + b)); gn_acc subscriptions describe that output
+   * tensor (its batch items are the source's).  4/9 of the MACs of the `up` = 1 request; the folded weights are rounded to
+   * the 16-bit format once more, so the result differs from the `up` = 1 request's by up to one rounding of an activation
+   *  -- a request of its own, never a route the library takes for `up` = 1.  Runs on the halo-tile loop
+   * only, one pass (splitk <= 1), one source tensor, no 1x1 tail, no gn_in_* / gn_next_* / out_dup_rows / res1_wrap_rows:
+   * PP_ERR_UNSUPPORTED otherwise (pp_upconv_subpix_supported() tells).  0: every request of ABI v27 as before. */
+  int32_t subpix;
 } PPGemmArgs;
 #define PP_GN_SUM_SCALE 16777216.0f /* 2^24 */
 #define PP_GN_SQ_SCALE 1048576.0f   /* 2^20 */
@@ -256,6 +269,17 @@ int pp_conv_gn_supported(const PPGemmArgs* args);
  * wins at every level (step -2.0 % same-box, profiles/r06_conv_raw.txt): this returns 0 for every shape of the SD-1.5 plans;
  * the fused launch remains an operator for a caller that sets gn_in_* . */
 int pp_conv_gn_preferred(const PPGemmArgs* args);
+/* (ABI v28) The sub-pixel form of an upsampling conv (PPGemmArgs.subpix), asked by SOURCE shape: 0 = pp_gemm_bf16 answers
+ * such a request PP_ERR_UNSUPPORTED (source rows narrower than 8 pixels or not a multiple of 8, channels off the 64 grid,
+ * no tile of whole source rows); 1 = it runs; 2 = it runs and is where the plans use it -- source images at least 16 wide,
+ * the widths from which plain convs run on the halo-tile loop at all (below, the 9-tap request stays on the tap-major
+ * weight stream at 16/9 fewer weight bytes). */
+int pp_upconv_subpix_supported(int batch, int h, int w, int cin, int cout, int dtype);
+/* (ABI v28) The folded weights of the sub-pixel form: w = the packed conv weight [cout][3][3][cin] (16-bit `dtype`) ->
+ * out [4][cout][2][2][cin], out[2a + b][n][dy][dx][c] = sum over ky in R[a][dy], kx in R[b][dx] of w[n][ky][kx][c] with
+ * R[0] = ({0}, {1, 2}), R[1] = ({0, 1}, {2}); summed in fp32 in the order ky outer, kx inner, rounded once (to nearest even).
+ * cin % 8 == 0.  A cache derived from the weights: the plans run it outside the step, again whenever the weights change. */
+int pp_upconv_fold(const void* w, int cout, int cin, int dtype, void* out, void* stream);
 /* (ABI v17) 1 if this launch, as pp_gemm_bf16 would configure it, ends in the split-K combine that can apply the consumer
  * GroupNorm of subscription `sub` (PPGemmArgs.gn_next_*), else 0. */
 int pp_gemm_gn_next_ok(const PPGemmArgs* args, int sub);

@@ -64,13 +64,24 @@ PP_DEVINL void cg_static_for(F&& f) { cg_static_for_impl(std::make_integer_seque
 // HPW: halo strips per wave = ceil((BM + 2 W) / 64): a wave DMAs and normalises strips wave + 8 j, j < HPW, of the next chunk.
 // NMODE: where the normalisation of the next halo tile runs -- 1 inside the MFMA burst, 0 in the read phase; lab timing
 // probes: 2 = no normalisation at all (the loop skeleton on raw data), 3 = read phase and no s_setprio around the burst.
+// NMODE 4 = the raw loop in its SUB-PIXEL form (PPGemmArgs.subpix: Upsample2D's nearest 2x -> conv3x3 as four 2x2 convs over
+// the source image, one per output parity (a, b), on weights folded by pp_upconv_fold).  A workgroup is (parity, source tile,
+// column tile); per 64-channel chunk it walks the FOUR taps (a + dy, b + dx) of the 3x3 window of the source tile's halo
+// tile -- the same fragment offsets and kx edge masks as the nine-tap walk, chosen from the workgroup-uniform parity -- and
+// its epilogue scatters tile row (image, i, j) to output pixel (2i + a, 2j + b).  The ring: 4 K steps per chunk do not
+// divide by the 3 weight stages, so the stage of a K step is a RUNTIME scalar that advances by one per step (it feeds M0 of
+// the DMAs and the base of the fragment reads: two SALU instructions per step) instead of a three-chunk static body with a
+// tail; the next chunk's halo strips go two per tap over taps 0 .. 2 and the counted wait of tap 3 leaves only that tap's
+// weight pieces in flight, so every strip has landed when the next chunk's first barrier opens.
 template <int BM, int HPW, bool PP, int NMODE, int EDT>
 __global__ void __launch_bounds__(CG_T, 2) pp_conv_gn_kernel(const PPGemmArgs a, const CGDerived d) {
   using E = E16<EDT>;
   typedef typename E::v8 v8_t;
   constexpr int T = CG_T, WN = 2, MI = BM / 64, NI = CG_NI, BN = CG_BN;
   constexpr int CG_HPW = HPW;
-  constexpr bool NORM = NMODE != 2;
+  constexpr bool SUBPIX = NMODE == 4;
+  static_assert(!SUBPIX || PP, "the sub-pixel form has the ping-pong loop only");
+  constexpr bool NORM = NMODE != 2 && !SUBPIX;
   constexpr bool NREAD = NMODE == 0 || NMODE == 3;      // normalisation in the read phase
   static_assert(HPW >= 2 && HPW <= CG_HPW_MAX, "halo strips per wave");
   constexpr int XP2 = BM / 64;                    // phase-2 (tail) X-tile pieces per wave and K step
@@ -95,6 +106,10 @@ __global__ void __launch_bounds__(CG_T, 2) pp_conv_gn_kernel(const PPGemmArgs a,
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
     lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
+  // (sub-pixel form) the four parities of a (source tile, column tile) are neighbours in the linear id: they read the same
+  // halo tile, and with a grid of a multiple of 32 workgroups they share an XCD's L2
+  const int par = SUBPIX ? (lid & 3) : 0, pa = par >> 1, pb = par & 1;
+  if constexpr (SUBPIX) lid >>= 2;
   int tile_m, tile_n;
   if (d.n_major) {
     tile_n = lid / d.tiles_m;
@@ -117,6 +132,8 @@ __global__ void __launch_bounds__(CG_T, 2) pp_conv_gn_kernel(const PPGemmArgs a,
   const int y0 = (m_blk - bimg * HW) / Wd;            // its first image row (BM % W == 0)
   const int ctot = a.c1 + a.c2;
   const uint32_t wbytes = (uint32_t)a.N * (uint32_t)a.K * 2u;
+  // (sub-pixel form) one [N][K = 4 C] matrix per parity
+  const void* const wmat = SUBPIX ? (const void*)((const char*)a.w + (size_t)par * wbytes) : a.w;
 
   // lane -> (row of an 8-row strip, the k-slot it FETCHES so that its lane-linear LDS slot is swizzled by the row)
   const int lrow = lane >> 3;
@@ -284,7 +301,7 @@ __global__ void __launch_bounds__(CG_T, 2) pp_conv_gn_kernel(const PPGemmArgs a,
 
     // ---- prologue: weight tiles of K steps 0 and 1, the first halo tile and its table; the groups' (mean, rstd)
     {
-      const __amdgpu_buffer_rsrc_t rsw = make_rsrc(a.w, wbytes);
+      const __amdgpu_buffer_rsrc_t rsw = make_rsrc(wmat, wbytes);
 #pragma unroll
       for (int i = 0; i < CG_WP; ++i) issue_w_piece(rsw, 0, i, (0 * ctot + ch_b * 64) * 2);
 #pragma unroll
@@ -315,166 +332,238 @@ __global__ void __launch_bounds__(CG_T, 2) pp_conv_gn_kernel(const PPGemmArgs a,
     if (PP && grp == 1) asm volatile("s_barrier" ::: "memory");      // group 1 runs one phase behind group 0
 
     int hb = 0;
+    if constexpr (SUBPIX) {
+      int st = 0;                                     // weight stage of the K step being read (K step mod 3)
+      const int tap00 = pa * Wd + pb - 1;             // halo pixel of tap (dy, dx) = tile row + tap00 + dy W + dx
+      // kx = pb + dx: the kx = 0 tap (pb = 0, dx = 0) sends the first pixel of an image row to the zero block, the kx = 2 tap
+      // (pb = 1, dx = 1) the last one
+      const unsigned em0 = pb == 0 ? (edge & 0xffu) : 0u, em1 = pb == 1 ? (edge >> 8) : 0u;
 #pragma unroll 1
-    for (int c = ch_b; c < ch_e; ++c) {
-      const bool nxt = c + 1 < ch_e;
-      halo_source(c + 1, nxt);
-      const __amdgpu_buffer_rsrc_t rsw_same = make_rsrc(a.w, wbytes);
-      const __amdgpu_buffer_rsrc_t rsw_next = make_rsrc(a.w, nxt ? wbytes : 0u);
-      const int hoff = hb * CG_HALO;
-      const int hbn = hb ^ 1;
-      int Wl = Wd;                                  // (opaque per iteration: keeps the nine taps' fragment addresses -- 2 x 9
-      asm volatile("" : "+s"(Wl));                  //  registers, hoisted out of the chunk loop otherwise -- inside it)
+      for (int c = ch_b; c < ch_e; ++c) {
+        const bool nxt = c + 1 < ch_e;
+        halo_source(c + 1, nxt);
+        const __amdgpu_buffer_rsrc_t rsw_same = make_rsrc(wmat, wbytes);
+        const __amdgpu_buffer_rsrc_t rsw_next = make_rsrc(wmat, nxt ? wbytes : 0u);
+        const int hoff = hb * CG_HALO;
+        const int hbn = hb ^ 1;
+        int Wl = Wd;
+        asm volatile("" : "+s"(Wl));
 
-      cg_static_for<9>([&](auto TT) __attribute__((always_inline)) {
-        constexpr int t = decltype(TT)::value;
-        constexpr int st_r = t % 3, st_w = (t + 2) % 3;             // (9 % 3 == 0: the stage of tap t is t % 3 in every chunk)
-        // extra DMA pieces of a tap, after its three weight pieces: the next chunk's halo strips two per tap over taps
-        // 0 .. 2 (strip j is needed from tap 3 + j on) and, in tap 0, the chunk's (gamma, beta) table
-        constexpr auto NXT = [](int tt) constexpr {
-          const int nh = tt > 2 ? 0 : (2 * tt + 2 <= CG_HPW ? 2 : 2 * tt + 1 <= CG_HPW ? 1 : 0);   // strips 2 tt, 2 tt + 1
-          return nh + (tt == 0 ? 1 : 0);
-        };
-        constexpr int NX = NXT(t);
-        // weight tile of K step + 2
-        const __amdgpu_buffer_rsrc_t rsw = t + 2 <= 8 ? rsw_same : rsw_next;
-        const int sow = t + 2 <= 8 ? ((t + 2) * ctot + c * 64) * 2 : ((t + 2 - 9) * ctot + (c + 1) * 64) * 2;
+        cg_static_for<4>([&](auto TT) __attribute__((always_inline)) {
+          constexpr int t = decltype(TT)::value;
+          // the next chunk's halo strips: two per tap over taps 0 .. 2 (strips 2 tt, 2 tt + 1), none in tap 3
+          constexpr auto NXT = [](int tt) constexpr { return tt > 2 ? 0 : (2 * tt + 2 <= CG_HPW ? 2 : 2 * tt + 1 <= CG_HPW ? 1 : 0); };
+          constexpr int NX = NXT(t);
+          const int st_w = st == 0 ? 2 : st - 1;      // stage of K step + 2
+          const __amdgpu_buffer_rsrc_t rsw = t + 2 <= 3 ? rsw_same : rsw_next;
+          const int sow = t + 2 <= 3 ? ((t + 2) * ctot + c * 64) * 2 : ((t + 2 - 4) * ctot + (c + 1) * 64) * 2;
 
-        if constexpr (PP) {
           asm volatile("s_barrier" ::: "memory");   // X: everyone's weight tile of this step is in LDS; the partner left its read phase
-        } else {
-          // this wave's weight pieces of this K step (issued two taps ago) have landed; younger pieces may be in flight
-          constexpr int V = NXT((t + 7) % 9) + CG_WP + NXT((t + 8) % 9);
-          asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(V) : "memory");
-        }
-        // ---- the next chunk's halo tile.  Strip j of this wave (DMA'd in tap j / 2) has landed when tap 3 + j begins: the
-        //      counted waits of taps 2 .. 4 leave only younger pieces in flight.  Its normalisation -- ~70 VALU instructions --
-        //      rides INSIDE this wave's MFMA burst (NMODE 1: two per MFMA, in the issue slots the 16-cycle matrix
-        //      instruction leaves free) or sits in the read phase (NMODE 0, where the partner wave's s_setprio 1 starves
-        //      its transcendentals: MI355X_MICROARCH.md "Two waves per SIMD", item 2).
-        constexpr bool NT = NORM && t >= 3 && t - 3 < CG_HPW;        // a tap that carries one strip
-        char* const np = smem + hbn * CG_HALO + (wave + 8 * (NT ? t - 3 : 0)) * 1024 + lane * 16;
-        u32x4_t nv = {0u, 0u, 0u, 0u};
-        f32x4_t ss0 = {0.f, 0.f, 0.f, 0.f}, ss1 = {0.f, 0.f, 0.f, 0.f};     // first half of this lane's (scale, shift) row
-        if constexpr (NT) {
-          // (unconditional: behind the last chunk this works on the zeros of the dead DMAs in the unused buffer -- a branch
-          //  around the MFMA burst would put the 80 accumulator registers through a phi and double them)
-          if constexpr (t == 3) compute_scsh(c + 1, hbn);
-          if constexpr (NREAD) norm_piece(hbn, t - 3);
-          else {
-            nv = *reinterpret_cast<const u32x4_t*>(np);
-            ss0 = *reinterpret_cast<const f32x4_t*>(smem + CG_T_SCSH + kslot * 64);
-            ss1 = *reinterpret_cast<const f32x4_t*>(smem + CG_T_SCSH + kslot * 64 + 16);
-          }
-          if constexpr (NREAD) __builtin_amdgcn_sched_barrier(0);
-        }
-        // ---- read phase: fragment reads of this K step, the DMA pieces spread between them
-        const char* ws = smem + CG_WOFF + st_r * CG_WST;
-        const int hp0 = rt0 + (t / 3) * Wl + (t % 3) - 1;
-        const int xbase = hoff + (hp0 << 7) + ((g ^ (hp0 & 7)) << 4);
-        v8_t wf[2][NI], xf[2][MI];
-        constexpr int NR = NI + MI, NPC = CG_WP + NX;
+          const char* ws = smem + CG_WOFF + st * CG_WST;
+          const int hp0 = rt0 + tap00 + (t / 2) * Wl + (t % 2);
+          const int xbase = hoff + (hp0 << 7) + ((g ^ (hp0 & 7)) << 4);
+          const unsigned em = t % 2 == 0 ? em0 : em1;
+          v8_t wf[2][NI], xf[2][MI];
+          constexpr int NR = NI + MI, NPC = CG_WP + NX;
 #pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          if (r < NI) {
-            const int ni = r < NI ? r : 0;
-            const char* pw = ws + (wrow0 + ni * 16) * 128;
-            wf[0][ni] = *reinterpret_cast<const v8_t*>(pw + ((g ^ fsw) << 4));
-            wf[1][ni] = *reinterpret_cast<const v8_t*>(pw + (((4 + g) ^ fsw) << 4));
-          } else {
-            const int mi = r >= NI ? r - NI : 0;
-            // k-slot g of halo pixel hp0 + 16 mi (same swizzle for every mi: 16 = 0 mod 8; ks = 1: slot g + 4 = ^ 64 B)
-            int o0 = xbase + mi * 2048;
-            if constexpr (t % 3 == 0) o0 = (edge >> mi) & 1u ? CG_T_ZERO : o0;
-            if constexpr (t % 3 == 2) o0 = (edge >> (8 + mi)) & 1u ? CG_T_ZERO : o0;
-            xf[0][mi] = *reinterpret_cast<const v8_t*>(smem + o0);
-            xf[1][mi] = *reinterpret_cast<const v8_t*>(smem + (o0 ^ 64));
-          }
-          // piece k goes after read number ceil((k + 1) * NR / (NPC + 1))
-#pragma unroll
-          for (int k = 0; k < NPC; ++k)
-            if (((k + 1) * NR + NPC) / (NPC + 1) == r + 1) {
-              __builtin_amdgcn_sched_barrier(0);
-              if (k < CG_WP) issue_w_piece(rsw, st_w, k < CG_WP ? k : 0, sow);
-              else if (t == 0 && k == NPC - 1) issue_gb(c + 1, hbn, nxt);
-              else issue_halo_piece(hbn, 2 * t + (k - CG_WP < 2 ? k - CG_WP : 0));
-              __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if constexpr (PP) {
-          // Y: this wave's weight pieces of the NEXT K step (issued in the previous tap) have landed, its fragments of this
-          // one are in registers
-          constexpr int V = NXT((t + 8) % 9) + CG_WP + NX;
-          asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(V) : "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (NMODE != 3) __builtin_amdgcn_s_setprio(1);
-        if constexpr (NT && NMODE == 1) {
-          // One matrix instruction per slot, and behind each a fixed slice of the strip's normalisation, pinned by
-          // sched_barrier(0) -- left to the scheduler (sched_group_barrier) the 64 VALU instructions ended up BEHIND the
-          // burst as one dependent chain of LDS round trips and transcendental latencies (~600 cycles per strip, nothing
-          // hidden; profiles/r04_conv_gn_variants.txt).  The program works on two channel pairs at a time (four
-          // independent chains, a dependent instruction at least two slots = 32 cycles behind its producer, 12 live
-          // registers besides the strip itself), one transcendental per slot at most:
-          //   U unpack, F x * scale + shift, M * -log2(e), X exp2 (one per slot), A 1 +, R rcp (one per slot), S *, C pack
-          // for pairs (0, 1), then (2, 3) with the second half of the (scale, shift) row loaded meanwhile; LDS store last.
-          constexpr int NM = 2 * MI * NI, NG = 41;
-          const uint32_t vmask = ~(uint32_t)(hpix[NT ? t - 3 : 0] >> 31);   // all ones inside the image, else 0
-          const char* const sp = smem + CG_T_SCSH + kslot * 64;
-          float xa[4], ea[4];
-          u32x4_t no;
-          auto micro = [&](auto GG) __attribute__((always_inline)) {
-            constexpr int g = decltype(GG)::value;
-            if constexpr (g == 40) {
-              *reinterpret_cast<u32x4_t*>(np) = no;
+          for (int r = 0; r < NR; ++r) {
+            if (r < NI) {
+              const int ni = r < NI ? r : 0;
+              const char* pw = ws + (wrow0 + ni * 16) * 128;
+              wf[0][ni] = *reinterpret_cast<const v8_t*>(pw + ((g ^ fsw) << 4));
+              wf[1][ni] = *reinterpret_cast<const v8_t*>(pw + (((4 + g) ^ fsw) << 4));
             } else {
-              constexpr int h = g / 20, gg = g % 20, p0 = 2 * h, p1 = 2 * h + 1;
-              if constexpr (gg == 0) { xa[0] = E::lo(nv[p0]); xa[1] = E::hi(nv[p0]); }
-              if constexpr (gg == 1) { xa[2] = E::lo(nv[p1]); xa[3] = E::hi(nv[p1]); }
-              if constexpr (gg == 2) { xa[0] = __builtin_fmaf(xa[0], ss0[0], ss0[1]); xa[1] = __builtin_fmaf(xa[1], ss0[2], ss0[3]); }
-              if constexpr (gg == 3) { xa[2] = __builtin_fmaf(xa[2], ss1[0], ss1[1]); xa[3] = __builtin_fmaf(xa[3], ss1[2], ss1[3]); }
-              if constexpr (gg == 4) { ea[0] = xa[0] * -1.44269504088896340736f; ea[1] = xa[1] * -1.44269504088896340736f; }
-              if constexpr (gg == 5) { ea[2] = xa[2] * -1.44269504088896340736f; ea[3] = xa[3] * -1.44269504088896340736f; }
-              if constexpr (gg == 6) {
-                ea[0] = __builtin_amdgcn_exp2f(ea[0]);
-                if constexpr (h == 0) ss0 = *reinterpret_cast<const f32x4_t*>(sp + 32);
-              }
-              if constexpr (gg == 7) {
-                ea[1] = __builtin_amdgcn_exp2f(ea[1]);
-                if constexpr (h == 0) ss1 = *reinterpret_cast<const f32x4_t*>(sp + 48);
-              }
-              if constexpr (gg == 8) ea[2] = __builtin_amdgcn_exp2f(ea[2]);
-              if constexpr (gg == 9) ea[3] = __builtin_amdgcn_exp2f(ea[3]);
-              if constexpr (gg == 10) { ea[0] += 1.0f; ea[1] += 1.0f; }
-              if constexpr (gg == 11) { ea[2] += 1.0f; ea[3] += 1.0f; }
-              if constexpr (gg == 12) ea[0] = __builtin_amdgcn_rcpf(ea[0]);
-              if constexpr (gg == 13) ea[1] = __builtin_amdgcn_rcpf(ea[1]);
-              if constexpr (gg == 14) ea[2] = __builtin_amdgcn_rcpf(ea[2]);
-              if constexpr (gg == 15) ea[3] = __builtin_amdgcn_rcpf(ea[3]);
-              if constexpr (gg == 16) { xa[0] *= ea[0]; xa[1] *= ea[1]; }
-              if constexpr (gg == 17) { xa[2] *= ea[2]; xa[3] *= ea[3]; }
-              if constexpr (gg == 18) no[p0] = E::pack2(xa[0], xa[1]) & vmask;   // (a mask, not a select: hipcc turns the
-              if constexpr (gg == 19) no[p1] = E::pack2(xa[2], xa[3]) & vmask;   //  select into a branch around the math)
+              const int mi = r >= NI ? r - NI : 0;
+              int o0 = xbase + mi * 2048;
+              o0 = (em >> mi) & 1u ? CG_T_ZERO : o0;
+              xf[0][mi] = *reinterpret_cast<const v8_t*>(smem + o0);
+              xf[1][mi] = *reinterpret_cast<const v8_t*>(smem + (o0 ^ 64));
             }
-          };
-          cg_static_for<NM>([&](auto II) __attribute__((always_inline)) {
-            constexpr int i = decltype(II)::value;
-            constexpr int ks = i / (NI * MI), ni = (i / MI) % NI, mi = i % MI;
-            acc[ni][mi] = E::mfma16(wf[ks][ni], xf[ks][mi], acc[ni][mi]);
-            __builtin_amdgcn_sched_barrier(0);
-            constexpr int G0 = i * NG / NM, G1 = (i + 1) * NG / NM;
-            cg_static_for<G1 - G0>([&](auto JJ) __attribute__((always_inline)) {
-              micro(std::integral_constant<int, G0 + decltype(JJ)::value>{});
-            });
-            __builtin_amdgcn_sched_barrier(0);
-          });
-        } else {
+            // piece k goes after read number ceil((k + 1) * NR / (NPC + 1))
+#pragma unroll
+            for (int k = 0; k < NPC; ++k)
+              if (((k + 1) * NR + NPC) / (NPC + 1) == r + 1) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (k < CG_WP) issue_w_piece(rsw, st_w, k < CG_WP ? k : 0, sow);
+                else issue_halo_piece(hbn, 2 * t + (k - CG_WP < 2 ? k - CG_WP : 0));
+                __builtin_amdgcn_sched_barrier(0);
+              }
+          }
+          // Y: this wave's weight pieces of the NEXT K step (issued in the previous tap) have landed, its fragments of this
+          // one are in registers.  Tap 3 also waits for the halo strips of tap 2: the next chunk reads them behind its X
+          constexpr int V = (t == 3 ? 0 : NXT((t + 3) % 4)) + CG_WP + NX;
+          asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(V) : "memory");
+          __builtin_amdgcn_sched_barrier(0);
+          __builtin_amdgcn_s_setprio(1);
           mfma_all(wf, xf);
-        }
-        if constexpr (NMODE != 3) __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-      });
-      hb ^= 1;
+          __builtin_amdgcn_s_setprio(0);
+          __builtin_amdgcn_sched_barrier(0);
+          st = st == 2 ? 0 : st + 1;
+        });
+        hb ^= 1;
+      }
+    } else {
+  #pragma unroll 1
+      for (int c = ch_b; c < ch_e; ++c) {
+        const bool nxt = c + 1 < ch_e;
+        halo_source(c + 1, nxt);
+        const __amdgpu_buffer_rsrc_t rsw_same = make_rsrc(wmat, wbytes);
+        const __amdgpu_buffer_rsrc_t rsw_next = make_rsrc(wmat, nxt ? wbytes : 0u);
+        const int hoff = hb * CG_HALO;
+        const int hbn = hb ^ 1;
+        int Wl = Wd;                                  // (opaque per iteration: keeps the nine taps' fragment addresses -- 2 x 9
+        asm volatile("" : "+s"(Wl));                  //  registers, hoisted out of the chunk loop otherwise -- inside it)
+
+        cg_static_for<9>([&](auto TT) __attribute__((always_inline)) {
+          constexpr int t = decltype(TT)::value;
+          constexpr int st_r = t % 3, st_w = (t + 2) % 3;             // (9 % 3 == 0: the stage of tap t is t % 3 in every chunk)
+          // extra DMA pieces of a tap, after its three weight pieces: the next chunk's halo strips two per tap over taps
+          // 0 .. 2 (strip j is needed from tap 3 + j on) and, in tap 0, the chunk's (gamma, beta) table
+          constexpr auto NXT = [](int tt) constexpr {
+            const int nh = tt > 2 ? 0 : (2 * tt + 2 <= CG_HPW ? 2 : 2 * tt + 1 <= CG_HPW ? 1 : 0);   // strips 2 tt, 2 tt + 1
+            return nh + (tt == 0 ? 1 : 0);
+          };
+          constexpr int NX = NXT(t);
+          // weight tile of K step + 2
+          const __amdgpu_buffer_rsrc_t rsw = t + 2 <= 8 ? rsw_same : rsw_next;
+          const int sow = t + 2 <= 8 ? ((t + 2) * ctot + c * 64) * 2 : ((t + 2 - 9) * ctot + (c + 1) * 64) * 2;
+
+          if constexpr (PP) {
+            asm volatile("s_barrier" ::: "memory");   // X: everyone's weight tile of this step is in LDS; the partner left its read phase
+          } else {
+            // this wave's weight pieces of this K step (issued two taps ago) have landed; younger pieces may be in flight
+            constexpr int V = NXT((t + 7) % 9) + CG_WP + NXT((t + 8) % 9);
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(V) : "memory");
+          }
+          // ---- the next chunk's halo tile.  Strip j of this wave (DMA'd in tap j / 2) has landed when tap 3 + j begins: the
+          //      counted waits of taps 2 .. 4 leave only younger pieces in flight.  Its normalisation -- ~70 VALU instructions --
+          //      rides INSIDE this wave's MFMA burst (NMODE 1: two per MFMA, in the issue slots the 16-cycle matrix
+          //      instruction leaves free) or sits in the read phase (NMODE 0, where the partner wave's s_setprio 1 starves
+          //      its transcendentals: MI355X_MICROARCH.md "Two waves per SIMD", item 2).
+          constexpr bool NT = NORM && t >= 3 && t - 3 < CG_HPW;        // a tap that carries one strip
+          char* const np = smem + hbn * CG_HALO + (wave + 8 * (NT ? t - 3 : 0)) * 1024 + lane * 16;
+          u32x4_t nv = {0u, 0u, 0u, 0u};
+          f32x4_t ss0 = {0.f, 0.f, 0.f, 0.f}, ss1 = {0.f, 0.f, 0.f, 0.f};     // first half of this lane's (scale, shift) row
+          if constexpr (NT) {
+            // (unconditional: behind the last chunk this works on the zeros of the dead DMAs in the unused buffer -- a branch
+            //  around the MFMA burst would put the 80 accumulator registers through a phi and double them)
+            if constexpr (t == 3) compute_scsh(c + 1, hbn);
+            if constexpr (NREAD) norm_piece(hbn, t - 3);
+            else {
+              nv = *reinterpret_cast<const u32x4_t*>(np);
+              ss0 = *reinterpret_cast<const f32x4_t*>(smem + CG_T_SCSH + kslot * 64);
+              ss1 = *reinterpret_cast<const f32x4_t*>(smem + CG_T_SCSH + kslot * 64 + 16);
+            }
+            if constexpr (NREAD) __builtin_amdgcn_sched_barrier(0);
+          }
+          // ---- read phase: fragment reads of this K step, the DMA pieces spread between them
+          const char* ws = smem + CG_WOFF + st_r * CG_WST;
+          const int hp0 = rt0 + (t / 3) * Wl + (t % 3) - 1;
+          const int xbase = hoff + (hp0 << 7) + ((g ^ (hp0 & 7)) << 4);
+          v8_t wf[2][NI], xf[2][MI];
+          constexpr int NR = NI + MI, NPC = CG_WP + NX;
+  #pragma unroll
+          for (int r = 0; r < NR; ++r) {
+            if (r < NI) {
+              const int ni = r < NI ? r : 0;
+              const char* pw = ws + (wrow0 + ni * 16) * 128;
+              wf[0][ni] = *reinterpret_cast<const v8_t*>(pw + ((g ^ fsw) << 4));
+              wf[1][ni] = *reinterpret_cast<const v8_t*>(pw + (((4 + g) ^ fsw) << 4));
+            } else {
+              const int mi = r >= NI ? r - NI : 0;
+              // k-slot g of halo pixel hp0 + 16 mi (same swizzle for every mi: 16 = 0 mod 8; ks = 1: slot g + 4 = ^ 64 B)
+              int o0 = xbase + mi * 2048;
+              if constexpr (t % 3 == 0) o0 = (edge >> mi) & 1u ? CG_T_ZERO : o0;
+              if constexpr (t % 3 == 2) o0 = (edge >> (8 + mi)) & 1u ? CG_T_ZERO : o0;
+              xf[0][mi] = *reinterpret_cast<const v8_t*>(smem + o0);
+              xf[1][mi] = *reinterpret_cast<const v8_t*>(smem + (o0 ^ 64));
+            }
+            // piece k goes after read number ceil((k + 1) * NR / (NPC + 1))
+  #pragma unroll
+            for (int k = 0; k < NPC; ++k)
+              if (((k + 1) * NR + NPC) / (NPC + 1) == r + 1) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (k < CG_WP) issue_w_piece(rsw, st_w, k < CG_WP ? k : 0, sow);
+                else if (t == 0 && k == NPC - 1) issue_gb(c + 1, hbn, nxt);
+                else issue_halo_piece(hbn, 2 * t + (k - CG_WP < 2 ? k - CG_WP : 0));
+                __builtin_amdgcn_sched_barrier(0);
+              }
+          }
+          if constexpr (PP) {
+            // Y: this wave's weight pieces of the NEXT K step (issued in the previous tap) have landed, its fragments of this
+            // one are in registers
+            constexpr int V = NXT((t + 8) % 9) + CG_WP + NX;
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(V) : "memory");
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          if constexpr (NMODE != 3) __builtin_amdgcn_s_setprio(1);
+          if constexpr (NT && NMODE == 1) {
+            // One matrix instruction per slot, and behind each a fixed slice of the strip's normalisation, pinned by
+            // sched_barrier(0) -- left to the scheduler (sched_group_barrier) the 64 VALU instructions ended up BEHIND the
+            // burst as one dependent chain of LDS round trips and transcendental latencies (~600 cycles per strip, nothing
+            // hidden; profiles/r04_conv_gn_variants.txt).  The program works on two channel pairs at a time (four
+            // independent chains, a dependent instruction at least two slots = 32 cycles behind its producer, 12 live
+            // registers besides the strip itself), one transcendental per slot at most:
+            //   U unpack, F x * scale + shift, M * -log2(e), X exp2 (one per slot), A 1 +, R rcp (one per slot), S *, C pack
+            // for pairs (0, 1), then (2, 3) with the second half of the (scale, shift) row loaded meanwhile; LDS store last.
+            constexpr int NM = 2 * MI * NI, NG = 41;
+            const uint32_t vmask = ~(uint32_t)(hpix[NT ? t - 3 : 0] >> 31);   // all ones inside the image, else 0
+            const char* const sp = smem + CG_T_SCSH + kslot * 64;
+            float xa[4], ea[4];
+            u32x4_t no;
+            auto micro = [&](auto GG) __attribute__((always_inline)) {
+              constexpr int g = decltype(GG)::value;
+              if constexpr (g == 40) {
+                *reinterpret_cast<u32x4_t*>(np) = no;
+              } else {
+                constexpr int h = g / 20, gg = g % 20, p0 = 2 * h, p1 = 2 * h + 1;
+                if constexpr (gg == 0) { xa[0] = E::lo(nv[p0]); xa[1] = E::hi(nv[p0]); }
+                if constexpr (gg == 1) { xa[2] = E::lo(nv[p1]); xa[3] = E::hi(nv[p1]); }
+                if constexpr (gg == 2) { xa[0] = __builtin_fmaf(xa[0], ss0[0], ss0[1]); xa[1] = __builtin_fmaf(xa[1], ss0[2], ss0[3]); }
+                if constexpr (gg == 3) { xa[2] = __builtin_fmaf(xa[2], ss1[0], ss1[1]); xa[3] = __builtin_fmaf(xa[3], ss1[2], ss1[3]); }
+                if constexpr (gg == 4) { ea[0] = xa[0] * -1.44269504088896340736f; ea[1] = xa[1] * -1.44269504088896340736f; }
+                if constexpr (gg == 5) { ea[2] = xa[2] * -1.44269504088896340736f; ea[3] = xa[3] * -1.44269504088896340736f; }
+                if constexpr (gg == 6) {
+                  ea[0] = __builtin_amdgcn_exp2f(ea[0]);
+                  if constexpr (h == 0) ss0 = *reinterpret_cast<const f32x4_t*>(sp + 32);
+                }
+                if constexpr (gg == 7) {
+                  ea[1] = __builtin_amdgcn_exp2f(ea[1]);
+                  if constexpr (h == 0) ss1 = *reinterpret_cast<const f32x4_t*>(sp + 48);
+                }
+                if constexpr (gg == 8) ea[2] = __builtin_amdgcn_exp2f(ea[2]);
+                if constexpr (gg == 9) ea[3] = __builtin_amdgcn_exp2f(ea[3]);
+                if constexpr (gg == 10) { ea[0] += 1.0f; ea[1] += 1.0f; }
+                if constexpr (gg == 11) { ea[2] += 1.0f; ea[3] += 1.0f; }
+                if constexpr (gg == 12) ea[0] = __builtin_amdgcn_rcpf(ea[0]);
+                if constexpr (gg == 13) ea[1] = __builtin_amdgcn_rcpf(ea[1]);
+                if constexpr (gg == 14) ea[2] = __builtin_amdgcn_rcpf(ea[2]);
+                if constexpr (gg == 15) ea[3] = __builtin_amdgcn_rcpf(ea[3]);
+                if constexpr (gg == 16) { xa[0] *= ea[0]; xa[1] *= ea[1]; }
+                if constexpr (gg == 17) { xa[2] *= ea[2]; xa[3] *= ea[3]; }
+                if constexpr (gg == 18) no[p0] = E::pack2(xa[0], xa[1]) & vmask;   // (a mask, not a select: hipcc turns the
+                if constexpr (gg == 19) no[p1] = E::pack2(xa[2], xa[3]) & vmask;   //  select into a branch around the math)
+              }
+            };
+            cg_static_for<NM>([&](auto II) __attribute__((always_inline)) {
+              constexpr int i = decltype(II)::value;
+              constexpr int ks = i / (NI * MI), ni = (i / MI) % NI, mi = i % MI;
+              acc[ni][mi] = E::mfma16(wf[ks][ni], xf[ks][mi], acc[ni][mi]);
+              __builtin_amdgcn_sched_barrier(0);
+              constexpr int G0 = i * NG / NM, G1 = (i + 1) * NG / NM;
+              cg_static_for<G1 - G0>([&](auto JJ) __attribute__((always_inline)) {
+                micro(std::integral_constant<int, G0 + decltype(JJ)::value>{});
+              });
+              __builtin_amdgcn_sched_barrier(0);
+            });
+          } else {
+            mfma_all(wf, xf);
+          }
+          if constexpr (NMODE != 3) __builtin_amdgcn_s_setprio(0);
+          __builtin_amdgcn_sched_barrier(0);
+        });
+        hb ^= 1;
+      }
     }
     if (PP && grp == 0) asm volatile("s_barrier" ::: "memory");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -543,6 +632,11 @@ __global__ void __launch_bounds__(CG_T, 2) pp_conv_gn_kernel(const PPGemmArgs a,
   // epilogue: 64-row passes through LDS (the staged form of gemm.hip): lane holds columns n = .. + 4 (lane >> 4) + {0..3}
   // of row m = .. + (lane & 15); thread = fixed 8-column strip on the read-back side
   // =====================================================================================================================
+  // (sub-pixel form) tile row m = source pixel (bimg, i, j) -> row of output pixel (2i + pa, 2j + pb) in [B][2H][2W][N]
+  auto out_row = [&](int m) __attribute__((always_inline)) -> size_t {
+    const int l = m - bimg * HW, i = l / Wd, j = l - i * Wd;
+    return (size_t)bimg * 4u * (size_t)HW + (size_t)((2 * i + pa) * 2 * Wd + 2 * j + pb);
+  };
   const bool splitk = splits > 1;
   const bool gns = !splitk && (a.gn_acc[0] || a.gn_acc[1]);
   const int my_pass = (wm * (MI * 16)) / EPI_ROWS;
@@ -584,9 +678,12 @@ __global__ void __launch_bounds__(CG_T, 2) pp_conv_gn_kernel(const PPGemmArgs a,
         for (int j = 0; j < EP; ++j) {
           const int row = r0 + j * ER, m = m0 + row;
           const bool ok = row < EPI_ROWS && m < a.M;
-          r1[j] = (ok && a.res1) ? *reinterpret_cast<const u32x4_t*>((const uint16_t*)a.res1 + (size_t)((a.res1_wrap_rows > 0 && m >= a.res1_wrap_rows) ? m - a.res1_wrap_rows : m) * a.ldres1 + n)
+          // row of the residual tensors ((sub-pixel form) they have the OUTPUT's geometry; res1_wrap_rows == 0, host-checked)
+          const size_t m1 = SUBPIX ? out_row(m) : (size_t)((a.res1_wrap_rows > 0 && m >= a.res1_wrap_rows) ? m - a.res1_wrap_rows : m);
+          const size_t m2 = SUBPIX ? out_row(m) : (size_t)m;
+          r1[j] = (ok && a.res1) ? *reinterpret_cast<const u32x4_t*>((const uint16_t*)a.res1 + m1 * a.ldres1 + n)
                                  : u32x4_t{0u, 0u, 0u, 0u};
-          r2[j] = (ok && a.res2) ? *reinterpret_cast<const u32x4_t*>((const uint16_t*)a.res2 + (size_t)m * a.ldres2 + n)
+          r2[j] = (ok && a.res2) ? *reinterpret_cast<const u32x4_t*>((const uint16_t*)a.res2 + m2 * a.ldres2 + n)
                                  : u32x4_t{0u, 0u, 0u, 0u};
         }
         f32x4_t bs0 = {0.f, 0.f, 0.f, 0.f}, bs1 = {0.f, 0.f, 0.f, 0.f};
@@ -616,7 +713,7 @@ __global__ void __launch_bounds__(CG_T, 2) pp_conv_gn_kernel(const PPGemmArgs a,
             u32x4_t o;
             o[0] = E::pack2(v0[0], v0[1]); o[1] = E::pack2(v0[2], v0[3]);
             o[2] = E::pack2(v1[0], v1[1]); o[3] = E::pack2(v1[2], v1[3]);
-            *reinterpret_cast<u32x4_t*>((uint16_t*)a.out + (size_t)m * a.ldo + n) = o;
+            *reinterpret_cast<u32x4_t*>((uint16_t*)a.out + (SUBPIX ? out_row(m) : (size_t)m) * a.ldo + n) = o;
             if (gns) {   // per-column moments of the values as stored, over this thread's rows of the tile
 #pragma unroll
               for (int jj = 0; jj < 4; ++jj) {
@@ -679,7 +776,7 @@ bool cg_geometry_ok(const PPGemmArgs& a) {
   const int ctot = a.c1 + a.c2;
   if (a.c1 <= 0 || a.c1 % 64 || a.c2 % 64 || (a.c2 > 0 && !a.x2)) return false;
   if (a.c3 < 0 || a.c4 < 0 || a.c3 % 64 || a.c4 % 64 || (a.c3 > 0 && !a.x3) || (a.c4 > 0 && (!a.x4 || a.c3 == 0))) return false;
-  if (a.K != 9 * ctot + a.c3 + a.c4 || a.M != a.batch * a.hout * a.wout || a.M <= 0 || a.N <= 0) return false;
+  if (a.K != (a.subpix ? 4 : 9) * ctot + a.c3 + a.c4 || a.M != a.batch * a.hout * a.wout || a.M <= 0 || a.N <= 0) return false;
   if (a.N % 8 || a.ldo % 8 || a.out_f32 || a.out_vt || a.act != PP_ACT_NONE || a.ln_stats || a.row_stats_out) return false;
   if ((a.res1 && a.ldres1 % 8) || (a.res2 && a.ldres2 % 8)) return false;
   if (a.rows_per_batch != a.hout * a.wout || a.out_dup_rows > 0 || a.w_batch_stride > 0 || a.vec_batch_stride > 0) return false;
@@ -693,7 +790,7 @@ bool cg_geometry_ok(const PPGemmArgs& a) {
 
 // norm -> SiLU -> conv3x3 in one launch (the request carries the producers' statistics of its input)
 bool cg_fused_ok(const PPGemmArgs& a) {
-  if (!a.gn_in_acc || !a.gn_in_gb || a.up || !cg_geometry_ok(a)) return false;
+  if (!a.gn_in_acc || !a.gn_in_gb || a.up || a.subpix || !cg_geometry_ok(a)) return false;
   if (a.gn_in_silu != 1 || a.gn_in_groups <= 0 || a.gn_in_groups > 32) return false;
   return (a.c1 + a.c2) % a.gn_in_groups == 0;
 }
@@ -708,8 +805,28 @@ bool cg_fused_ok(const PPGemmArgs& a) {
 // (lab) PP_CONV_RAW = the smallest image width routed here (0 = never)
 bool cg_raw_ok(const PPGemmArgs& a) {
   static const int min_w = pp_lab_env("PP_CONV_RAW", 16);
-  if (a.gn_in_acc || a.gn_in_gb || a.tile != PP_TILE_AUTO || min_w <= 0 || a.wout < min_w) return false;
+  if (a.gn_in_acc || a.gn_in_gb || a.subpix || a.tile != PP_TILE_AUTO || min_w <= 0 || a.wout < min_w) return false;
   return cg_geometry_ok(a);
+}
+
+// The sub-pixel form of an upsampling conv (PPGemmArgs.subpix, the kernel's NMODE 4): the request describes the SOURCE image,
+// so the loader's geometry rules (cg_geometry_ok: stride 1, tiles of whole source rows inside one image) apply to it as
+// they stand.  One source tensor, no 1x1 tail, one pass: a forced split is refused (the four parities of a tile would need
+// four slabs per split), as is everything the scattered epilogue does not implement.
+bool cg_subpix_ok(const PPGemmArgs& a) {
+  if (a.subpix != 1 || a.up || a.gn_in_acc || a.gn_in_gb || a.c2 || a.c3 || a.c4 || a.splitk > 1) return false;
+  if (a.res1_wrap_rows > 0 || a.gn_next_out || a.gn_dup_mask) return false;
+  return cg_geometry_ok(a);
+}
+
+// its tile: the largest that still fills the chip with (tiles x 4 parities) workgroups, else the largest the image takes
+CGChoice cg_choose_subpix(const PPGemmArgs& a) {
+  const int tn = (a.N + 159) / 160;
+  const int want = a.tile == PP_TILE_256x160 ? 256 : a.tile == PP_TILE_128x160 ? 128 : a.tile == PP_TILE_64x160 ? 64 : 0;
+  if (want && cg_shape_ok(a, want)) return CGChoice{want, 1};
+  for (int bm = 256; bm >= 64; bm >>= 1)
+    if (cg_shape_ok(a, bm) && 4 * (a.M / bm) * tn >= 224) return CGChoice{bm, 1};
+  return CGChoice{cg_shape_ok(a, 256) ? 256 : cg_shape_ok(a, 128) ? 128 : 64, 1};
 }
 
 CGChoice cg_choose(const PPGemmArgs& a) {
@@ -777,7 +894,7 @@ int cg_launch(const PPGemmArgs& a, int splitk, hipStream_t st) {
   d.hp = BM + 2 * a.wout;
   d.cg = a.gn_in_groups > 0 ? (a.c1 + a.c2) / a.gn_in_groups : 1;
   d.inv_cg = 1.0f / (float)d.cg;
-  hipLaunchKernelGGL(kern, dim3(d.tiles_m * d.tiles_n, splitk, 1), dim3(CG_T), CG_LDS, st, a, d);
+  hipLaunchKernelGGL(kern, dim3(d.tiles_m * d.tiles_n * (NMODE == 4 ? 4 : 1), splitk, 1), dim3(CG_T), CG_LDS, st, a, d);
   PP_CHECK_LAUNCH("pp_conv_gn_kernel");
   return PP_OK;
 }
@@ -822,6 +939,13 @@ int cg_dispatch(const PPGemmArgs& a, const CGChoice& c, hipStream_t st) {
 #undef CG_CASE
   }
 #endif
+  if (a.subpix) {                     // the sub-pixel form of an upsampling conv (cg_subpix_ok)
+    switch (c.bm) {
+      case 256: return cg_launch_hpw<256, true, 4, EDT>(a, 1, st);
+      case 128: return cg_launch_hpw<128, true, 4, EDT>(a, 1, st);
+      default: return cg_launch_hpw<64, true, 4, EDT>(a, 1, st);
+    }
+  }
   if (!a.gn_in_acc) {                 // plain conv: the loop without the normalisation (cg_raw_ok)
     switch (c.bm) {
       case 256: return cg_launch_hpw<256, true, 2, EDT>(a, c.splitk, st);
@@ -842,6 +966,11 @@ int cg_dispatch(const PPGemmArgs& a, const CGChoice& c, hipStream_t st) {
 // or a plain conv the library sends here (cg_raw_ok)
 int pp_conv_gn_form(const PPGemmArgs& a, CGChoice* c) {
   if (a.x_mode != PP_X_CONV3X3) return 0;
+  if (a.subpix) {                     // a form of its own, asked for by name: it runs here or not at all
+    if (!cg_subpix_ok(a)) return PP_ERR_UNSUPPORTED;
+    *c = cg_choose_subpix(a);
+    return 1;
+  }
   if (a.gn_in_acc) {
     if (!cg_fused_ok(a)) return PP_ERR_UNSUPPORTED;
   } else if (!cg_raw_ok(a)) {
@@ -860,6 +989,30 @@ int pp_conv_gn_run(const PPGemmArgs& a, const CGChoice& c, hipStream_t st) {
 extern "C" int pp_conv_gn_supported(const PPGemmArgs* args) {
   if (!args) return 0;
   return cg_fused_ok(*args) ? 1 : cg_raw_ok(*args) ? 2 : 0;
+}
+
+// the sub-pixel request of these SOURCE shapes as a planner would build it: 0 refused, 1 runs, 2 runs and is routed (source
+// images from 16 pixels of width: where plain convs take this loop at all, cg_raw_ok -- at 8x8 the launch is a weight stream
+// and the folded weights are 16/9 of the bytes)
+extern "C" int pp_upconv_subpix_supported(int batch, int h, int w, int cin, int cout, int dtype) {
+  if (batch <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return 0;
+  PPGemmArgs a = {};
+  a.x_mode = PP_X_CONV3X3;
+  a.dtype = dtype;
+  a.batch = batch;
+  a.hin = a.hout = h;
+  a.win = a.wout = w;
+  a.stride = 1;
+  a.c1 = cin;
+  a.M = batch * h * w;
+  a.N = cout;
+  a.K = 4 * cin;
+  a.ldo = a.ldres1 = a.ldres2 = cout;
+  a.rows_per_batch = h * w;
+  a.subpix = 1;
+  if ((uint64_t)batch * h * w * 4u * (uint64_t)cout * 2u >= (1ull << 40)) return 0;
+  if (!cg_subpix_ok(a)) return 0;
+  return w >= 16 ? 2 : 1;
 }
 
 // Where the fused launch beats pp_groupnorm_apply_acc + plain conv inside the UNet step (same-box A/Bs of the headline

@@ -1764,6 +1764,7 @@ int validate(const PPGemmArgs& a) {
   if (a.K % 64 != 0 || a.N % 4 != 0) return PP_ERR_BAD_ARG;
   if (!a.x1 || !a.w || !a.out) return PP_ERR_BAD_ARG;
   if (a.x_mode == PP_X_PLAIN) {
+    if (a.subpix) return PP_ERR_BAD_ARG;
     if (a.c1 + a.c2 != a.K) return PP_ERR_BAD_ARG;
     if (a.c2 > 0 && (!a.x2 || a.c1 % 64 != 0)) return PP_ERR_BAD_ARG;
     if (a.ldx1 % 8 != 0 || (a.c2 > 0 && a.ldx2 % 8 != 0)) return PP_ERR_BAD_ARG;
@@ -1774,7 +1775,10 @@ int validate(const PPGemmArgs& a) {
     if (a.c3 < 0 || a.c4 < 0 || a.c3 % 64 || a.c4 % 64 || (a.c3 > 0 && !a.x3) || (a.c4 > 0 && (!a.x4 || a.c3 == 0)))
       return PP_ERR_BAD_ARG;
     if ((a.c3 > 0) && (a.stride != 1 || a.up)) return PP_ERR_UNSUPPORTED;
-    if (a.K != 9 * (a.c1 + a.c2) + a.c3 + a.c4) return PP_ERR_BAD_ARG;
+    // (ABI v28) the sub-pixel form of an upsampling conv: four taps on folded weights over the SOURCE image
+    if (a.subpix != 0 && a.subpix != 1) return PP_ERR_BAD_ARG;
+    if (a.subpix && (a.up || a.stride != 1)) return PP_ERR_BAD_ARG;
+    if (a.K != (a.subpix ? 4 : 9) * (a.c1 + a.c2) + a.c3 + a.c4) return PP_ERR_BAD_ARG;
     if (a.stride != 1 && a.stride != 2) return PP_ERR_BAD_ARG;
     if (a.M != a.batch * a.hout * a.wout) return PP_ERR_BAD_ARG;
     const int hv = a.up ? 2 * a.hin : a.hin, wv = a.up ? 2 * a.win : a.win;
@@ -1851,7 +1855,7 @@ int resolve_form(const PPGemmArgs& a, LaunchForm* f) {
   const int halo = pp_conv_gn_form(a, &cg);
   if (halo < 0) return halo;
   if (halo) {
-    *f = LaunchForm{Family::HALO, 0, cg.bm, (a.M / cg.bm) * tn, cg.splitk, true};
+    *f = LaunchForm{Family::HALO, 0, cg.bm, (a.M / cg.bm) * tn * (a.subpix ? 4 : 1), cg.splitk, true};
     return PP_OK;
   }
   const Choice c = choose(a);

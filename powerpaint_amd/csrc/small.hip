@@ -291,6 +291,42 @@ __global__ void __launch_bounds__(256) add_bf16_kernel(const uint16_t* __restric
   }
 }
 
+// ------------------------------------------------------------------------------------------ sub-pixel upsampling conv
+// The folded weights of PPGemmArgs.subpix (include/pp_hip.h, pp_upconv_fold): out[2a + b][n][dy][dx][c] = the sum of the
+// taps (ky, kx) of w[n][ky][kx][c] that read source pixel (i + a - 1 + dy, j + b - 1 + dx) for output pixel (2i + a, 2j + b)
+// of `nearest 2x -> conv3x3`: ky in [lo(a, dy), hi(a, dy)] with lo = dy ? 1 + a : 0, hi = dy ? 2 : a, kx likewise from (b, dx).
+// One thread = 8 channels of one (parity, n, dy, dx); fp32 sums in the order ky outer, kx inner, one rounding.
+template <int EDT>
+__global__ void __launch_bounds__(256) upconv_fold_kernel(const uint16_t* __restrict__ w, uint16_t* __restrict__ out, int cout,
+                                                          int cin8, long long total) {
+  using E = E16<EDT>;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int c8 = (int)(i % cin8);
+    long long r = i / cin8;
+    const int dx = (int)(r & 1), dy = (int)((r >> 1) & 1);
+    r >>= 2;
+    const int n = (int)(r % cout), par = (int)(r / cout);
+    const int pa = par >> 1, pb = par & 1;
+    const int ky0 = dy ? 1 + pa : 0, ky1 = dy ? 2 : pa, kx0 = dx ? 1 + pb : 0, kx1 = dx ? 2 : pb;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    for (int ky = ky0; ky <= ky1; ++ky)
+      for (int kx = kx0; kx <= kx1; ++kx) {
+        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(w + (((size_t)n * 9 + ky * 3 + kx) * cin8 + c8) * 8);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          acc[2 * q] += E::lo(v[q]);
+          acc[2 * q + 1] += E::hi(v[q]);
+        }
+      }
+    u32x4_t o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = E::pack2(acc[2 * q], acc[2 * q + 1]);
+    *reinterpret_cast<u32x4_t*>(out + i * 8) = o;
+  }
+}
+
 // ------------------------------------------------------------------------------------------ CFG + scheduler step
 PP_DEVINL void cfg_sched_step_body(const float* __restrict__ eps2, int cfg, float g, float* __restrict__ x,
                                    float* __restrict__ m_prev, int n, int kind, const float* __restrict__ coef,
@@ -705,6 +741,15 @@ extern "C" int pp_add_bf16(const void* a, const void* b, void* out, long long n,
   PP_DT_SWITCH(dtype, hipLaunchKernelGGL(add_bf16_kernel<EDT>, dim3(grid_for_host(n / 8)), dim3(256), 0, (hipStream_t)stream,
                                          (const uint16_t*)a, (const uint16_t*)b, (uint16_t*)out, n / 8));
   PP_CHECK_LAUNCH("add_bf16_kernel");
+  return PP_OK;
+}
+
+extern "C" int pp_upconv_fold(const void* w, int cout, int cin, int dtype, void* out, void* stream) {
+  if (!w || !out || cout <= 0 || cin <= 0 || cin % 8 || !pp_dt_ok(dtype)) return PP_ERR_BAD_ARG;
+  const long long total = 16ll * cout * (cin / 8);
+  PP_DT_SWITCH(dtype, hipLaunchKernelGGL(upconv_fold_kernel<EDT>, dim3(grid_for_host(total)), dim3(256), 0, (hipStream_t)stream,
+                                         (const uint16_t*)w, (uint16_t*)out, cout, cin / 8, total));
+  PP_CHECK_LAUNCH("upconv_fold_kernel");
   return PP_OK;
 }
 

@@ -47,6 +47,13 @@ TWIN_PREFIX = _lab_switch("PP_TWIN")
 # round 6: the split-K combine inside the producing kernel, every split combining its own share of the tile
 # (csrc/gemm_combine.h, PPGemmArgs.tile_ctr).  (lab) PP_FUSED_COMBINE=0: the separate combine launches
 FUSED_COMBINE = _lab_switch("PP_FUSED_COMBINE")
+# Upsample2D's `nearest 2x -> conv3x3` as four 2x2 sub-pixel convs on folded weights, 4/9 of the MACs (PPGemmArgs.subpix,
+# csrc/conv_gn.hip NMODE 4), where pp_upconv_subpix_supported() routes it.  (lab) PP_UPCONV_SUBPIX=0: the nine-tap launch
+# over the upsampled image everywhere -- the plan of ABI v27, bit for bit
+UPCONV_SUBPIX = _lab_switch("PP_UPCONV_SUBPIX")
+# (lab) PP_UPCONV_SUBPIX=2: also where the library says "runs" but does not route (the 8 -> 16 upsampler, a weight stream
+# that would read 16/9 of the weight bytes: the arm of its A/B)
+UPCONV_SUBPIX_FROM = 1 if (os.environ.get("PP_LAB") == "1" and os.environ.get("PP_UPCONV_SUBPIX") == "2") else 2
 
 
 class Arena:
@@ -173,7 +180,8 @@ class Plan:
         self.calls: List[Tuple] = []     # (fn, args_tuple, name)
         self.keep: List = []             # keep ctypes structs alive
         self.flops = 0.0                 # algorithmic FLOPs (2*MAC of conv/linear/attention matmuls)
-        self.flops_by_kind: Dict[str, float] = {}
+        self.flops_by_kind: Dict[str, float] = {}  # FLOPs the launches EXECUTE, by launch name
+        self.flops_skipped = 0.0         # part of `flops` no launch executes (sub-pixel upsampling convs: 5 of 9 taps)
 
     def add(self, name: str, fn, *args):
         self.calls.append((fn, args, name))
@@ -181,6 +189,15 @@ class Plan:
     def count(self, kind: str, flops: float):
         self.flops += flops
         self.flops_by_kind[kind] = self.flops_by_kind.get(kind, 0.0) + flops
+
+    def skip(self, flops: float):
+        """MACs of the algorithm that the plan's launches do not execute: in `flops`, not in `flops_by_kind` / `flops_executed`."""
+        self.flops += flops
+        self.flops_skipped += flops
+
+    @property
+    def flops_executed(self) -> float:
+        return self.flops - self.flops_skipped
 
     def run(self, stream: int):
         for fn, args, name in self.calls:
@@ -275,7 +292,11 @@ class Builder:
         self.last_gemm = a
         a._arena_top = self.arena.off       # everything this launch reads or scratches lies below (see _apply_in_producer_combine)
         self.plan.add(name, self.lib.pp_gemm_bf16, C.byref(a))
-        self.plan.count(name, 2.0 * a.M * a.N * a.K)
+        if a.subpix:      # four parities of M rows on four taps each; the nine-tap algorithm has 9/4 of these MACs
+            self.plan.count(name, 4 * 2.0 * a.M * a.N * a.K)
+            self.plan.skip(5 * 2.0 * a.M * a.N * a.K)
+        else:
+            self.plan.count(name, 2.0 * a.M * a.N * a.K)
 
     def linear(self, x: int, rows: int, K: int, w: int, N: int, bias: int = 0, ldx: Optional[int] = None,
                x2: int = 0, K2: int = 0, ldx2: int = 0, res1: int = 0, ldres1: int = 0, res2: int = 0,
@@ -364,6 +385,18 @@ class Builder:
         self.release(m)
         return out
 
+    def conv3x3_up_subpix(self, x: Act, wfold: int, cout: int, bias: int = 0, res2: int = 0, name: str = "conv3x3") -> Act:
+        """Upsample2D's `nearest 2x -> conv3x3` in its sub-pixel form (PPGemmArgs.subpix): four 2x2 convs over the source x on
+        the folded weights at `wfold` (pp_upconv_fold, SDNet.build_setup) -> [B][2H][2W][cout]; res2 has the output's shape.
+        The caller has asked pp_upconv_subpix_supported()."""
+        a = L.conv3x3_args(self.dt, x.B, x.H, x.W, x.C, cout, x.ptr, w=wfold)
+        a.K, a.subpix = 4 * x.C, 1
+        out = self.new_act(x.B, 2 * x.H, 2 * x.W, cout)
+        a.out, a.bias, a.res2 = out.ptr, bias or None, res2 or None
+        self._gemm(a, name)
+        out.producer = a
+        return out
+
     def groupnorm(self, x: Act, gamma: int, beta: int, eps: float, silu: bool, x2: Optional[Act] = None,
                   groups: int = 32, out: Optional[Act] = None) -> Act:
         c2 = x2.C if x2 is not None else 0
@@ -438,11 +471,12 @@ class Builder:
             a = t.producer
             if a is None or (a.gn_acc[0] and a.gn_acc[1]):
                 return 0
+            rows = hw // 4 if a.subpix else hw      # (sub-pixel form: the request counts SOURCE pixels, a quarter of the tensor's)
             rpb = a.rows_per_batch
-            a.rows_per_batch = hw
+            a.rows_per_batch = rows
             ok = self.lib.pp_gemm_gn_stats_ok(C.byref(a))
             a.rows_per_batch = rpb
-            if not ok or (rpb not in (0, hw)):
+            if not ok or (rpb not in (0, rows)):
                 return 0
         nbytes = x.B * groups * 2 * 8
         if self.gn_acc_used + nbytes > self.gn_acc_cap:
@@ -452,7 +486,7 @@ class Builder:
         for t, c0 in parts:
             a = t.producer
             k = 0 if not a.gn_acc[0] else 1
-            a.rows_per_batch = hw
+            a.rows_per_batch = hw // 4 if a.subpix else hw
             a.gn_acc[k], a.gn_cg[k], a.gn_c0[k], a.gn_groups[k] = acc, Ct // groups, c0, groups
             if t.dup_half:       # this consumer sees the full (twice-stored) tensor: both halves' accumulators get the sums
                 a.gn_dup_batch, a.gn_dup_mask = t.dup_half, a.gn_dup_mask | (1 << k)
@@ -1363,6 +1397,18 @@ class SDNet:
                             self.P[f"{tbq}.bias"] if fold else None, self.P[f"{tb}.attn2.to_out.weight"],
                             float(c // self.heads) ** -0.5, gt, gcs, gb, ht, int(kperm), pb.dt)
                 self.xa[pre] = (gt, gcs, gb, ht, kperm)
+        # Upsample2D convs in their sub-pixel form (PPGemmArgs.subpix): the folded weights are a cache derived from the packed
+        # conv weight, rebuilt with everything else here whenever ParamPack.version has moved (NetRuntime.set_context)
+        self.upfold: Dict[str, int] = {}
+        if UPCONV_SUBPIX and hw0 is not None and self.kind in ("unet", "brushnet") and not (pb.gemm_tile or pb.gemm_splitk):
+            rev = list(reversed(self.boc))
+            for i in range(len(rev) - 1):
+                lvl = len(rev) - 1 - i
+                h, w, c = hw0[0] >> lvl, hw0[1] >> lvl, rev[i]
+                if pb.lib.pp_upconv_subpix_supported(B, h, w, c, c, pb.dt) >= UPCONV_SUBPIX_FROM:
+                    pre = f"up_blocks.{i}.upsamplers.0.conv"
+                    self.upfold[pre] = pb.alloc(16 * c * c * 2)
+                    pb.plan.add("upconv_fold", pb.lib.pp_upconv_fold, self.P[pre + ".weight"], c, c, pb.dt, self.upfold[pre])
         self.cond_emb = None
         if self.kind == "controlnet":
             assert cond is not None
@@ -1541,8 +1587,11 @@ class SDNet:
                 brush_up.append(s)
             if i != len(boc) - 1:
                 pre = f"up_blocks.{i}.upsamplers.0.conv"
-                s = pb.conv3x3(s, P[pre + ".weight"], rev[i], P[pre + ".bias"], up=True, res2=pop(add_up),
-                               name="conv3x3")
+                if pre in getattr(self, "upfold", {}):
+                    s = pb.conv3x3_up_subpix(s, self.upfold[pre], rev[i], P[pre + ".bias"], res2=pop(add_up))
+                else:
+                    s = pb.conv3x3(s, P[pre + ".weight"], rev[i], P[pre + ".bias"], up=True, res2=pop(add_up),
+                                   name="conv3x3")
                 brush_up.append(s)
 
         if self.kind == "brushnet":

@@ -212,6 +212,44 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, bias=None, stride: int = 1, up: bo
     return (out, ynext) if gn_next is not None else out
 
 
+def upconv_fold(w: torch.Tensor) -> torch.Tensor:
+    """The folded weights of the sub-pixel upsampling conv (pp_upconv_fold): w 16-bit [Cout, 9*C] (k = (ky*3+kx)*C + c) ->
+    [4, Cout, 4*C], parity p = 2a + b, k = (dy*2+dx)*C + c."""
+    cout, cin = w.shape[0], w.shape[1] // 9
+    assert w.is_contiguous() and w.shape[1] == 9 * cin
+    out = torch.empty(4, cout, 4 * cin, dtype=w.dtype, device=w.device)
+    L.check(L.lib().pp_upconv_fold(_p(w), cout, cin, L.dtype_code(w.dtype), _p(out), _s()), "pp_upconv_fold")
+    return out
+
+
+def upconv_subpix_supported(x: torch.Tensor, cout: int) -> int:
+    """pp_upconv_subpix_supported for a source tensor x NHWC [B,H,W,C]: 0 refused, 1 runs, 2 runs and the plans route it."""
+    B, H, W, C1 = x.shape
+    return int(L.lib().pp_upconv_subpix_supported(B, H, W, C1, cout, L.dtype_code(x.dtype)))
+
+
+def conv3x3_up_subpix(x: torch.Tensor, wfold: torch.Tensor, bias=None, rowvec=None, res1=None, res2=None, scale: float = 1.0,
+                      tile: int = 0, splitk: int = 0, gn=None):
+    """`nearest 2x -> conv3x3` of x NHWC [B,H,W,C] in its sub-pixel form (PPGemmArgs.subpix) on wfold = upconv_fold(w)
+    -> NHWC [B,2H,2W,Cout]; res1 / res2 have the output's shape, `gn` subscriptions describe the output tensor.  Raises
+    PPError(PP_ERR_UNSUPPORTED) where upconv_subpix_supported() is 0 or a split is forced; conv3x3(up=True) is the other,
+    nine-tap request and is not routed here."""
+    B, H, W, C1 = x.shape
+    cout = wfold.shape[1]
+    assert tuple(wfold.shape) == (4, cout, 4 * C1) and wfold.is_contiguous()
+    a = L.conv3x3_args(L.dtype_code(x.dtype), B, H, W, C1, cout, _p(x))
+    a.K, a.subpix = 4 * C1, 1
+    out = torch.empty(B, 2 * H, 2 * W, cout, dtype=x.dtype, device=x.device)
+    a.w, a.out, a.scale = _p(wfold), _p(out), scale
+    a.bias, a.rowvec, a.res1, a.res2 = _p(bias), _p(rowvec), _p(res1), _p(res2)
+    if rowvec is not None and rowvec.dim() == 2 and rowvec.shape[0] > 1:
+        a.ld_rowvec = rowvec.stride(0)
+    a.tile, a.splitk = tile, splitk
+    _set_gn(a, gn, H * W)
+    L.check(L.lib().pp_gemm_bf16(C.byref(a), _s()), "pp_gemm_bf16(sub-pixel upsampling conv)")
+    return out
+
+
 def groupnorm(x: torch.Tensor, gamma, beta, eps: float, silu: bool, groups: int = 32, x2=None):
     """x NHWC bf16 [B,H,W,C1] (+x2) -> NHWC bf16 [B,H,W,C1+C2]; gamma/beta fp32."""
     lib = L.lib()

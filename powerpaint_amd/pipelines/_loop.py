@@ -339,7 +339,7 @@ class DenoiseLoop:
                 full.calls += heads[id(r)]
             for r in side_rts + [rt]:
                 full.calls += [c for i, c in enumerate(r.step_plan.calls) if i not in skips[id(r)]]
-                full.flops += r.step_plan.flops
+                full.flops += r.step_plan.flops_executed      # (a program's `flops`: what its launches execute)
             full.calls += prog.calls
             self.program = full
         self._keep = (ts, step, mp, lat)
@@ -426,11 +426,11 @@ class DenoiseLoop:
             calls, records[k] = rts[k].chained_step_calls(rts[0], accumulate=n > 0, scale=0.0,
                                                          skip=P["skips"][id(rts[k])])
             prog.calls += calls
-            prog.flops += rts[k].step_plan.flops
+            prog.flops += rts[k].step_plan.flops_executed
         if not included:
             prog.add("zero_u64", self.lib.pp_zero_u64, *rts[0].residual_block())
         prog.calls += [c for i, c in enumerate(self.rt.step_plan.calls) if i not in P["skips"][id(self.rt)]]
-        prog.flops += self.rt.step_plan.flops
+        prog.flops += self.rt.step_plan.flops_executed
         prog.calls += P["tail"]
         ent = self._sets[active] = dict(active=active, included=included, program=prog, records=records, graph=None,
                                         scales=None)
