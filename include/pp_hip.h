@@ -242,6 +242,35 @@ typedef struct PPGemmArgs {
 } PPGemmArgs;
 #define PP_GN_SUM_SCALE 16777216.0f /* 2^24 */
 #define PP_GN_SQ_SCALE 1048576.0f   /* 2^20 */
+/* Accuracy envelope of the statistics behind ln_stats and gn_acc (and of the two-launch GroupNorm / LayerNorm).  Every
+ * path but pp_layernorm forms the variance as E[x^2] - mean^2, which magnifies a relative error e of the sums by
+ *     kappa = (mean^2 + var) / (var + eps)          (eps in the denominator on purpose: rstd is 1 / sqrt(var + eps), and a
+ *                                                    constant population, var = 0, then has a finite kappa = mean^2 / eps)
+ * into a relative error e kappa / 2 of rstd.  With eS / eQ the guaranteed relative error of the sum / the sum of squares
+ * (u32 = 2^-24 per fp32 rounding of a running sum; derivation and the tests that hold the kernels to it:
+ * tests/norm_cases.py), the statistics term stays below the rounding of the 16-bit output (u = 2^-8 bf16, 2^-11 fp16) for
+ *     kappa <= 2 u / (eQ + 2 eS).
+ * These are worst-case figures, linear in the number of roundings; a typical tensor errs like its square root and the
+ * error beyond the envelope grows gradually (tests/test_norm_exact_gpu.py gates it there as well).
+ *                                                 eS ~ eQ                              kappa (mean / std)   bf16         fp16
+ *   pp_groupnorm_stats -> pp_groupnorm_apply      (L - 1 + Pe cg - 1) u32: 82 .. 126 u32 at the
+ *     (fp32 chunk partials, fp64 fold)            UNet's shapes (L pixels per thread, Pe cg partials)       350 (18)     43 (6.5)
+ *   gn_acc, filled by an epilogue                 R u32 for the column sums of a row block of R <= 256
+ *     (int64 fixed point, fp64 fold)              rows, + half a quantum (2^-25 / 2^-21) per add:  R = 64   680 (26)     85 (9)
+ *                                                                                                   R = 256  170 (13)     21 (4.6)
+ *   gn_acc as a contract (exact sums rounded once to the quanta)                    limited by the format:  mean / std 64, 512
+ *   row_stats_out -> ln_stats, fp32 one pass      (28 + tiles + 2) u32, tiles = C / 160:           C = 320  1300 (36)    165 (13)
+ *     (gemm / xattn_fused / ff_fused consumers)   (+)                                              C = 1280 1100 (33)    140 (12)
+ *   moments formed inside pp_tfront / the chained 84 u32 (80 roundings per lane, two shuffle adds, 1 / C and the product) (+)
+ *     pp_xattn_block from the stored row                                                           C = 320  510 (23)     64 (8)
+ *   ln_stats given exactly (rounded once to fp32) (tiles + 3) u32                                  C = 320  7700 (64*)   960 (31)
+ *   (+) these rows follow from the same model but no `edge` case sits at them: the tests pin the producer (row moments
+ *       against exact sums) and the consumers (moments given exactly, at their edge; pp_tfront at mean / std 16) separately.
+ *   pp_layernorm (two passes)                     no magnification: the mean errs by (8 NP + 6) u32 |mean|, below u std up to
+ *                                                 the format's limit (*: a standard deviation of two quanta is mean / std = 64
+ *                                                 in bf16, 512 in fp16)
+ * Inside the envelope the output is within u |y| + the fp32 terms of tests/norm_cases.py of the fp64 result.  var is
+ * clamped at 0 everywhere, so rstd never exceeds 1 / sqrt(eps): a constant population yields beta. */
 
 #define PP_TILE_AUTO 0
 #define PP_TILE_128x160 1

@@ -72,12 +72,23 @@ def _attach_combine(a, device, enable):
     last_combine["fused"] = bool(L.lib().pp_gemm_combine_fused(C.byref(a)))
 
 
+def _norm_out(out, shape, like: torch.Tensor, what: str) -> torch.Tensor:
+    """The output of the norm wrappers: a new tensor, or `out` -- a contiguous tensor (or view into a larger buffer) of the
+    result's shape and the inputs' format; the kernels take no row stride.  Elements outside it are the caller's."""
+    if out is None:
+        return torch.empty(*shape, dtype=like.dtype, device=like.device)
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.dtype != like.dtype or out.device != like.device:
+        raise L.PPError(f"{what}: `out` must be a contiguous {list(shape)} tensor of the inputs' format")
+    return out
+
+
 def groupnorm_apply_acc(x: torch.Tensor, acc: torch.Tensor, gamma, beta, eps: float, silu: bool, groups: int = 32,
-                        x2=None):
-    """GroupNorm(+SiLU) of concat(x, x2) from statistics accumulated by the producers (PPGemmArgs.gn_acc)."""
+                        x2=None, out: Optional[torch.Tensor] = None):
+    """GroupNorm(+SiLU) of concat(x, x2) from statistics accumulated by the producers (PPGemmArgs.gn_acc).
+    out: see _norm_out."""
     B, H, W, C1 = x.shape
     C2 = x2.shape[3] if x2 is not None else 0
-    y = torch.empty(B, H, W, C1 + C2, dtype=x.dtype, device=x.device)
+    y = _norm_out(out, (B, H, W, C1 + C2), x, "groupnorm_apply_acc")
     L.check(L.lib().pp_groupnorm_apply_acc(_p(x), C1, _p(x2), C2, B, H * W, groups, eps, _p(gamma), _p(beta), _p(acc),
                                            int(silu), _p(y), L.dtype_code(x.dtype), _s()), "pp_groupnorm_apply_acc")
     return y
@@ -250,14 +261,15 @@ def conv3x3_up_subpix(x: torch.Tensor, wfold: torch.Tensor, bias=None, rowvec=No
     return out
 
 
-def groupnorm(x: torch.Tensor, gamma, beta, eps: float, silu: bool, groups: int = 32, x2=None):
-    """x NHWC bf16 [B,H,W,C1] (+x2) -> NHWC bf16 [B,H,W,C1+C2]; gamma/beta fp32."""
+def groupnorm(x: torch.Tensor, gamma, beta, eps: float, silu: bool, groups: int = 32, x2=None,
+              out: Optional[torch.Tensor] = None):
+    """x NHWC bf16 [B,H,W,C1] (+x2) -> NHWC bf16 [B,H,W,C1+C2]; gamma/beta fp32.  out: see _norm_out."""
     lib = L.lib()
     B, H, W, C1 = x.shape
     C2 = x2.shape[3] if x2 is not None else 0
     Ct = C1 + C2
     ws = torch.empty(lib.pp_groupnorm_workspace_bytes(B, H * W, Ct) // 4, dtype=torch.float32, device=x.device)
-    y = torch.empty(B, H, W, Ct, dtype=x.dtype, device=x.device)
+    y = _norm_out(out, (B, H, W, Ct), x, "groupnorm")
     dt = L.dtype_code(x.dtype)
     L.check(lib.pp_groupnorm_stats(_p(x), C1, _p(x2), C2, B, H * W, groups, _p(ws), dt, _s()), "pp_groupnorm_stats")
     L.check(lib.pp_groupnorm_apply(_p(x), C1, _p(x2), C2, B, H * W, groups, eps, _p(gamma), _p(beta), _p(ws),
@@ -265,9 +277,10 @@ def groupnorm(x: torch.Tensor, gamma, beta, eps: float, silu: bool, groups: int 
     return y
 
 
-def layernorm(x: torch.Tensor, gamma, beta, eps: float = 1e-5):
+def layernorm(x: torch.Tensor, gamma, beta, eps: float = 1e-5, out: Optional[torch.Tensor] = None):
+    """x [rows, C] 16-bit contiguous -> LayerNorm over C; gamma / beta fp32.  out: see _norm_out."""
     rows, Cc = x.shape
-    y = torch.empty_like(x)
+    y = _norm_out(out, (rows, Cc), x, "layernorm")
     L.check(L.lib().pp_layernorm(_p(x), rows, Cc, _p(gamma), _p(beta), eps, _p(y), L.dtype_code(x.dtype), _s()),
             "pp_layernorm")
     return y

@@ -5,6 +5,8 @@ fp32 (on the GPU via torch, which is only the checker here).  Tolerances are sta
 2^-9 relative, fp32 accumulation order differences are ~1e-6 * sqrt(K).
 """
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -15,6 +17,9 @@ pytestmark = pytest.mark.gpu
 
 from powerpaint_amd import _lib as L  # noqa: E402
 from powerpaint_amd import ops  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import norm_cases as NC  # noqa: E402
 
 DEV = "cuda"
 
@@ -129,7 +134,7 @@ V2_TILES = [21, 31, 22, 32, 42, 23, 33, 24] + PP_TILES
 
 
 @pytest.mark.parametrize("tile", V2_TILES + [0])
-@pytest.mark.parametrize("M,N", [(520, 320), (1024, 640), (192, 1280)])
+@pytest.mark.parametrize("M,N", [(520, 320), (1024, 640), (192, 1280), (520, 200)])
 def test_gemm_row_stats(tile, M, N):
     """Producer side of the folded LayerNorm: per-row (sum, sumsq) of the STORED bf16 output, per 160-column tile."""
     K = 320
@@ -137,7 +142,8 @@ def test_gemm_row_stats(tile, M, N):
     bias, res = rnd(N, seed=3), bf(rnd(M, N, seed=4))
     out, st = ops.gemm(x, w, bias=bias, res1=res, tile=tile, row_stats=True)
     o = out.float()
-    tiles = N // 160
+    tiles = (N + 159) // 160                               # (N = 200: the last column tile holds 40 columns)
+    o = F.pad(o, (0, tiles * 160 - N))
     ref = torch.stack([o.reshape(M, tiles, 160).sum(-1), (o * o).reshape(M, tiles, 160).sum(-1)], -1)
     check(st, ref, 1e-3, 1e-5, "row moments")
 
@@ -287,8 +293,11 @@ def test_conv_epilogue_groupnorm_stats(tile, splitk):
     assert torch.equal(again1, acc1)                       # integer accumulation: order-independent
     g, b = rnd(Cout, seed=5), rnd(Cout, seed=6)
     y = ops.groupnorm_apply_acc(out, acc1, g, b, 1e-5, True)
-    ref = F.silu(F.group_norm(out.float().permute(0, 3, 1, 2), 32, g, b, 1e-5)).permute(0, 2, 3, 1)
-    check(y, ref, 2e-2, 1e-2, "groupnorm from accumulated statistics")
+    # the derived gate of tests/norm_cases.py: the accumulators are within gS / gQ of the exact sums (gate_epilogue_acc)
+    o3 = out.reshape(B, H * H, Cout)
+    _, _, gS, gQ = NC.gate_epilogue_acc(o3, H * H, 20, 0, 32)
+    ref, gate = NC.gate_groupnorm(o3, None, 32, g, b, 1e-5, True, torch.bfloat16, (0.0, 0.0, gS, gQ))
+    assert NC.worst_ratio(y.reshape(B, H * H, Cout), ref, gate) <= 1.0, "groupnorm from accumulated statistics"
 
 
 def test_gemm_epilogue_groupnorm_stats_plain():
@@ -312,18 +321,20 @@ def test_groupnorm(C1, C2, H, silu):
     g, b = rnd(C, seed=3), rnd(C, seed=4)
     eps = 1e-5 if silu else 1e-6
     out = ops.groupnorm(x1, g, b, eps, silu, x2=x2)
-    x = torch.cat([x1, x2], -1) if C2 else x1
-    ref = F.group_norm(x.float().permute(0, 3, 1, 2), 32, g, b, eps)
-    if silu:
-        ref = F.silu(ref)
-    check(out, ref.permute(0, 2, 3, 1), 2e-2, 1e-2, "groupnorm")
+    # the derived gate of tests/norm_cases.py (fp64 reference; statistics terms of gn_stats_kernel -> gn_fold)
+    f = lambda t: t.reshape(B, H * H, -1) if t is not None else None      # noqa: E731
+    ref, gate = NC.gate_groupnorm(f(x1), f(x2), 32, g, b, eps, silu, torch.bfloat16, NC.stats_eps(H * H, C, 32))
+    r = NC.worst_ratio(out.reshape(B, H * H, C), ref, gate)
+    assert r <= 1.0, f"groupnorm: error / gate {r:.3f}"
 
 
 @pytest.mark.parametrize("C", [320, 640, 1280])
 def test_layernorm(C):
     x = bf(rnd(1000, C, seed=1) * 3 + 1)
     g, b = rnd(C, seed=2), rnd(C, seed=3)
-    check(ops.layernorm(x, g, b), F.layer_norm(x.float(), (C,), g, b, 1e-5), 2e-2, 1e-2, "layernorm")
+    ref, gate = NC.gate_layernorm(x, g, b, 1e-5, torch.bfloat16)           # the derived gate of tests/norm_cases.py
+    r = NC.worst_ratio(ops.layernorm(x, g, b), ref, gate)
+    assert r <= 1.0, f"layernorm: error / gate {r:.3f}"
 
 
 # ------------------------------------------------------------------------------------------------ attention
