@@ -272,6 +272,20 @@ typedef struct PPGemmArgs {
  * Inside the envelope the output is within u |y| + the fp32 terms of tests/norm_cases.py of the fp64 result.  var is
  * clamped at 0 everywhere, so rstd never exceeds 1 / sqrt(eps): a constant population yields beta. */
 
+/* Order and rounding of the GEMM / conv epilogue -- the same on every path a request can take (the single-pass staged and
+ * register-staged epilogues, the lean, full and statistics split-K combines, the in-kernel combine, the halo-tile kernel):
+ *     acc = sum_k X[m][k] W[n][k]                                     fp32 (MFMA); split-K: fp32 slabs added in slab order
+ *     v   = (acc [folded-LayerNorm correction] + bias[n] + rowvec[m / rows_per_batch][n]) * scale
+ *     v   = v + res1[m or m - res1_wrap_rows][n] + res2[m][n]         (the residuals are NOT scaled)
+ *     v   = act(v)                                                    PP_ACT_SILU | the GEGLU product | the group softmax
+ *     out = v rounded ONCE to the 16-bit format, to nearest even      (no rounding with out_f32)
+ * every operation in fp32; nothing is rounded to 16 bits before the store (the row moments and GroupNorm accumulators are
+ * formed from the values AS STORED).  With integer data whose partial sums stay below 2^24 the result is therefore exact
+ * under any tile form, K order or split count, and a sum that lies halfway between two 16-bit values goes to the even one:
+ * tests/test_gemm_exact_gpu.py holds every tile form to bit equality on such data, on sentinel-guarded outputs with row
+ * strides ldo > N, and to |out - ref| <= u |ref| + (K + splits + 5) 2^-24 sum|terms| on random data (tests/gemm_cases.py).
+ * Nothing outside rows [0, M) x columns [0, N) of `out` (ldo may exceed N; likewise out_vt / vt_ld), and nothing behind
+ * pp_gemm_workspace_bytes() of the workspace, is written; pads of x* / res* / w may hold any finite values. */
 #define PP_TILE_AUTO 0
 #define PP_TILE_128x160 1
 #define PP_TILE_64x160 2

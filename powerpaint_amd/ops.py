@@ -82,6 +82,64 @@ def _norm_out(out, shape, like: torch.Tensor, what: str) -> torch.Tensor:
     return out
 
 
+def _view2d(t, rows: int, cols: int, dtype, like: torch.Tensor, what: str) -> torch.Tensor:
+    """A caller-owned [rows, cols] output: any 2-D view with unit column stride (a window of a larger buffer); its row stride
+    is the leading dimension the kernel gets.  Elements outside the view are the caller's."""
+    if (t.dim() != 2 or tuple(t.shape) != (rows, cols) or t.stride(1) != 1 or t.stride(0) < cols or t.dtype != dtype
+            or t.device != like.device):
+        raise L.PPError(f"{what}: must be a [{rows}, {cols}] row-major view (unit column stride) of the output format")
+    return t
+
+
+def _nhwc_view(t, shape, like: torch.Tensor, what: str) -> torch.Tensor:
+    """A caller-owned NHWC conv output [B, H, W, C]: dense pixels whose channel stride (the kernel's ldo) is the view's pixel
+    stride, i.e. a column window of a [B*H*W, ldo] buffer."""
+    B, H, W, Cc = shape
+    bad = t.dim() != 4 or tuple(t.shape) != tuple(shape) or t.stride(3) != 1 or t.dtype != like.dtype or t.device != like.device
+    if not bad:                      # (the stride of a dimension of size 1 is arbitrary: the pixel stride comes from the first that counts)
+        ld = t.stride(2) if W > 1 else (t.stride(1) if H > 1 else (t.stride(0) if B > 1 else Cc))
+        bad = (ld < Cc or (W > 1 and H > 1 and t.stride(1) != W * ld) or (B > 1 and H * W > 1 and t.stride(0) != H * W * ld))
+    if bad:
+        raise L.PPError(f"{what}: must be a {list(shape)} NHWC view of the inputs' format with dense pixels (channel stride = ld)")
+    return t
+
+
+def _nhwc_ld(t, shape) -> int:
+    B, H, W, Cc = shape
+    return t.stride(2) if W > 1 else (t.stride(1) if H > 1 else (t.stride(0) if B > 1 else Cc))
+
+
+def _res_ld(t, shape, like: torch.Tensor, what: str, rows_only: bool = False) -> int:
+    """Pixel stride (ldres) of a conv residual: an NHWC tensor of `shape` (the request's output; rows_only: any number of
+    leading rows, as res1 with res1_wrap holds) of the inputs' format with dense pixels, checked as `out` is."""
+    if t is None:
+        return shape[3]
+    if t.dim() == 2:                 # rows x channels: the same tensor, flattened
+        if t.shape[1] != shape[3] or t.stride(1) != 1 or t.dtype != like.dtype or t.device != like.device or \
+                (not rows_only and t.shape[0] != shape[0] * shape[1] * shape[2]):
+            raise L.PPError(f"{what}: must be [{shape[0] * shape[1] * shape[2]}, {shape[3]}] rows of the inputs' format")
+        return t.stride(0) if t.shape[0] > 1 else shape[3]
+    if rows_only:
+        shape = tuple(t.shape[:3]) + (shape[3],) if t.dim() == 4 else shape
+    _nhwc_view(t, shape, like, what)
+    return _nhwc_ld(t, shape)
+
+
+last_workspace = {"bytes": 0}     # what pp_gemm_workspace_bytes() asked for the most recent gemm / conv call
+
+
+def _workspace(lib, a, device, workspace):
+    """The split-K workspace of request `a`: a new buffer, or the caller's fp32 tensor (contiguous, large enough)."""
+    ws = lib.pp_gemm_workspace_bytes(C.byref(a))
+    last_workspace["bytes"] = ws
+    if workspace is None:
+        return torch.empty(max(ws, 4) // 4, dtype=torch.float32, device=device) if ws else None
+    if (workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != device
+            or workspace.numel() * 4 < ws):
+        raise L.PPError(f"`workspace` must be a contiguous fp32 tensor of at least {ws} bytes on the inputs' device")
+    return workspace if ws else None
+
+
 def groupnorm_apply_acc(x: torch.Tensor, acc: torch.Tensor, gamma, beta, eps: float, silu: bool, groups: int = 32,
                         x2=None, out: Optional[torch.Tensor] = None):
     """GroupNorm(+SiLU) of concat(x, x2) from statistics accumulated by the producers (PPGemmArgs.gn_acc).
@@ -97,9 +155,14 @@ def groupnorm_apply_acc(x: torch.Tensor, acc: torch.Tensor, gamma, beta, eps: fl
 def gemm(x: torch.Tensor, w: torch.Tensor, bias=None, x2=None, res1=None, res2=None, scale: float = 1.0, act: int = 0,
          rowvec=None, rows_per_batch: int = 0, out_f32: bool = False, vt_col0: int = 0, tile: int = 0,
          splitk: int = 0, row_stats: bool = False, ln_stats=None, ln_colsum=None, ln_dim: int = 0,
-         ln_eps: float = 1e-5, gn=None, res1_wrap: int = 0, fuse_combine: bool = False, out=None):
+         ln_eps: float = 1e-5, gn=None, res1_wrap: int = 0, fuse_combine: bool = False, out=None, vt=None, stats=None,
+         workspace=None):
     """x [M,K1] (+ x2 [M,K2]) bf16, w [N,K1+K2] bf16 -> out [M,N] (or [M,N/2] for GEGLU; (out, vt) when vt_col0).
-    out: write into this contiguous tensor instead of a new one; it may BE res1 (in place, include/pp_hip.h "Aliasing").
+    out: write into this tensor instead of a new one -- any [M, n_out] view with unit column stride, its row stride is the
+    ldo of the launch (a window of a larger buffer; what lies outside it is the caller's); it may BE res1 (in place,
+    include/pp_hip.h "Aliasing").  vt: the caller's V^T output, a [nb, N - vt_col0, rows_per_batch] window of a contiguous
+    [nb, N - vt_col0, vt_ld] buffer; stats: the caller's row moments, contiguous [M, ceil(N/160), 2] fp32 (the ABI has no
+    stride for them); workspace: the caller's fp32 split-K workspace.  A mismatch of shape, format or device raises PPError.
     w [nb, N, K]: one matrix per batch item of rows_per_batch rows (PPGemmArgs.w_batch_stride); with act =
     L.PP_ACT_SOFTMAX80 bias / ln_colsum may then be [nb, N] as well (vec_batch_stride).
     res1_wrap: res1 holds that many rows only, row m adds res1[m mod res1_wrap] (PPGemmArgs.res1_wrap_rows).
@@ -110,12 +173,14 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias=None, x2=None, res1=None, res2=N
     K2 = x2.shape[1] if x2 is not None else 0
     N = w.shape[-2]
     n_out = N // 2 if act == L.PP_ACT_GEGLU else (vt_col0 if vt_col0 else N)
+    odt = torch.float32 if out_f32 else x.dtype
     if out is None:
-        out = torch.empty(M, n_out, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
-    elif tuple(out.shape) != (M, n_out) or not out.is_contiguous() or out.dtype != (torch.float32 if out_f32 else x.dtype):
-        raise L.PPError(f"gemm: `out` must be a contiguous [{M}, {n_out}] tensor of the output format")
+        out = torch.empty(M, n_out, dtype=odt, device=x.device)
+    else:
+        _view2d(out, M, n_out, odt, x, "gemm: `out`")
     a = L.gemm_args(L.dtype_code(x.dtype), M, N, K1, _p(x), _p(w), _p(out), x2=_p(x2), K2=K2, ldx=x.stride(0),
-                    ldx2=x2.stride(0) if x2 is not None else 0, ldo=n_out, ldres1=res1.stride(0) if res1 is not None else 0,
+                    ldx2=x2.stride(0) if x2 is not None else 0, ldo=out.stride(0) if M > 1 else n_out,
+                    ldres1=res1.stride(0) if res1 is not None else 0,
                     ldres2=res2.stride(0) if res2 is not None else 0, rows_per_batch=rows_per_batch, scale=scale)
     if w.dim() == 3:
         a.w_batch_stride = w.stride(0)
@@ -124,21 +189,32 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias=None, x2=None, res1=None, res2=N
     a.bias, a.rowvec, a.res1, a.res2 = _p(bias), _p(rowvec), _p(res1), _p(res2)
     a.ld_rowvec = rowvec.stride(0) if (rowvec is not None and rowvec.dim() == 2 and rowvec.shape[0] > 1) else 0
     a.res1_wrap_rows, a.act, a.out_f32 = res1_wrap, act, int(out_f32)
-    vt = None
     if vt_col0:
-        nb = M // rows_per_batch
-        vt = torch.zeros(nb, N - vt_col0, rows_per_batch, dtype=x.dtype, device=x.device)
-        a.out_vt, a.vt_col0, a.vt_ld = _p(vt), vt_col0, rows_per_batch
+        nb, ncols = M // rows_per_batch, N - vt_col0
+        if vt is None:
+            vt = torch.zeros(nb, ncols, rows_per_batch, dtype=x.dtype, device=x.device)
+        elif (vt.dim() != 3 or tuple(vt.shape) != (nb, ncols, rows_per_batch) or vt.stride(2) != 1 or vt.dtype != x.dtype
+              or vt.device != x.device or vt.stride(1) < rows_per_batch or vt.stride(0) != ncols * vt.stride(1)):
+            raise L.PPError(f"gemm: `vt` must be a [{nb}, {ncols}, {rows_per_batch}] window of a contiguous [nb, cols, vt_ld] "
+                            "buffer of the inputs' format")
+        a.out_vt, a.vt_col0, a.vt_ld = _p(vt), vt_col0, vt.stride(1)
+    elif vt is not None:
+        raise L.PPError("gemm: `vt` without vt_col0")
     a.tile, a.splitk = tile, splitk
     _set_gn(a, gn, rows_per_batch)
-    stats = None
     if row_stats:
-        stats = torch.zeros(M, (N + 159) // 160, 2, dtype=torch.float32, device=x.device)
+        tn = (N + 159) // 160
+        if stats is None:
+            stats = torch.zeros(M, tn, 2, dtype=torch.float32, device=x.device)
+        elif (tuple(stats.shape) != (M, tn, 2) or not stats.is_contiguous() or stats.dtype != torch.float32
+              or stats.device != x.device):
+            raise L.PPError(f"gemm: `stats` must be a contiguous [{M}, {tn}, 2] fp32 tensor")
         a.row_stats_out = _p(stats)
+    elif stats is not None:
+        raise L.PPError("gemm: `stats` without row_stats")
     if ln_stats is not None:
         a.ln_stats, a.ln_colsum, a.ln_tiles, a.ln_dim, a.ln_eps = _p(ln_stats), _p(ln_colsum), ln_stats.shape[1], ln_dim, ln_eps
-    ws = lib.pp_gemm_workspace_bytes(C.byref(a))
-    wsb = torch.empty(max(ws, 4) // 4, dtype=torch.float32, device=x.device) if ws else None
+    wsb = _workspace(lib, a, x.device, workspace)
     a.workspace = _p(wsb)
     _attach_combine(a, x.device, fuse_combine)
     L.check(lib.pp_gemm_bf16(C.byref(a), _s()), "pp_gemm_bf16")
@@ -179,21 +255,31 @@ def _conv_request(x, cout, stride, up, x2, x3, x4) -> L.PPGemmArgs:
 def conv3x3(x: torch.Tensor, w: torch.Tensor, bias=None, stride: int = 1, up: bool = False, x2=None, rowvec=None,
             res1=None, res2=None, scale: float = 1.0, tile: int = 0, splitk: int = 0, gn=None, x3=None, x4=None,
             gn_in=None, gn_next=None, dup: bool = False, gn_dup_mask: int = 0, res1_wrap: int = 0,
-            fuse_combine: bool = False):
+            fuse_combine: bool = False, out=None, workspace=None, ynext=None):
     """x NHWC bf16 [B,H,W,C1] (+x2 [B,H,W,C2]); w bf16 [Cout, 9*(C1+C2)] (k = (ky*3+kx)*C + c) -> NHWC bf16.
     dup: every output row is stored twice -> out [2B, ...] (PPGemmArgs.out_dup_rows: the CFG twin prefix); gn_dup_mask:
     which of the `gn` subscriptions hold [2B][groups][2] accumulators that receive both halves' sums.
     gn_in = (acc int64 [B][groups][2], gamma_beta fp32 [C1+C2][2], groups, eps): GroupNorm + SiLU of concat(x, x2) fused
     into the loader (x, x2 are then the RAW tensors); raises PPError(PP_ERR_UNSUPPORTED) where conv_gn_supported() is
     False.  gn_next = (gamma, beta, eps, silu, sub): the GroupNorm that consumes the OUTPUT (its statistics subscription
-    is gn[sub]) applied by the split-K combine (PPGemmArgs.gn_next_*) -> returns (out, normalised)."""
+    is gn[sub]) applied by the split-K combine (PPGemmArgs.gn_next_*) -> returns (out, normalised).
+    out: the caller's NHWC output, dense pixels with the channel stride taken from the view (ldo; see _nhwc_view); res1 / res2
+    likewise carry their own pixel stride and are checked the same way.  workspace: the caller's fp32 split-K workspace.
+    ynext: the caller's gn_next output, a contiguous tensor of the output's shape (the ABI has no stride for it; _norm_out)."""
     lib = L.lib()
     B, C1, C2, cout = x.shape[0], x.shape[3], (x2.shape[3] if x2 is not None else 0), w.shape[0]
     a = _conv_request(x, cout, stride, up, x2, x3, x4)
     ho, wo = a.hout, a.wout
-    out = torch.empty(2 * B if dup else B, ho, wo, cout, dtype=x.dtype, device=x.device)
+    oshape = (2 * B if dup else B, ho, wo, cout)
+    if out is None:
+        out = torch.empty(*oshape, dtype=x.dtype, device=x.device)
+    else:
+        a.ldo = _nhwc_ld(_nhwc_view(out, oshape, x, "conv3x3: `out`"), oshape)
     a.w, a.out, a.scale = _p(w), _p(out), scale
     a.bias, a.rowvec, a.res1, a.res2 = _p(bias), _p(rowvec), _p(res1), _p(res2)
+    rshape = (B, ho, wo, cout)
+    a.ldres1 = _res_ld(res1, rshape, x, "conv3x3: `res1`", rows_only=res1_wrap > 0)
+    a.ldres2 = _res_ld(res2, rshape, x, "conv3x3: `res2`")
     if rowvec is not None and rowvec.dim() == 2 and rowvec.shape[0] > 1:
         a.ld_rowvec = rowvec.stride(0)
     a.res1_wrap_rows = res1_wrap
@@ -203,18 +289,18 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, bias=None, stride: int = 1, up: bo
             a.gn_dup_batch, a.gn_dup_mask = B, gn_dup_mask
     a.tile, a.splitk = tile, splitk
     _set_gn(a, gn, ho * wo)
-    ynext = None
+    if gn_next is None and ynext is not None:
+        raise L.PPError("conv3x3: `ynext` without gn_next")
     if gn_next is not None:
         g_, b_, eps_, silu_, sub_ = gn_next
-        ynext = torch.empty_like(out)
+        ynext = _norm_out(ynext, oshape, x, "conv3x3: `ynext`")
         a.gn_next_out, a.gn_next_gamma, a.gn_next_beta = _p(ynext), _p(g_), _p(b_)
         a.gn_next_eps, a.gn_next_silu, a.gn_next_sub = eps_, int(silu_), sub_
     if gn_in is not None:
         acc, gb, groups, eps = gn_in
         assert gb.dtype == torch.float32 and gb.shape == (C1 + C2, 2) and gb.is_contiguous()
         a.gn_in_acc, a.gn_in_gb, a.gn_in_groups, a.gn_in_silu, a.gn_in_eps = _p(acc), _p(gb), groups, 1, eps
-    ws = lib.pp_gemm_workspace_bytes(C.byref(a))
-    wsb = torch.empty(max(ws, 4) // 4, dtype=torch.float32, device=x.device) if ws else None
+    wsb = _workspace(lib, a, x.device, workspace)
     a.workspace = _p(wsb)
     if gn_next is not None and not lib.pp_gemm_gn_next_ok(C.byref(a), a.gn_next_sub):
         raise L.PPError("pp_gemm_gn_next_ok() = 0 for this launch (PP_ERR_UNSUPPORTED)")
@@ -240,23 +326,30 @@ def upconv_subpix_supported(x: torch.Tensor, cout: int) -> int:
 
 
 def conv3x3_up_subpix(x: torch.Tensor, wfold: torch.Tensor, bias=None, rowvec=None, res1=None, res2=None, scale: float = 1.0,
-                      tile: int = 0, splitk: int = 0, gn=None):
+                      tile: int = 0, splitk: int = 0, gn=None, out=None, workspace=None):
     """`nearest 2x -> conv3x3` of x NHWC [B,H,W,C] in its sub-pixel form (PPGemmArgs.subpix) on wfold = upconv_fold(w)
     -> NHWC [B,2H,2W,Cout]; res1 / res2 have the output's shape, `gn` subscriptions describe the output tensor.  Raises
     PPError(PP_ERR_UNSUPPORTED) where upconv_subpix_supported() is 0 or a split is forced; conv3x3(up=True) is the other,
-    nine-tap request and is not routed here."""
+    nine-tap request and is not routed here.  out / workspace: as conv3x3 takes them (the form runs in one pass: a
+    workspace is checked and never used)."""
     B, H, W, C1 = x.shape
     cout = wfold.shape[1]
     assert tuple(wfold.shape) == (4, cout, 4 * C1) and wfold.is_contiguous()
     a = L.conv3x3_args(L.dtype_code(x.dtype), B, H, W, C1, cout, _p(x))
     a.K, a.subpix = 4 * C1, 1
-    out = torch.empty(B, 2 * H, 2 * W, cout, dtype=x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty(B, 2 * H, 2 * W, cout, dtype=x.dtype, device=x.device)
+    else:
+        a.ldo = _nhwc_ld(_nhwc_view(out, (B, 2 * H, 2 * W, cout), x, "conv3x3_up_subpix: `out`"), (B, 2 * H, 2 * W, cout))
     a.w, a.out, a.scale = _p(wfold), _p(out), scale
     a.bias, a.rowvec, a.res1, a.res2 = _p(bias), _p(rowvec), _p(res1), _p(res2)
+    a.ldres1 = _res_ld(res1, (B, 2 * H, 2 * W, cout), x, "conv3x3_up_subpix: `res1`")
+    a.ldres2 = _res_ld(res2, (B, 2 * H, 2 * W, cout), x, "conv3x3_up_subpix: `res2`")
     if rowvec is not None and rowvec.dim() == 2 and rowvec.shape[0] > 1:
         a.ld_rowvec = rowvec.stride(0)
     a.tile, a.splitk = tile, splitk
     _set_gn(a, gn, H * W)
+    a.workspace = _p(_workspace(L.lib(), a, x.device, workspace))
     L.check(L.lib().pp_gemm_bf16(C.byref(a), _s()), "pp_gemm_bf16(sub-pixel upsampling conv)")
     return out
 

@@ -24,6 +24,7 @@ from powerpaint_amd import schedulers as PS  # noqa: E402
 
 from test_models_gpu import TINY, close, gen  # noqa: E402
 from test_ops_gpu import check, conv_ref, rnd  # noqa: E402
+import gemm_cases as GC  # noqa: E402
 
 DEV = "cuda"
 H16 = torch.float16
@@ -50,6 +51,9 @@ def test_gemm_fp16(tile):
     out = ops.gemm(x, w, bias=bias, res1=res, tile=tile, splitk=1 if tile else 0)
     assert out.dtype == H16
     check(out, x.float() @ w.float().t() + bias + res.float(), 5e-3, 2.5e-3, f"fp16 gemm tile{tile}")
+    GC.derived_check(out, x.double() @ w.double().t() + bias + res.double(),       # (and the derived gate: tests/gemm_cases.py)
+                     x.double().abs() @ w.double().abs().t() + bias.abs() + res.double().abs(), K, 1 if tile else 8,
+                     f"fp16 gemm tile{tile}")
     # the same bits through the bf16 path differ (the kernels really interpret the storage format)
     assert not torch.equal(out.view(torch.int16), ops.gemm(x.view(torch.bfloat16), w.view(torch.bfloat16), tile=tile,
                                                            splitk=1 if tile else 0).view(torch.int16))
@@ -64,6 +68,8 @@ def test_conv3x3_fp16(tile, splitk, stride, up):
     bias = rnd(Cout, seed=3)
     out = ops.conv3x3(x, w, bias, stride=stride, up=up, tile=tile, splitk=splitk)
     check(out, conv_ref(x, w, bias, stride, up), 5e-3, 2.5e-3, f"fp16 conv s{stride} up{up} tile{tile}")
+    GC.derived_check(out, GC.conv64(x, w, stride, up) + bias, GC.conv64(x.abs(), w.abs(), stride, up) + bias.abs(), 9 * Cin,
+                     splitk or 8, f"fp16 conv s{stride} up{up} tile{tile}")
 
 
 def test_geglu_folded_layernorm_and_gn_stats_fp16():

@@ -20,6 +20,7 @@ from powerpaint_amd import ops  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import norm_cases as NC  # noqa: E402
+import gemm_cases as GC  # noqa: E402
 
 DEV = "cuda"
 
@@ -46,7 +47,10 @@ def check(out, ref, atol, rtol, what=""):
 
 # ------------------------------------------------------------------------------------------------ GEMM
 PP_TILES = [53, 44, 54]      # ping-pong 8-wave tiles (256x160x3, 128x160x3, 128x160x4)
-ALL_TILES = [1, 2, 3, 21, 31, 22, 32, 42, 23, 33, 24] + PP_TILES
+ALL_TILES = [1, 2, 3, 21, 31, 22, 32, 42, 62, 23, 33, 24] + PP_TILES
+# test_gemm_plain, test_gemm_splitk, test_conv3x3 and test_conv3x3_with_1x1_tail (and their fp16 twins) hold the derived gate
+# of tests/gemm_cases.py (probe R-: u |ref| + (K + splits + 5) 2^-24 A against the fp64 result) AND the check() tolerance they
+# always had; tests/test_gemm_probes.py shows element by element where the derived gate is the tighter of the two.
 
 
 @pytest.mark.parametrize("tile", ALL_TILES)
@@ -58,6 +62,8 @@ def test_gemm_plain(tile, M, N, K):
     out = ops.gemm(x, w, bias=bias, res1=res, tile=tile, splitk=1)
     ref = x.float() @ w.float().t() + bias + res.float()
     check(out, ref, 2e-2, 1e-2, f"gemm tile{tile}")
+    GC.derived_check(out, x.double() @ w.double().t() + bias + res.double(),
+                     x.double().abs() @ w.double().abs().t() + bias.abs() + res.double().abs(), K, 1, f"gemm tile{tile} {M}x{N}x{K}")
 
 
 @pytest.mark.parametrize("tile", [33, 31] + PP_TILES)
@@ -96,6 +102,9 @@ def test_gemm_splitk(splitk, tile):
     out = ops.gemm(x, w, bias=bias, res1=res, res2=res, scale=0.5, tile=tile, splitk=splitk)
     ref = (x.float() @ w.float().t() + bias) * 0.5 + 2 * res.float()
     check(out, ref, 2e-2, 1e-2, "gemm splitk")
+    GC.derived_check(out, (x.double() @ w.double().t() + bias) * 0.5 + 2 * res.double(),
+                     (x.double().abs() @ w.double().abs().t() + bias.abs()) * 0.5 + 2 * res.double().abs(), K, splitk,
+                     f"gemm splitk{splitk} tile{tile}")
 
 
 def test_gemm_concat_and_rowvec():
@@ -210,6 +219,8 @@ def test_conv3x3(tile, stride, up):
     bias = rnd(Cout, seed=3)
     out = ops.conv3x3(x, w, bias, stride=stride, up=up, tile=tile, splitk=1)
     check(out, conv_ref(x, w, bias, stride, up), 2e-2, 1e-2, f"conv s{stride} up{up} tile{tile}")
+    GC.derived_check(out, GC.conv64(x, w, stride, up) + bias, GC.conv64(x.abs(), w.abs(), stride, up) + bias.abs(), 9 * Cin, 1,
+                     f"conv s{stride} up{up} tile{tile}")
 
 
 def test_conv3x3_concat_temb_res_splitk():
@@ -253,6 +264,9 @@ def test_conv3x3_with_1x1_tail(tile, splitk, two):
     xin = torch.cat([x, sk], -1) if two else x
     ref = conv_ref(h, w2, bias) + xin.float() @ wsc.float().t()
     check(out, ref, 3e-2, 1e-2, "conv + 1x1 tail")
+    r64 = GC.conv64(h, w2) + xin.double() @ wsc.double().t() + bias
+    a64 = GC.conv64(h.abs(), w2.abs()) + xin.double().abs() @ wsc.double().abs().t() + bias.abs()
+    GC.derived_check(out, r64, a64, 9 * Ch + cin, splitk or 8, f"conv + 1x1 tail tile{tile} splitk{splitk}")
 
 
 # ------------------------------------------------------------------------------------------------ GroupNorm statistics in the epilogue
