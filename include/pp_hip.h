@@ -29,7 +29,7 @@ extern "C" {
 #define PP_ERR_LAUNCH (-3)       /* hipLaunchKernel / hipFuncSetAttribute failed                  */
 #define PP_ERR_WORKSPACE (-4)    /* workspace pointer null or too small                           */
 
-#define PP_ABI_VERSION 28
+#define PP_ABI_VERSION 29
 /* 16-bit storage format of activations and matrix weights ("dtype" arguments; the same codes pp_nchw_to_nhwc uses for
  * its source): bf16 or fp16 -- the reference's default is fp16 (/root/reference/app.py:548,559).  MFMA accumulation,
  * norm statistics, softmax, biases and latents are fp32 with either. */
@@ -58,7 +58,15 @@ const char* pp_last_error(void);
  *                  -> channel-concat of two tensors without materialising it (up-block skip concat,
  *                  unet_2d_blocks.py:2589,2732).  K = c1 + c2.
  *   PP_X_CONV3X3 : X is the im2col view of an NHWC tensor [batch][hin][win][c1(+c2)]; pad 1; k = (ky*3+kx)*C + c;
- *                  `stride` 1|2 (Downsample2D); `up`=1 fuses a nearest-2x upsample of the input (Upsample2D);
+ *                  `stride` 1|2 (Downsample2D: hout = (hin - 1) / stride + 1, odd hin included); `up`=1 fuses the nearest
+ *                  upsample of the input (Upsample2D).  (ABI v29) With up = 1 and stride 1 the virtual input is
+ *                  F.interpolate(x, size=(hout, wout), mode="nearest") for hout in {2 hin - 1, 2 hin} and wout in
+ *                  {2 win - 1, 2 win}, the axes independent: virtual pixel (y, x) is source pixel (y >> 1, x >> 1) --
+ *                  floor(i hin / (2 hin - 1)) = i >> 1 for every i <= 2 hin - 2 -- and the conv's zero padding begins at
+ *                  hout x wout, not at 2 hin x 2 win (the upsamplers of a UNet whose latent is no multiple of
+ *                  2^levels resize to the next skip tensor's size).  Any other hout / wout: PP_ERR_BAD_ARG.  The
+ *                  tap-major kernels take every such request; the halo-tile loop (pp_conv_gn_supported) and the sub-pixel
+ *                  form (pp_upconv_subpix_supported_to) take the exact 2x target only.
  *                  M = batch*hout*wout, K = 9*(c1+c2).  c1, c2 multiples of 64.
  * W operand: bf16 [N][K] row-major (conv weights pre-permuted to [Cout][ky][kx][Cin] by the host).
  * Epilogue:  v = (acc + bias[n] + rowvec[m / rows_per_batch][n]) * scale + res1[m][n] + res2[m][n]
@@ -318,6 +326,10 @@ int pp_conv_gn_preferred(const PPGemmArgs* args);
  * the widths from which plain convs run on the halo-tile loop at all (below, the 9-tap request stays on the tap-major
  * weight stream at 16/9 fewer weight bytes). */
 int pp_upconv_subpix_supported(int batch, int h, int w, int cin, int cout, int dtype);
+/* (ABI v29) The same question for an upsampler that resizes the h x w source to hout x wout (PP_X_CONV3X3, up = 1): the
+ * sub-pixel form writes whole 2x2 output quads, so a cropped target (2 h - 1 rows or 2 w - 1 columns) answers 0 and the
+ * caller keeps the nine-tap `up` request; the exact target answers what pp_upconv_subpix_supported does. */
+int pp_upconv_subpix_supported_to(int batch, int h, int w, int hout, int wout, int cin, int cout, int dtype);
 /* (ABI v28) The folded weights of the sub-pixel form: w = the packed conv weight [cout][3][3][cin] (16-bit `dtype`) ->
  * out [4][cout][2][2][cin], out[2a + b][n][dy][dx][c] = sum over ky in R[a][dy], kx in R[b][dx] of w[n][ky][kx][c] with
  * R[0] = ({0}, {1, 2}), R[1] = ({0, 1}, {2}); summed in fp32 in the order ky outer, kx inner, rounded once (to nearest even).
@@ -687,6 +699,8 @@ int pp_embed_splice(const void* table, const void* ext, const int32_t* src_row, 
  * The VAE mid-block attention (diffusers AutoencoderKL: one head of dim 512 over H*W tokens -- the call sites are
  * /root/reference/powerpaint/pipelines/pipeline_PowerPaint.py:657-669,1051) is two pp_gemm_bf16 launches around this
  * kernel; pp_attention_fwd covers the UNet's head dims only.  lds / ldp: row strides in elements (multiples of 4).
+ * (ABI v29) Columns [n, ldp) of every row of p are WRITTEN as zeros: a caller whose second GEMM needs K % 64 == 0 pads ldp
+ * to it and multiplies the pad columns with zero-padded V^T columns (pp_transpose_v), whatever the buffer held before.
  */
 int pp_softmax_rows(const float* s, long long lds, int rows, int n, float scale, void* p, long long ldp, int dtype,
                     void* stream);

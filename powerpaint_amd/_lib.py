@@ -16,7 +16,7 @@ PP_ACT_NONE, PP_ACT_GEGLU, PP_ACT_SILU, PP_ACT_SOFTMAX80 = 0, 1, 2, 3
 PP_TILE_AUTO, PP_TILE_128x160, PP_TILE_64x160, PP_TILE_256x160 = 0, 1, 2, 3
 PP_DT_F32, PP_DT_BF16, PP_DT_F16 = 0, 1, 2      # dtype codes of the C ABI (include/pp_hip.h)
 PP_ATTN_AUTO, PP_ATTN_PHASED, PP_ATTN_PIPE_Q32, PP_ATTN_PIPE_Q64, PP_ATTN_PIPE_LOG2 = 0, 1, 2, 3, 4   # pp_attention_fwd_variant
-ABI_VERSION = 28                                  # PP_ABI_VERSION of include/pp_hip.h this binding was written against
+ABI_VERSION = 29                                  # PP_ABI_VERSION of include/pp_hip.h this binding was written against
 PP_ERR = {0: "PP_OK", -1: "PP_ERR_BAD_ARG", -2: "PP_ERR_UNSUPPORTED", -3: "PP_ERR_LAUNCH", -4: "PP_ERR_WORKSPACE"}
 
 vp, i32, f32, sz = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
@@ -68,11 +68,17 @@ def gemm_args(dtype: int, M: int, N: int, K: int, x, w, out, x2=None, K2: int = 
 
 
 def conv3x3_args(dtype: int, B: int, H: int, W: int, c1: int, cout: int, x, x2=None, c2: int = 0, x3=None, c3: int = 0,
-                 x4=None, c4: int = 0, stride: int = 1, up: bool = False, w=None, out=None, scale: float = 1.0) -> PPGemmArgs:
+                 x4=None, c4: int = 0, stride: int = 1, up: bool = False, w=None, out=None, scale: float = 1.0,
+                 up_size=None) -> PPGemmArgs:
     """The geometry of a PP_X_CONV3X3 request: conv3x3 (padding 1) over concat(x, x2) NHWC [B][H][W][c1 + c2], after a nearest
     2x upsample if `up`, + a 1x1 tail over concat(x3, x4) at the output pixel -> NHWC [B][hout][wout][cout] (a.hout / a.wout:
-    a caller that sizes `out` from them sets a.out afterwards)."""
+    a caller that sizes `out` from them sets a.out afterwards).  up_size = (h, w) with `up`: the nearest resize goes to that
+    size instead, 2 H - 1 or 2 H rows and 2 W - 1 or 2 W columns (F.interpolate(size=...) of Upsample2D)."""
     hv, wv = (2 * H, 2 * W) if up else (H, W)
+    if up_size is not None:
+        if not up or stride != 1 or up_size[0] not in (2 * H - 1, 2 * H) or up_size[1] not in (2 * W - 1, 2 * W):
+            raise ValueError(f"up_size {tuple(up_size)} is no nearest-resize target of a {H}x{W} source")
+        hv, wv = up_size
     ho, wo = (hv - 1) // stride + 1, (wv - 1) // stride + 1
     a = PPGemmArgs()
     a.dtype = dtype
@@ -118,6 +124,7 @@ SIGNATURES = {
     "pp_conv_gn_preferred": (C.c_int, [C.POINTER(PPGemmArgs)]),
     "pp_gemm_gn_next_ok": (C.c_int, [C.POINTER(PPGemmArgs), C.c_int]),
     "pp_upconv_subpix_supported": (C.c_int, [C.c_int] * 6),
+    "pp_upconv_subpix_supported_to": (C.c_int, [C.c_int] * 8),
     "pp_upconv_fold": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "pp_gemm_combine_ctr_bytes": (sz, [C.POINTER(PPGemmArgs)]),
     "pp_gemm_combine_fused": (C.c_int, [C.POINTER(PPGemmArgs)]),

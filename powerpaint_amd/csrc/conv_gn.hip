@@ -1015,6 +1015,13 @@ extern "C" int pp_upconv_subpix_supported(int batch, int h, int w, int cin, int 
   return w >= 16 ? 2 : 1;
 }
 
+// the same for an upsampler that resizes to hout x wout: the scattered epilogue writes whole 2x2 quads, a cropped target is not
+// this form's
+extern "C" int pp_upconv_subpix_supported_to(int batch, int h, int w, int hout, int wout, int cin, int cout, int dtype) {
+  if (hout != 2 * h || wout != 2 * w) return 0;
+  return pp_upconv_subpix_supported(batch, h, w, cin, cout, dtype);
+}
+
 // Where the fused launch beats pp_groupnorm_apply_acc + plain conv inside the UNet step (same-box A/Bs of the headline
 // benchmark and per-launch timings, profiles/r04_conv_gn_variants.txt): the normalisation is ~600 wave cycles per strip
 // that no placement hides behind the matrix pipe, repeated per N tile (N / 160) and per halo row ((BM + 2 W) / BM):

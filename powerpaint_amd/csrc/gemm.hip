@@ -204,8 +204,10 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) pp_gemm_kernel(const PPGemmArg
     tap = kt_begin / d.ctiles;
     cc = (kt_begin - tap * d.ctiles) * 64;
   }
-  const int hv = a.up ? a.hin * 2 : a.hin;
-  const int wv = a.up ? a.win * 2 : a.win;
+  // (ABI v29) a.up, stride 1: the virtual input is the nearest resize of the source to hout x wout (2 hin or 2 hin - 1 rows),
+  // read at source index i >> 1; the conv's zero padding begins at hout x wout
+  const int hv = a.up ? (a.stride == 1 ? a.hout : a.hin * 2) : a.hin;
+  const int wv = a.up ? (a.stride == 1 ? a.wout : a.win * 2) : a.win;
 
   u32x4_t xr[XP], wr[WP];
 
@@ -496,8 +498,10 @@ pp_gemm_kernel_v2(const PPGemmArgs a, const GemmDerived d) {   // 2nd bound = wa
   int cur_cA = pc1, cur_c0 = 0;
   const uint32_t xbytes3 = (XMODE == PP_X_CONV3X3 && a.x3) ? (uint32_t)a.M * (uint32_t)a.c3 * 2u : 0u;
   const uint32_t xbytes4 = (XMODE == PP_X_CONV3X3 && a.x4) ? (uint32_t)a.M * (uint32_t)a.c4 * 2u : 0u;
-  const int hv = a.up ? a.hin * 2 : a.hin;
-  const int wv = a.up ? a.win * 2 : a.win;
+  // (ABI v29) a.up, stride 1: the virtual input is the nearest resize of the source to hout x wout (2 hin or 2 hin - 1 rows),
+  // read at source index i >> 1; the conv's zero padding begins at hout x wout
+  const int hv = a.up ? (a.stride == 1 ? a.hout : a.hin * 2) : a.hin;
+  const int wv = a.up ? (a.stride == 1 ? a.wout : a.win * 2) : a.win;
 
   // (always_inline: once this lambda is outlined its by-reference captures force the whole kernel-argument struct into
   //  scratch memory -- 700 B per lane and a 2.7x slower kernel)
@@ -1782,7 +1786,12 @@ int validate(const PPGemmArgs& a) {
     if (a.stride != 1 && a.stride != 2) return PP_ERR_BAD_ARG;
     if (a.M != a.batch * a.hout * a.wout) return PP_ERR_BAD_ARG;
     const int hv = a.up ? 2 * a.hin : a.hin, wv = a.up ? 2 * a.win : a.win;
-    if (a.hout != (hv + 2 - 3) / a.stride + 1 || a.wout != (wv + 2 - 3) / a.stride + 1) return PP_ERR_BAD_ARG;
+    if (a.up && a.stride == 1) {
+      // (ABI v29) nearest resize to the size of the next skip tensor: 2 hin or 2 hin - 1 per axis, the axes independent
+      if ((a.hout != hv && a.hout != hv - 1) || (a.wout != wv && a.wout != wv - 1) || a.hout <= 0 || a.wout <= 0) return PP_ERR_BAD_ARG;
+    } else if (a.hout != (hv + 2 - 3) / a.stride + 1 || a.wout != (wv + 2 - 3) / a.stride + 1) {
+      return PP_ERR_BAD_ARG;
+    }
     if ((uint64_t)a.batch * a.hin * a.win * (uint64_t)(a.c1 > a.c2 ? a.c1 : a.c2) * 2u >= 0x80000000ull)
       return PP_ERR_UNSUPPORTED;
   } else {

@@ -1017,6 +1017,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     reinterpret_cast<uint2*>(out)[i] = o;
   }
   for (int i = (n4 << 2) + tid; i < n; i += 256) out[i] = E16<EDT>::from_f(exp2f(row[i] * scale_log2e - M) * inv);
+  for (long long i = n + tid; i < ldp; i += 256) out[i] = (uint16_t)0;      // pad columns of the K-padded P: exact zeros
 }
 }  // namespace
 

@@ -56,6 +56,19 @@ UPCONV_SUBPIX = _lab_switch("PP_UPCONV_SUBPIX")
 UPCONV_SUBPIX_FROM = 1 if (os.environ.get("PP_LAB") == "1" and os.environ.get("PP_UPCONV_SUBPIX") == "2") else 2
 
 
+def level_sizes(H: int, W: int, levels: int) -> List[Tuple[int, int]]:
+    """(h, w) of the `levels` resolution levels of a UNet whose latent is H x W.  Downsample2D is a conv3x3 with stride 2 and
+    padding 1, so a level is the CEIL half of the one above, h -> (h - 1) // 2 + 1 (13 -> 7 -> 4 -> 2), not h >> level; on the way
+    up every upsampler resizes to the size of the level it returns to (unet_2d_condition.py:1120-1126,1311-1312 of the
+    reference: `upsample_size`).  The one place the size chain is written down: SDNet.build_setup sizes the step-invariant
+    operands with it, build_step reaches the same sizes through its convs, NetRuntime its residual slots."""
+    out = [(H, W)]
+    for _ in range(levels - 1):
+        h, w = out[-1]
+        out.append(((h - 1) // 2 + 1, (w - 1) // 2 + 1))
+    return out
+
+
 class Arena:
     """Stack-scoped bump allocator over one device buffer (or a dry counting arena when device is None)."""
 
@@ -331,8 +344,10 @@ class Builder:
     def conv3x3(self, x: Act, w: int, cout: int, bias: int = 0, stride: int = 1, up: bool = False,
                 x2: Optional[Act] = None, rowvec: int = 0, res1: int = 0, res2: int = 0, scale: float = 1.0,
                 out: Optional[Act] = None, x3: Optional[Act] = None, x4: Optional[Act] = None,
-                name: str = "conv3x3", gn_in: Optional[Tuple[int, int, int, float, int]] = None, dup: bool = False) -> Act:
-        """gn_in = (gamma, beta, gamma_beta_interleaved, eps, groups): the conv input is SiLU(GroupNorm(concat(x, x2))).
+                name: str = "conv3x3", gn_in: Optional[Tuple[int, int, int, float, int]] = None, dup: bool = False,
+                up_size: Optional[Tuple[int, int]] = None) -> Act:
+        """up_size (with up): the nearest resize goes to that (h, w), 2 H or 2 H - 1 rows, 2 W or 2 W - 1 columns.
+        gn_in = (gamma, beta, gamma_beta_interleaved, eps, groups): the conv input is SiLU(GroupNorm(concat(x, x2))).
         Where the statistics arrive from the producers' epilogues and the shape suits csrc/conv_gn.hip the norm runs in
         the conv's loader (ONE launch, the normalised activation is never written); else pp_groupnorm_apply(_acc) + conv.
         dup: x is ONE half of a CFG pair whose halves are identical; the launch stores every output row twice and the
@@ -351,7 +366,7 @@ class Builder:
         ptr = lambda t: t.ptr if t is not None else None      # noqa: E731
         # (x3, x4: the 1x1 tail over concat(x3, x4) at the output pixel -- the merged conv_shortcut)
         a = L.conv3x3_args(self.dt, x.B, x.H, x.W, x.C, cout, x.ptr, ptr(x2), c2, ptr(x3), x3.C if x3 is not None else 0,
-                           ptr(x4), x4.C if x4 is not None else 0, stride, up, w=w, scale=scale)
+                           ptr(x4), x4.C if x4 is not None else 0, stride, up, w=w, scale=scale, up_size=up_size)
         ho, wo = a.hout, a.wout
         if dup:
             assert out is None and gn_in is None
@@ -1360,12 +1375,13 @@ class SDNet:
         ldvt = _align(nctx, 8)
         pre_hw: Dict[str, bool] = {}        # transformer -> the fused block kernel takes its step geometry
         pre_hw64: Dict[str, bool] = {}      # transformer -> whole 64-row GEMM tiles per batch item (the two-GEMM form)
+        nl = len(self.boc)
+        sizes = level_sizes(hw0[0], hw0[1], nl) if hw0 is not None else None
         if hw0 is not None:
-            nl = len(self.boc)
             for pre, c in self._attn_specs():
                 part = pre.split(".")
                 lvl = int(part[1]) if part[0] == "down_blocks" else (nl - 1 if part[0] == "mid_block" else nl - 1 - int(part[1]))
-                hw = (hw0[0] >> lvl) * (hw0[1] >> lvl)
+                hw = sizes[lvl][0] * sizes[lvl][1]
                 pre_hw[pre] = hw > 0 and bool(pb.lib.pp_xattn_block_supported(B * hw, c, hw, nctx, self.heads))
                 pre_hw64[pre] = hw > 0 and hw % 64 == 0
         self.kv: Dict[str, Tuple[int, int, int, int]] = {}
@@ -1404,8 +1420,8 @@ class SDNet:
             rev = list(reversed(self.boc))
             for i in range(len(rev) - 1):
                 lvl = len(rev) - 1 - i
-                h, w, c = hw0[0] >> lvl, hw0[1] >> lvl, rev[i]
-                if pb.lib.pp_upconv_subpix_supported(B, h, w, c, c, pb.dt) >= UPCONV_SUBPIX_FROM:
+                (h, w), (ht, wt), c = sizes[lvl], sizes[lvl - 1], rev[i]      # (a cropped target keeps the nine-tap `up` request)
+                if pb.lib.pp_upconv_subpix_supported_to(B, h, w, ht, wt, c, c, pb.dt) >= UPCONV_SUBPIX_FROM:
                     pre = f"up_blocks.{i}.upsamplers.0.conv"
                     self.upfold[pre] = pb.alloc(16 * c * c * 2)
                     pb.plan.add("upconv_fold", pb.lib.pp_upconv_fold, self.P[pre + ".weight"], c, c, pb.dt, self.upfold[pre])
@@ -1587,11 +1603,14 @@ class SDNet:
                 brush_up.append(s)
             if i != len(boc) - 1:
                 pre = f"up_blocks.{i}.upsamplers.0.conv"
-                if pre in getattr(self, "upfold", {}):
+                # the upsampler resizes to the size of the skip tensor the next block pops: 2 h or, behind an odd level of the
+                # down path, 2 h - 1 per axis (`upsample_size`, unet_2d_condition.py:1311-1312; BrushNet_CA.py:874)
+                tgt = (skips[-1].H, skips[-1].W)
+                if pre in getattr(self, "upfold", {}) and tgt == (2 * s.H, 2 * s.W):
                     s = pb.conv3x3_up_subpix(s, self.upfold[pre], rev[i], P[pre + ".bias"], res2=pop(add_up))
                 else:
-                    s = pb.conv3x3(s, P[pre + ".weight"], rev[i], P[pre + ".bias"], up=True, res2=pop(add_up),
-                                   name="conv3x3")
+                    s = pb.conv3x3(s, P[pre + ".weight"], rev[i], P[pre + ".bias"], up=True, up_size=tgt,
+                                   res2=pop(add_up), name="conv3x3")
                 brush_up.append(s)
 
         if self.kind == "brushnet":

@@ -236,27 +236,29 @@ def conv_gn_supported(x: torch.Tensor, cout: int, x2=None, x3=None, x4=None, gro
 
 
 def conv_halo_routed(x: torch.Tensor, cout: int, x2=None, x3=None, x4=None, stride: int = 1, up: bool = False,
-                     tile: int = 0) -> bool:
+                     tile: int = 0, up_size=None) -> bool:
     """Does a PLAIN conv3x3 of these shapes run on the halo-tile loop (pp_conv_gn_supported() == 2) rather than the tap-major
     implicit GEMM?"""
-    a = _conv_request(x, cout, stride, up, x2, x3, x4)
+    a = _conv_request(x, cout, stride, up, x2, x3, x4, up_size)
     a.tile = tile
     return L.lib().pp_conv_gn_supported(C.byref(a)) == 2
 
 
-def _conv_request(x, cout, stride, up, x2, x3, x4) -> L.PPGemmArgs:
+def _conv_request(x, cout, stride, up, x2, x3, x4, up_size=None) -> L.PPGemmArgs:
     """L.conv3x3_args of NHWC tensors (x2 rides beside x; x3 / x4: the 1x1 tail over concat(x3, x4) at the output pixel)"""
     B, H, W, C1 = x.shape
     ch = lambda t: t.shape[3] if t is not None else 0      # noqa: E731
     return L.conv3x3_args(L.dtype_code(x.dtype), B, H, W, C1, cout, _p(x), _p(x2), ch(x2), _p(x3), ch(x3), _p(x4), ch(x4),
-                          stride, up)
+                          stride, up, up_size=up_size)
 
 
 def conv3x3(x: torch.Tensor, w: torch.Tensor, bias=None, stride: int = 1, up: bool = False, x2=None, rowvec=None,
             res1=None, res2=None, scale: float = 1.0, tile: int = 0, splitk: int = 0, gn=None, x3=None, x4=None,
             gn_in=None, gn_next=None, dup: bool = False, gn_dup_mask: int = 0, res1_wrap: int = 0,
-            fuse_combine: bool = False, out=None, workspace=None, ynext=None):
+            fuse_combine: bool = False, out=None, workspace=None, ynext=None, up_size=None):
     """x NHWC bf16 [B,H,W,C1] (+x2 [B,H,W,C2]); w bf16 [Cout, 9*(C1+C2)] (k = (ky*3+kx)*C + c) -> NHWC bf16.
+    up_size (with up): F.interpolate(size=up_size, mode="nearest") in front of the conv instead of the 2x upsample, 2 H - 1 or
+    2 H rows and 2 W - 1 or 2 W columns (Upsample2D with `output_size`).
     dup: every output row is stored twice -> out [2B, ...] (PPGemmArgs.out_dup_rows: the CFG twin prefix); gn_dup_mask:
     which of the `gn` subscriptions hold [2B][groups][2] accumulators that receive both halves' sums.
     gn_in = (acc int64 [B][groups][2], gamma_beta fp32 [C1+C2][2], groups, eps): GroupNorm + SiLU of concat(x, x2) fused
@@ -268,7 +270,7 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, bias=None, stride: int = 1, up: bo
     ynext: the caller's gn_next output, a contiguous tensor of the output's shape (the ABI has no stride for it; _norm_out)."""
     lib = L.lib()
     B, C1, C2, cout = x.shape[0], x.shape[3], (x2.shape[3] if x2 is not None else 0), w.shape[0]
-    a = _conv_request(x, cout, stride, up, x2, x3, x4)
+    a = _conv_request(x, cout, stride, up, x2, x3, x4, up_size)
     ho, wo = a.hout, a.wout
     oshape = (2 * B if dup else B, ho, wo, cout)
     if out is None:

@@ -6,7 +6,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import Act, Arena, Builder, Plan, SDNet, _align
+from .engine import Act, Arena, Builder, Plan, SDNet, _align, level_sizes
 
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
@@ -108,13 +108,14 @@ class NetRuntime:
         """(batch, C, h, w) of the residual tensors the UNet accepts, in reference order."""
         net = self.net
         boc = net.boc
+        sizes = level_sizes(H, W, len(boc))
         down = [(B, boc[0], H, W)]
-        h, w = H, W
         for i, c in enumerate(boc):
+            h, w = sizes[i]
             for _ in range(net.L):
                 down.append((B, c, h, w))
             if i != len(boc) - 1:
-                h, w = h // 2, w // 2
+                h, w = sizes[i + 1]
                 down.append((B, c, h, w))
         out = {"down": down, "mid": [(B, boc[-1], h, w)]}
         if with_up:
@@ -123,7 +124,7 @@ class NetRuntime:
                 for _ in range(net.L + 1):
                     up.append((B, c, h, w))
                 if i != len(boc) - 1:
-                    h, w = h * 2, w * 2
+                    h, w = sizes[len(boc) - 2 - i]
                     up.append((B, c, h, w))
             out["up"] = up
         return out
@@ -149,8 +150,6 @@ class NetRuntime:
                 self._patch_scale(scale)
             self.set_freeu(freeu)
             return
-        if H % (2 ** (len(self.net.boc) - 1)) or W % (2 ** (len(self.net.boc) - 1)):
-            raise L.PPError(f"latent size {H}x{W} must be divisible by {2 ** (len(self.net.boc) - 1)}")
         # (the one synchronising probe of the library runs here, at plan-build time and never under a stream capture: are
         #  workgroups placed on the XCDs round-robin by linear id?  Plans combine split-K in-kernel only if so.)
         self.xcd_placement_ok = bool(self.lib.pp_xcd_placement_ok())

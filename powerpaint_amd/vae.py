@@ -221,25 +221,29 @@ class VAENet:
         """Single-head attention over the H*W tokens with residual (diffusers Attention(residual_connection=True))."""
         P = self.P
         Cc, n, B = x.C, x.H * x.W, x.B
-        if n % 64:
-            raise L.PPError(f"AutoencoderKL attention: H*W = {n} tokens must be a multiple of 64")
+        # The keys are padded to the GEMMs' K step, npad = n rounded up to 64: S = Q K^T is [n][npad] (its pad columns multiply
+        # whatever rows follow K -- the next image's keys, or the pad rows allocated behind the last -- and are never read:
+        # the softmax runs over n columns), P is [n][npad] with pad columns the softmax WRITES as zeros (the arena is reused),
+        # V^T is [C][npad] with pad columns pp_transpose_v zeroes.  n % 64 == 0: npad = n, the plan that always was.
+        npad = _align(n, 64)
         out = pb.new_act(B, x.H, x.W, Cc)
         m = pb.mark()
         h = pb.groupnorm(x, P[f"{pre}.group_norm.weight"], P[f"{pre}.group_norm.bias"], EPS, False,
                          groups=self.groups)
         q = pb.linear(h.ptr, x.rows, Cc, P[f"{pre}.to_q.weight"], Cc, P[f"{pre}.to_q.bias"], name="linear")
-        k = pb.linear(h.ptr, x.rows, Cc, P[f"{pre}.to_k.weight"], Cc, P[f"{pre}.to_k.bias"], name="linear")
+        k = pb.linear(h.ptr, x.rows, Cc, P[f"{pre}.to_k.weight"], Cc, P[f"{pre}.to_k.bias"],
+                      out=pb.alloc((x.rows + npad - n) * Cc * 2), name="linear")
         v = pb.linear(h.ptr, x.rows, Cc, P[f"{pre}.to_v.weight"], Cc, P[f"{pre}.to_v.bias"], name="linear")
-        vt = pb.alloc(B * Cc * n * 2)
-        pb.plan.add("transpose_v", pb.lib.pp_transpose_v, v, Cc, B, n, Cc, vt, n)
+        vt = pb.alloc(B * Cc * npad * 2)
+        pb.plan.add("transpose_v", pb.lib.pp_transpose_v, v, Cc, B, n, Cc, vt, npad)
         o = pb.alloc(x.rows * Cc * 2)
-        s = pb.alloc(n * n * 4)
-        p = pb.alloc(n * n * 2)
+        s = pb.alloc(n * npad * 4)
+        p = pb.alloc(n * npad * 2)
         for b in range(B):
             tok = b * n * Cc * 2
-            pb.linear(q + tok, n, Cc, k + tok, n, out=s, ldo=n, out_f32=True, name="attn_qk")
-            pb.plan.add("softmax_rows", pb.lib.pp_softmax_rows, s, n, n, n, float(Cc) ** -0.5, p, n, pb.dt)
-            pb.linear(p, n, n, vt + b * Cc * n * 2, Cc, out=o + tok, ldo=Cc, name="attn_pv")
+            pb.linear(q + tok, n, Cc, k + tok, npad, out=s, ldo=npad, out_f32=True, name="attn_qk")
+            pb.plan.add("softmax_rows", pb.lib.pp_softmax_rows, s, npad, n, n, float(Cc) ** -0.5, p, npad, pb.dt)
+            pb.linear(p, n, npad, vt + b * Cc * npad * 2, Cc, out=o + tok, ldo=Cc, name="attn_pv")
         pb.linear(o, x.rows, Cc, P[f"{pre}.to_out.0.weight"], Cc, P[f"{pre}.to_out.0.bias"], res1=x.ptr, out=out.ptr,
                   name="linear")
         pb.release(m)
