@@ -786,6 +786,23 @@ int pp_lora_merge(const PPLoraMergeArgs* args, void* stream);
 int pp_freeu(const void* hidden, void* hidden_out, int ch, const void* skip, void* skip_out, int cs, int batch, int h, int w,
              const float* bs, int64_t* acc, int groups, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * (added under ABI 29; purely additive) IP-Adapter: the image-prompt term of the decoupled cross-attention of diffusers-0.27
+ * IPAdapterAttnProcessor2_0, added IN PLACE to the output of the text cross-attention, ONE launch per adapter:
+ *     o[b][r][h*d .. (h+1)*d) += ip_scale * sum_j softmax_j(qk_scale * q[b][r][h] . k_ip[b][j][h]) * v_ip[b][j][h]
+ *   q, o       : 16-bit [batch * nq][heads * d] with row strides ldq / ldo (elements, multiples of 8, >= heads * d), 16-byte
+ *                aligned, not overlapping; q is only read
+ *   k_ip, v_ip : 16-bit [batch][nk][heads * d], contiguous, 16-byte aligned: to_k_ip / to_v_ip of the adapter's image tokens
+ *   d          : 40, 80 or 160 (else PP_ERR_UNSUPPORTED; d % 8 != 0 is PP_ERR_BAD_ARG); 1 <= nk <= PP_IP_MAX_TOKENS (4 tokens
+ *                per image of a base adapter: 16 images); heads <= 64, batch <= 65535
+ *   ip_scale   : by value.  0 is "no term": the call returns PP_OK without a launch and o keeps its bits
+ * Scores, softmax (maximum subtracted), the weighted sum and the add are fp32, one rounding to `dtype` (bf16 / fp16) at the
+ * store; every element of o is read once and written once by the same lane, nothing outside [batch * nq) x [heads * d) is
+ * touched (the gaps of ldo > heads * d included). */
+#define PP_IP_MAX_TOKENS 64
+int pp_ip_attn_add(const void* q, int ldq, const void* k_ip, const void* v_ip, void* o, int ldo, int batch, int heads, int nq,
+                   int nk, int d, float qk_scale, float ip_scale, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

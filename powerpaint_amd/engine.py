@@ -153,6 +153,34 @@ class ParamPack:
         self.items = []  # drop host copies
         return self
 
+    def regrow(self, keep: int):
+        """Re-lay the tail of the buffer on the device: the first `keep` bytes (the network's own entries) are copied as they
+        are into a NEW contiguous buffer and the entries `add()`ed since (behind a `forget`) are appended behind them.  Every
+        pointer changes: whoever baked one into a plan rebuilds it."""
+        old = self.buf
+        self.total = max(self.total, keep)
+        buf = torch.zeros(_align(self.total) + ALIGN, dtype=torch.uint8, device=old.device)
+        skew = (-buf.data_ptr()) % ALIGN
+        buf = buf[skew:skew + _align(self.total)]
+        buf[:keep].copy_(old[:keep])
+        for name, t in self.items:
+            off, nb = self.offsets[name], t.numel() * t.element_size()
+            buf[off:off + nb].copy_(t.view(-1).view(torch.uint8))
+        self.items = []
+        self.buf = buf
+        base = buf.data_ptr()
+        self.ptr.clear()              # (SDNet.P is this dict)
+        self.ptr.update({name: base + off for name, off in self.offsets.items()})
+        self.touch()
+
+    def forget(self, prefix: str, keep: int):
+        """Drop the entries named `prefix`... (all of which lie behind byte `keep`); the next add() lands at `keep`."""
+        for name in [n for n in self.offsets if n.startswith(prefix)]:
+            assert self.offsets[name] >= keep, name
+            del self.offsets[name], self.shapes[name]
+            self.ptr.pop(name, None)
+        self.total = keep
+
     def tensor(self, name: str) -> torch.Tensor:
         shape, dtype = self.shapes[name]
         off = self.offsets[name]
@@ -544,6 +572,15 @@ class Builder:
         self.plan.count("attention", 4.0 * B * heads * nq * nk * d)
         return out
 
+    def ip_attn_add(self, q: int, ldq: int, k_ip: int, v_ip: int, o: int, ldo: int, B: int, heads: int, nq: int, nk: int,
+                    d: int, scale):
+        """IP-Adapter's image-prompt term added in place to a cross-attention output (csrc/ip_attn.hip): `scale` is a
+        ctypes.c_float CELL handed over by value at every launch -- whoever owns it (NetRuntime.set_ip_scales) changes the
+        value of eager runs in place; a captured graph carries the value it was captured with."""
+        self.plan.add("ip_attn_add", self.lib.pp_ip_attn_add, q, ldq, k_ip, v_ip, o, ldo, B, heads, nq, nk, d,
+                      float(d) ** -0.5, scale, self.dt)
+        self.plan.count("ip_attn_add", 4.0 * B * nq * nk * heads * d)
+
     def ff_fused(self, hs: int, rows: int, Cc: int, hw: int, w1: int, b1: int, cs1: int, ln_stats: int, ln_tiles: int,
                  w2: int, bias2: int, out: int, res1: int = 0, res1_wrap: int = 0, res2: int = 0, w2_kperm: bool = False):
         """FeedForward (GEGLU) + FF2 . proj_out of a C = 320 transformer as ONE launch (csrc/ff_fused.hip, pp_ff_fused): the
@@ -736,6 +773,8 @@ class SDNet:
         self.P: Dict[str, int] = {}
         self.temb_off: Dict[str, int] = {}
         self.temb_total = 0
+        # IP-Adapters (set_ip_adapters): per adapter (tokens per image, image-embed dimension); empty = a network without any
+        self.ip: List[Tuple[int, int]] = []
         for c in self.boc:
             if c % 64 or (c // heads) not in (40, 80, 160):
                 raise L.PPError(f"unsupported channel width {c} (need multiple of 64 and head_dim in 40/80/160)")
@@ -1080,6 +1119,8 @@ class SDNet:
                 pk.add(name, t, dt)
         pk.to_device(device, materialize)
         self.params, self.P = pk, pk.ptr
+        self.ip = []                           # (IP-Adapter entries lived behind the old buffer's own entries: gone with it)
+        self._own_bytes = pk.total
         return self
 
     def recipes_of(self, modules) -> List["PackRecipe"]:
@@ -1191,6 +1232,49 @@ class SDNet:
         self.params.touch()
         self.repack_launches = len(keep)      # (temporaries are stream-ordered allocations: safe to let go once queued)
         return recipes
+
+    # ---------------------------------------------------------------- IP-Adapter parameters (DESIGN.md "IP-Adapter")
+    def ip_attn_order(self) -> List[str]:
+        """The transformers in the order an IP-Adapter file numbers their cross-attentions: the order of the reference
+        UNet's `attn_processors` -- down blocks, then UP blocks, then the mid block (its registration order) -- where
+        _attn_specs() walks in execution order."""
+        pres = [p for p, _ in self._attn_specs()]
+        return [p for head in ("down_blocks.", "up_blocks.", "mid_block.") for p in pres if p.startswith(head)]
+
+    def set_ip_adapters(self, adapters: Sequence[Dict[str, object]]):
+        """Replace the IP-Adapter entries of the packed buffer.  adapters: per adapter {"proj.weight" [T * ctx][D], "proj.bias"
+        [T * ctx], "norm.weight" [ctx], "norm.bias" [ctx], "kv": {transformer prefix: (to_k_ip [C][ctx], to_v_ip [C][ctx])}}
+        (validated by the caller, models/unet_2d_condition.py); [] removes them.  Packed behind the network's own entries:
+          ip_adapter.<i>.proj.weight   16-bit [T * ctx][D rounded up to 64] (zero columns: the GEMM contracts 64 at a time)
+          ip_adapter.<i>.proj.bias, .norm.weight, .norm.bias   fp32
+          ip_adapter.<i>.<transformer>.kv.weight   16-bit [2 C][ctx] = [to_k_ip; to_v_ip], as attn2.kv.weight
+        They are no source of any PackRecipe: `repack` (LoRA) never touches them.  Every packed pointer moves."""
+        if self.kind != "unet":
+            raise L.PPError("IP-Adapters attach to the UNet's cross-attentions only")
+        pk = self.params
+        if pk is None or pk.buf is None:
+            raise L.PPError("SDNet.set_ip_adapters: pack the network's own parameters first (load_state_dict)")
+        if not self.ip and not adapters:
+            return self
+        pk.forget("ip_adapter.", self._own_bytes)
+        ip = []
+        for i, ad in enumerate(adapters):
+            w = ad["proj.weight"].float()
+            D = w.shape[1]
+            T = w.shape[0] // self.ctx_dim
+            wp = torch.zeros(w.shape[0], _align(D, 64))
+            wp[:, :D] = w
+            pk.add(f"ip_adapter.{i}.proj.weight", wp, self.dtype)
+            for n in ("proj.bias", "norm.weight", "norm.bias"):
+                pk.add(f"ip_adapter.{i}.{n}", ad[n].float(), torch.float32)
+            for pre, _ in self._attn_specs():
+                wk, wv = ad["kv"][pre]
+                pk.add(f"ip_adapter.{i}.{pre}.kv.weight", torch.cat([wk.float(), wv.float()], 0), self.dtype)
+            ip.append((T, D))
+        pk.regrow(self._own_bytes)
+        self.P = pk.ptr
+        self.ip = ip
+        return self
 
     # ---------------------------------------------------------------- plan pieces
     def _resnet(self, pb: Builder, pre: str, x: Act, cout: int, temb_all: int, x2: Optional[Act] = None,
@@ -1338,6 +1422,9 @@ class SDNet:
             ln, kw = normed(hs, st, "norm2", "attn2.to_q")
             q = pb.linear(ln, rows, Cc, P[f"{tb}.attn2.to_q.weight"], Cc, name="linear", **kw)
             a = pb.attention(q, Cc, kv[0], kv[1], kv[2], kv[3], x.B, self.heads, hw, self._nctx, d)
+            # IP-Adapter: a += scale_i * softmax(q K_i^T / sqrt(d)) V_i per adapter, in place, in front of to_out
+            for (k_ip, v_ip, nk_ip), cell in zip(getattr(self, "ip_kv", {}).get(pre, ()), getattr(self, "ip_scale_cells", ())):
+                pb.ip_attn_add(q, Cc, k_ip, v_ip, a, Cc, x.B, self.heads, hw, nk_ip, d, cell)
             st = producer()
             hs = pb.linear(a, rows, Cc, P[f"{tb}.attn2.to_out.weight"], Cc, P[f"{tb}.attn2.to_out.bias"], res1=hs,
                            row_stats_out=st, name="linear")
@@ -1367,11 +1454,29 @@ class SDNet:
 
     # ---------------------------------------------------------------- setup plan: step-invariant work
     def build_setup(self, pb: Builder, B: int, nctx: int, ehs: int, cond: Optional[Act] = None,
-                    hw0: Optional[Tuple[int, int]] = None):
+                    hw0: Optional[Tuple[int, int]] = None, ip_in: Sequence[Tuple[int, int]] = (), ip_scales=()):
         """Cross-attention K and V^T for every transformer from encoder_hidden_states (bf16 [B*nctx][ctx_dim] at
         `ehs`); for ControlNet also the conditioning embedding of `cond` (NHWC bf16 image).  hw0 = (H, W) of the latents the
-        step plan will be built for (the folded cross-attention operands of a transformer depend on which kernel runs it)."""
+        step plan will be built for (the folded cross-attention operands of a transformer depend on which kernel runs it).
+        ip_in (a UNet with IP-Adapters, one entry per adapter): (pointer, n) of the call's image embeds, 16-bit [B][n][D rounded
+        up to 64] with zero pad columns; ip_scales: the adapters' ctypes.c_float scale cells.  The image tokens
+        e_i = LayerNorm(reshape(proj(embeds))) [B][n T][ctx] and, per transformer, K_i = to_k_ip(e_i) and V_i = to_v_ip(e_i),
+        row-major [B][n T][C] each, are step-invariant: computed here, read by the step plan's pp_ip_attn_add launches.  While
+        adapters are loaded no cross-attention is folded (self.xa stays empty): every attn2 runs to_q -> attention -> to_out."""
         self._nctx = nctx
+        if len(ip_in) != len(self.ip) or len(ip_scales) != len(self.ip):
+            raise L.PPError(f"{len(self.ip)} IP-Adapters are loaded, the setup plan was given {len(ip_in)} image-embed buffers")
+        self.ip_kv: Dict[str, List[Tuple[int, int, int]]] = {}
+        self.ip_scale_cells = list(ip_scales)
+        ip_tok = []
+        for i, ((T, D), (src, n)) in enumerate(zip(self.ip, ip_in)):
+            if n < 1 or n * T > L.PP_IP_MAX_TOKENS:
+                raise L.PPError(f"IP-Adapter {i}: {n} images of {T} tokens, pp_ip_attn_add takes 1..{L.PP_IP_MAX_TOKENS} tokens")
+            Pn = f"ip_adapter.{i}"
+            y = pb.linear(src, B * n, _align(D, 64), self.P[f"{Pn}.proj.weight"], T * self.ctx_dim, self.P[f"{Pn}.proj.bias"],
+                          name="linear")
+            e = pb.layernorm(y, B * n * T, self.ctx_dim, self.P[f"{Pn}.norm.weight"], self.P[f"{Pn}.norm.bias"])
+            ip_tok.append((e, n * T))
         ldvt = _align(nctx, 8)
         pre_hw: Dict[str, bool] = {}        # transformer -> the fused block kernel takes its step geometry
         pre_hw64: Dict[str, bool] = {}      # transformer -> whole 64-row GEMM tiles per batch item (the two-GEMM form)
@@ -1392,6 +1497,13 @@ class SDNet:
             k = pb.linear(ehs, B * nctx, self.ctx_dim, self.P[f"{tb}.attn2.kv.weight"], 2 * c, out_vt=vt,
                           vt_col0=c, vt_ld=ldvt, rows_per_batch=nctx, name="linear")
             self.kv[pre] = (k, c, vt, ldvt)
+            for i, (e, nk_ip) in enumerate(ip_tok):
+                w = self.P[f"ip_adapter.{i}.{pre}.kv.weight"]
+                k_ip = pb.linear(e, B * nk_ip, self.ctx_dim, w, c, name="linear")
+                v_ip = pb.linear(e, B * nk_ip, self.ctx_dim, w + c * self.ctx_dim * 2, c, name="linear")
+                self.ip_kv.setdefault(pre, []).append((k_ip, v_ip, nk_ip))
+            if self.ip:
+                continue
             tbq = f"{tb}.attn2.to_q"
             two_gemm = bool(self.fuse_xattn and self.fuse_xattn_2g and c > 320 and pre_hw64.get(pre) and
                             not (self.fuse_xattn_wide and c <= self.xattn_wide_max_c))
@@ -1489,7 +1601,8 @@ class SDNet:
         add_up = list(add_up) if brush else None
         # (a forced tile / split-K factor -- NetRuntime.gemm_tile / gemm_splitk, a measurement knob -- may send conv_in off
         #  the single-pass staged epilogue that stores the twin copy: the flag then changes nothing, as everywhere it cannot run)
-        twin = bool(twin) and not pad_uncond and not (pb.gemm_tile or pb.gemm_splitk) and \
+        # (IP-Adapters: the prefix ends in the fused cross-attention block, which is not taken while one is loaded)
+        twin = bool(twin) and not pad_uncond and not self.ip and not (pb.gemm_tile or pb.gemm_splitk) and \
             self.twin_prefix_ok(lib, B, H, W, self._nctx, brush)
 
         def pop(lst):

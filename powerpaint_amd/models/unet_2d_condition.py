@@ -11,6 +11,7 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 import torch
 
 from .. import _lib as L
+from .. import ip_adapter as IPA
 from ..lora import AdapterSet, LoraAdapter, unet_targets
 from ._base import SD15_DOWN, SD15_UP, Output, _HipModel
 
@@ -38,6 +39,7 @@ class UNet2DConditionModel(_HipModel):
             resnet_time_scale_shift="default", mid_block_scale_factor=1, downsample_padding=1,
             num_attention_heads=None, projection_class_embeddings_input_dim=None, encoder_hid_dim=None,
             encoder_hid_dim_type=None, addition_time_embed_dim=None, transformer_layers_per_block=1)
+        self.encoder_hid_proj = None        # (IP-Adapters loaded: MultiIPAdapterImageProjection, as in diffusers)
 
     # ------------------------------------------------------------------ LoRA adapters (DESIGN.md "LoRA adapters")
     # Adapters are MERGED into the packed parameter buffer in place (SDNet.repack -> pp_lora_merge): the launch plans, the
@@ -49,6 +51,8 @@ class UNet2DConditionModel(_HipModel):
         source of an adapter merge is read from it, at the time of the first merge."""
         super().load_state_dict(sd, strict, keep_state_dict, materialize)
         self._lora_forget()
+        # (a fresh packed buffer: IP-Adapter entries, which live behind the network's own, are gone with the old one)
+        self.encoder_hid_proj, self.config.encoder_hid_dim_type = None, None
         return self
 
     def _lora_set(self) -> AdapterSet:
@@ -164,6 +168,64 @@ class UNet2DConditionModel(_HipModel):
         self.params_changed()
         return self
 
+    # ------------------------------------------------------------------ IP-Adapter (DESIGN.md "IP-Adapter")
+    def _load_ip_adapter_weights(self, state_dicts):
+        """diffusers' `UNet2DConditionLoadersMixin._load_ip_adapter_weights`: state_dicts = one {"image_proj", "ip_adapter"}
+        dict, or a list of them (several adapters, each with its own image embeds and scale at call time).  Replaces whatever
+        adapters were loaded.  Everything is validated before anything changes: a refused file leaves the model as it was.
+        The weights go into the packed parameter buffer (SDNet.set_ip_adapters); the plans are rebuilt on the next call,
+        without the fused cross-attention forms and the CFG twin prefix (every attn2 runs to_q -> attention ->
+        pp_ip_attn_add per adapter -> to_out).  Scales start at 1.0, as in diffusers."""
+        if isinstance(state_dicts, dict):
+            state_dicts = [state_dicts]
+        if not state_dicts:
+            raise L.PPError("_load_ip_adapter_weights: no adapter given (unload with _unload_ip_adapter)")
+        ads = [IPA.check_ip_adapter(self.net, IPA.read_ip_adapter(sd), f"IP-Adapter {i}") for i, sd in enumerate(state_dicts)]
+        self.net.set_ip_adapters(ads)
+        self.encoder_hid_proj = IPA.MultiIPAdapterImageProjection([IPA.projection_module(a, self.net.ctx_dim) for a in ads])
+        self.config.encoder_hid_dim_type = "ip_image_proj"
+        self.rt.key = None
+        self.rt.set_ip_scales([1.0] * len(ads))
+        self.params_changed()
+        return self
+
+    def _unload_ip_adapter(self):
+        """Back to the UNet that never had an adapter: its packed entries, its plans (launch for launch), its config."""
+        if self.net.ip:
+            self.net.set_ip_adapters([])
+            self.rt.key = None
+            self.params_changed()
+        self.encoder_hid_proj, self.config.encoder_hid_dim_type = None, None
+        return self
+
+    def set_ip_adapter_scale(self, scale):
+        """A float for all adapters or one value per adapter (by-value kernel arguments: captured graphs are re-captured)."""
+        if not self.net.ip:
+            raise L.PPError("set_ip_adapter_scale: no IP-Adapter is loaded")
+        self.rt.set_ip_scales(IPA.scales_list(scale, len(self.net.ip)))
+        return self
+
+    def _ip_image_embeds(self, added_cond_kwargs, B: int):
+        """`added_cond_kwargs["image_embeds"]` of a UNet with IP-Adapters (unet_2d_condition.py:1030-1037 of the reference):
+        a list of [B, n, D] tensors, one per adapter.  Without adapters the key is refused, never ignored."""
+        if not self.net.ip:
+            if added_cond_kwargs and "image_embeds" in added_cond_kwargs:
+                raise L.PPError("added_cond_kwargs['image_embeds'] given but no IP-Adapter is loaded (load_ip_adapter first)")
+            return None
+        if not added_cond_kwargs or "image_embeds" not in added_cond_kwargs:
+            raise ValueError(f"{self.__class__} has the config param `encoder_hid_dim_type` set to 'ip_image_proj' which requires "
+                             f"the keyword argument `image_embeds` to be passed in  `added_conditions`")
+        embeds = added_cond_kwargs["image_embeds"]
+        IPA.check_image_embeds(embeds, len(self.net.ip))
+        for i, (e, (T, D)) in enumerate(zip(embeds, self.net.ip)):
+            if e.shape[0] != B or e.shape[2] != D:
+                raise ValueError(f"image_embeds[{i}] has shape {tuple(e.shape)}, the UNet runs batch {B} and adapter {i} takes "
+                                 f"embeds of dimension {D}")
+            if e.shape[1] * T > L.PP_IP_MAX_TOKENS:
+                raise L.PPError(f"image_embeds[{i}]: {e.shape[1]} images of {T} tokens, at most {L.PP_IP_MAX_TOKENS} tokens "
+                                f"per adapter")
+        return list(embeds)
+
     # ------------------------------------------------------------------ FreeU (DESIGN.md "FreeU")
     def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
         """FreeU (https://arxiv.org/abs/2309.11497), the reference's `UNet2DConditionModel.enable_freeu`
@@ -198,8 +260,9 @@ class UNet2DConditionModel(_HipModel):
 
     def prepare(self, sample_shape, encoder_hidden_states, down_block_add_samples=None, mid_block_add_sample=None,
                 up_block_add_samples=None, down_block_additional_residuals=None, mid_block_additional_residual=None,
-                twin: bool = False, timestep_cond: Optional[torch.Tensor] = None):
-        """Compile (or reuse) the launch plan for this shape / residual wiring and bind the inputs.  timestep_cond: the
+                twin: bool = False, timestep_cond: Optional[torch.Tensor] = None, added_cond_kwargs=None):
+        """Compile (or reuse) the launch plan for this shape / residual wiring and bind the inputs.  added_cond_kwargs:
+        {"image_embeds": [...]} while IP-Adapters are loaded (_ip_image_embeds), copied in on every call.  timestep_cond: the
         guidance embedding of a UNet with `time_cond_proj_dim` ([B or 1, d], one value over the batch; None = no term, as
         in diffusers) -- constant over a denoising call, folded into the time embedding's first bias once
         (NetRuntime.set_timestep_cond).  twin: the caller (the
@@ -211,7 +274,11 @@ class UNet2DConditionModel(_HipModel):
             raise ValueError(f"sample has {Cin} channels, unet.config.in_channels = {self.config.in_channels}")
         wiring = self._wiring(down_block_add_samples, mid_block_add_sample, up_block_add_samples,
                               down_block_additional_residuals, mid_block_additional_residual)
-        self.rt.ensure(B, H, W, self._nctx(encoder_hidden_states), Cin, wiring, twin=twin, freeu=self._freeu_values())
+        ip_embeds = self._ip_image_embeds(added_cond_kwargs, B)
+        self.rt.ensure(B, H, W, self._nctx(encoder_hidden_states), Cin, wiring, twin=twin, freeu=self._freeu_values(),
+                       ip_n=[e.shape[1] for e in ip_embeds] if ip_embeds else ())
+        if ip_embeds:
+            self.rt.set_ip_embeds(ip_embeds)
         if wiring[0] != "plain":
             groups = {"down": down_block_add_samples if wiring[0] == "brushnet" else down_block_additional_residuals,
                       "mid": [mid_block_add_sample if wiring[0] == "brushnet" else mid_block_additional_residual]}
@@ -261,7 +328,7 @@ class UNet2DConditionModel(_HipModel):
         self.merge_adapters((cross_attention_kwargs or {}).get("scale", 1.0))
         rt = self.prepare(tuple(sample.shape), encoder_hidden_states, down_block_add_samples, mid_block_add_sample,
                           up_block_add_samples, down_block_additional_residuals, mid_block_additional_residual,
-                          timestep_cond=timestep_cond)
+                          timestep_cond=timestep_cond, added_cond_kwargs=added_cond_kwargs)
         # the reference consumes the BrushNet lists destructively (.pop(0), unet_2d_condition.py:1223,1234,1318)
         for lst in (down_block_add_samples, up_block_add_samples):
             if isinstance(lst, list):

@@ -80,8 +80,10 @@ class DenoiseLoop:
     def bind(self, latents_shape, do_cfg: bool, guidance_scale: float, prompt_embeds, prompt_embeds_side=None,
              static_inputs=(), side_static_inputs=(), controlnet_cond=None, side_scale: float = 1.0,
              guess_mode: bool = False, eta: float = 0.0, generator=None, noise_dtype=torch.float32, blend=None,
-             timestep_cond=None):
+             timestep_cond=None, added_cond_kwargs=None):
         """Compile the per-step program.  latents_shape = (B, 4, h, w) of the *un-duplicated* latents.
+        added_cond_kwargs: {"image_embeds": [...]} of a UNet with IP-Adapters (pipeline_PowerPaint_Brushnet_CA.py:1363-1366,
+        1430-1441: the UNet only, never the side network); copied in and projected once per call (NetRuntime.set_ip_embeds).
         blend = (image_latents [1,4,h,w], mask [1,1,h,w], noise [B,4,h,w]): the `num_channels_unet == 4` branch of the
         ppt-v1 loop body (pipeline_PowerPaint.py:1025-1039) -- after every scheduler step the unmasked region is
         replaced by the init image's latents noised to the NEXT timestep.
@@ -210,6 +212,8 @@ class DenoiseLoop:
             side_rts = [side_rt]
         if timestep_cond is not None:
             wiring_kw["timestep_cond"] = timestep_cond
+        if added_cond_kwargs is not None:
+            wiring_kw["added_cond_kwargs"] = added_cond_kwargs
         rt = self.unet.prepare((Be, cin, h, w), prompt_embeds, twin=twin_u, **wiring_kw)
         # one-time (per call) static channels of the UNet / side inputs
         rt.load_input(list(static_inputs))
@@ -245,7 +249,8 @@ class DenoiseLoop:
         if key == self._key and self.program is not None:
             # The conditioning scale is a by-value argument of the zero-conv launches: `prepare` has patched the launch
             # records (eager runs see it), but a graph captured with another value still carries the old one.
-            if self.graph is not None and self._scale_now() != self._graph_scale:
+            if self.graph is not None and (self._scale_now() != self._graph_scale or
+                                           rt.ip_scales() != getattr(self, "_graph_ip", ())):
                 self.graph = None
             return self
         self._key = key
@@ -472,6 +477,7 @@ class DenoiseLoop:
         """Capture one step into a hipGraph (torch.cuda.CUDAGraph).  The captured launches read the step counter from
         device memory, so the same graph serves every step."""
         self._graph_scale = self._scale_now()
+        self._graph_ip = self.rt.ip_scales()          # (IP-Adapter scales: by-value arguments of the UNet's launches as well)
         self.graph = self._capture_program(self.program)
 
     def _capture_program(self, program):
@@ -523,7 +529,8 @@ class DenoiseLoop:
         if not varying and scale_schedule and self.side_rt is not None and \
                 self._scale_now() != self._side_scale(scale_schedule[0]):
             self.side_rt._patch_scale(self._side_scale(scale_schedule[0]))   # (a previous call may have left a windowed value)
-        if use_graph and not varying and (self.graph is None or self._graph_scale != self._scale_now()):
+        if use_graph and not varying and (self.graph is None or self._graph_scale != self._scale_now() or
+                                          getattr(self, "_graph_ip", ()) != self.rt.ip_scales()):
             self.capture()
         stream = torch.cuda.current_stream().cuda_stream
         for i in range(num_steps):
@@ -606,7 +613,8 @@ class DenoiseLoop:
                 else:
                     ent["program"].run(stream)
             elif use_graph and not varying:
-                if self.graph is None or self._graph_scale != self._scale_now():
+                if self.graph is None or self._graph_scale != self._scale_now() or \
+                        getattr(self, "_graph_ip", ()) != self.rt.ip_scales():
                     self.capture()
                     self._f_step.fill_(i)
                 self.graph.replay()

@@ -11,6 +11,8 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
+from .. import _lib as L
+from .. import ip_adapter as IPA
 from ._base import PipelineBase, hip_mask_prep, randn_tensor
 from ._loop import DenoiseLoop
 from .image_processor import VaeImageProcessor
@@ -108,6 +110,104 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
             prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds])
         return prompt_embeds
 
+    # ------------------------------------------------------------------ IP-Adapter (DESIGN.md "IP-Adapter")
+    def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder=None, weight_name=None,
+                        image_encoder_folder=None, **kwargs):
+        """diffusers' `IPAdapterMixin.load_ip_adapter` for local files and state dicts (nothing is downloaded): a dict
+        {"image_proj": {...}, "ip_adapter": {...}}, a .bin holding one, a .safetensors with `image_proj.` / `ip_adapter.` key
+        prefixes, a folder plus `weight_name` (and `subfolder`) -- or a list of those for several adapters (`subfolder` /
+        `weight_name` then a value or one per adapter).  Base adapters only; Plus / FaceID files are refused by name
+        (powerpaint_amd.ip_adapter.check_ip_adapter, which also states the index order of the cross-attentions).
+        No image encoder is loaded (`image_encoder_folder` must be None): register a duck-typed `image_encoder` and
+        `feature_extractor` on the pipeline, or pass `ip_adapter_image_embeds`."""
+        if image_encoder_folder is not None:
+            raise L.PPError("load_ip_adapter: image_encoder_folder is not supported (no image encoder is loaded here): pass "
+                            "image_encoder_folder=None and register pipe.image_encoder / pipe.feature_extractor yourself")
+        if kwargs.get("ip_adapter_masks") is not None:
+            raise L.PPError("load_ip_adapter: ip_adapter_masks are not implemented on the HIP path")
+        srcs = pretrained_model_name_or_path_or_dict
+        srcs = list(srcs) if isinstance(srcs, (list, tuple)) else [srcs]
+
+        def per(v, what):
+            v = list(v) if isinstance(v, (list, tuple)) else [v] * len(srcs)
+            if len(v) != len(srcs):
+                raise ValueError(f"`{what}` must have the same length as the number of adapters ({len(srcs)})")
+            return v
+
+        sds = [IPA.read_ip_adapter(s_, sf, wn) for s_, sf, wn in zip(srcs, per(subfolder, "subfolder"),
+                                                                     per(weight_name, "weight_name"))]
+        self.unet._load_ip_adapter_weights(sds)
+
+    def set_ip_adapter_scale(self, scale):
+        self.unet.set_ip_adapter_scale(scale)
+
+    def unload_ip_adapter(self):
+        """diffusers' `unload_ip_adapter`: the UNet of before `load_ip_adapter` (a registered image encoder stays: it was
+        never loaded here)."""
+        self.unet._unload_ip_adapter()
+
+    def encode_image(self, image, device, num_images_per_prompt, output_hidden_states=None):
+        """pipeline_PowerPaint_Brushnet_CA.py:632-654 through the registered (duck-typed) `image_encoder` /
+        `feature_extractor`; the unconditional embeds of a base adapter are zeros."""
+        if self.image_encoder is None:
+            raise ValueError("`ip_adapter_image` needs an `image_encoder` registered on the pipeline (none is: the HIP path has no "
+                             "CLIP vision tower of its own); register one, or pass `ip_adapter_image_embeds`")
+        if output_hidden_states:
+            raise L.PPError("encode_image(output_hidden_states=True) serves IP-Adapter Plus, which is not implemented")
+        dtype = next(self.image_encoder.parameters()).dtype
+        if not isinstance(image, torch.Tensor):
+            if self.feature_extractor is None:
+                raise ValueError("`ip_adapter_image` that is not a tensor needs a `feature_extractor` registered on the pipeline")
+            image = self.feature_extractor(image, return_tensors="pt").pixel_values
+        image = image.to(device=device, dtype=dtype)
+        image_embeds = self.image_encoder(image).image_embeds
+        image_embeds = image_embeds.repeat_interleave(num_images_per_prompt, dim=0)
+        return image_embeds, torch.zeros_like(image_embeds)
+
+    def prepare_ip_adapter_image_embeds(self, ip_adapter_image, ip_adapter_image_embeds, device, num_images_per_prompt,
+                                        do_classifier_free_guidance):
+        """pipeline_PowerPaint_Brushnet_CA.py:657-706: one [B, n, D] tensor per adapter, under CFG the negative embeds in the
+        first half of the batch (precomputed embeds carry them there already and are `chunk(2)`ed for the repeat)."""
+        layers = getattr(getattr(self.unet, "encoder_hid_proj", None), "image_projection_layers", None)
+        if layers is None:
+            raise ValueError("an IP-Adapter image prompt was given but no IP-Adapter is loaded: call `load_ip_adapter` first "
+                             "(the prompt is never silently dropped)")
+        out = []
+        if ip_adapter_image_embeds is None:
+            if not isinstance(ip_adapter_image, list):
+                ip_adapter_image = [ip_adapter_image]
+            if len(ip_adapter_image) != len(layers):
+                raise ValueError(f"`ip_adapter_image` must have same length as the number of IP Adapters. Got "
+                                 f"{len(ip_adapter_image)} images and {len(layers)} IP Adapters.")
+            for img, layer in zip(ip_adapter_image, layers):
+                pos, neg = self.encode_image(img, device, 1, not isinstance(layer, IPA.ImageProjection))
+                pos = torch.stack([pos] * num_images_per_prompt, dim=0)
+                neg = torch.stack([neg] * num_images_per_prompt, dim=0)
+                out.append(torch.cat([neg, pos]).to(device) if do_classifier_free_guidance else pos)
+        else:
+            for e in ip_adapter_image_embeds:
+                ones = [1] * (e.dim() - 1)
+                if do_classifier_free_guidance:
+                    neg, pos = e.chunk(2)
+                    e = torch.cat([neg.repeat(num_images_per_prompt, *ones), pos.repeat(num_images_per_prompt, *ones)])
+                else:
+                    e = e.repeat(num_images_per_prompt, *ones)
+                out.append(e)
+        return out
+
+    @staticmethod
+    def _check_ip_inputs(ip_adapter_image, ip_adapter_image_embeds):
+        """The IP-Adapter branches of `check_inputs`, pipeline_PowerPaint_Brushnet_CA.py:853-866."""
+        if ip_adapter_image is not None and ip_adapter_image_embeds is not None:
+            raise ValueError("Provide either `ip_adapter_image` or `ip_adapter_image_embeds`. Cannot leave both "
+                             "`ip_adapter_image` and `ip_adapter_image_embeds` defined.")
+        if ip_adapter_image_embeds is not None:
+            if not isinstance(ip_adapter_image_embeds, list):
+                raise ValueError(f"`ip_adapter_image_embeds` has to be of type `list` but is {type(ip_adapter_image_embeds)}")
+            elif ip_adapter_image_embeds[0].ndim not in [3, 4]:
+                raise ValueError(f"`ip_adapter_image_embeds` has to be a list of 3D or 4D tensors but is "
+                                 f"{ip_adapter_image_embeds[0].ndim}D")
+
     @torch.no_grad()
     def __call__(self, promptA: Union[str, List[str]] = None, promptB: Union[str, List[str]] = None,
                  promptU: Union[str, List[str]] = None, tradoff: float = 1.0, tradoff_nag: float = 1.0, image=None,
@@ -129,8 +229,7 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
                  negative_prompt_embedsU: Optional[torch.FloatTensor] = None, **kwargs):
         callback = kwargs.pop("callback", None)
         callback_steps = kwargs.pop("callback_steps", 1)
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
-            raise NotImplementedError("IP-Adapter is outside the PowerPaint hot path (never enabled by app.py)")
+        self._check_ip_inputs(ip_adapter_image, ip_adapter_image_embeds)
         if isinstance(control_guidance_start, list):
             control_guidance_start = control_guidance_start[0]
         if isinstance(control_guidance_end, list):
@@ -160,6 +259,11 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
         prompt_embedsU = self.encode_prompt(promptU, device, num_images_per_prompt, do_cfg, negative_promptU,
                                             prompt_embeds=prompt_embedsU, negative_prompt_embeds=negative_prompt_embedsU,
                                             lora_scale=lora_scale)
+        # :1279-1290 -- the image prompt (per call: no memo covers it); :1363-1366 -- for the UNet only
+        added_cond_kwargs = None
+        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
+            added_cond_kwargs = {"image_embeds": self.prepare_ip_adapter_image_embeds(
+                ip_adapter_image, ip_adapter_image_embeds, device, batch_size * num_images_per_prompt, do_cfg)}
         nb = batch_size * num_images_per_prompt
         # 4./6.1 conditioning latents: [VAE latents of the masked image | latent-resolution keep-mask]
         if conditioning_latents is None:
@@ -213,7 +317,8 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
         self._loop.bind(shape, do_cfg, guidance_scale, prompt_embedsU, prompt_embeds_side=prompt_embeds,
                         side_static_inputs=[(conditioning_latents, self.unet.config.in_channels)],
                         side_scale=scales[0], guess_mode=guess_mode, eta=eta, generator=generator,
-                        noise_dtype=self._noise_dtype(prompt_embeds), timestep_cond=timestep_cond)
+                        noise_dtype=self._noise_dtype(prompt_embeds), timestep_cond=timestep_cond,
+                        added_cond_kwargs=added_cond_kwargs)
         cb = None
         bad = [k for k in callback_on_step_end_tensor_inputs if k not in self._callback_tensor_inputs]
         if bad:                                                                              # check_inputs, :775-780

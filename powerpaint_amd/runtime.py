@@ -36,8 +36,39 @@ class NetRuntime:
         self.gemm_splitk = 0
 
     # ------------------------------------------------------------------ build
+    def _ip_cells(self, n: int):
+        """One ctypes.c_float per loaded IP-Adapter: the by-value `ip_scale` of its pp_ip_attn_add launches.  The cells outlive
+        the plans (a rebuilt plan keeps the scales that were set)."""
+        cells = self.__dict__.setdefault("_ip_scale_cells", [])
+        del cells[n:]
+        while len(cells) < n:
+            cells.append(C.c_float(1.0))
+        return cells
+
+    def set_ip_scales(self, scales: Sequence[float]):
+        """Per-adapter scales: eager runs see the new values at once; a captured graph carries by-value arguments, so this
+        runtime's graph is dropped and `ip_scales()` tells a loop that captured the plan inside its own graph to re-capture."""
+        cells = self._ip_cells(len(scales))
+        if [c.value for c in cells] != [C.c_float(float(v)).value for v in scales]:
+            for c, v in zip(cells, scales):
+                c.value = float(v)
+            self.graph = None
+
+    def ip_scales(self) -> Tuple[float, ...]:
+        return tuple(c.value for c in self.__dict__.get("_ip_scale_cells", [])[:len(getattr(self.net, "ip", []))])
+
+    def set_ip_embeds(self, embeds: Optional[Sequence[torch.Tensor]]):
+        """The call's image embeds, one [B, n, D] tensor per loaded adapter, copied into the setup plan's inputs; the setup plan
+        runs again at the next set_context (the embeds change per call: they are never assumed unchanged)."""
+        if "ip_in" not in self.lay:
+            return
+        for (ptr, n), (T, D), e in zip(self.lay["ip_in"], self.net.ip, embeds):
+            dst = self.arena.view(ptr, (self.B * n, D), self.net.dtype, strides=(_align(D, 64), 1))
+            dst.copy_(e.reshape(self.B * n, D).to(self.device))
+        self._ctx_id = None
+
     def _build(self, arena: Arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond=False, twin=False,
-               freeu=False):
+               freeu=False, ip_n=()):
         net = self.net
         pb_setup = Builder(arena, dtype=net.dtype)
         pb_setup.gemm_tile, pb_setup.gemm_splitk = self.gemm_tile, self.gemm_splitk
@@ -67,7 +98,15 @@ class NetRuntime:
             slots = {k: [Act(arena.alloc(b * h * w * c * 2), b, h, w, c) for (b, c, h, w) in v]
                      for k, v in shapes.items()}
         lay["slots"] = slots
-        net.build_setup(pb_setup, B, nctx, lay["ehs"], cond, hw0=(H, W))
+        ip_kw = {}
+        if getattr(net, "ip", None):
+            # IP-Adapters: the call's image embeds, 16-bit [B][n][D rounded up to 64] per adapter (set_ip_embeds; the pad columns
+            # stay the arena's zeros), and one by-value scale cell per adapter shared by all its launches (set_ip_scales)
+            if len(ip_n) != len(net.ip):
+                raise L.PPError(f"{len(net.ip)} IP-Adapters are loaded: the plan needs the image count of each")
+            lay["ip_in"] = [(arena.alloc(B * n * _align(D, 64) * 2), n) for (T, D), n in zip(net.ip, ip_n)]
+            ip_kw = dict(ip_in=lay["ip_in"], ip_scales=self._ip_cells(len(net.ip)))
+        net.build_setup(pb_setup, B, nctx, lay["ehs"], cond, hw0=(H, W), **ip_kw)
         pb = Builder(arena, dtype=net.dtype)
         pb.gemm_tile, pb.gemm_splitk = self.gemm_tile, self.gemm_splitk
         pb.gn_acc_base, pb.gn_acc_cap = lay["gn_acc"], gn_cap
@@ -130,9 +169,10 @@ class NetRuntime:
         return out
 
     def ensure(self, B: int, H: int, W: int, nctx: int, cin_total: int, wiring=("plain",), cond_hw=None,
-               scale: float = 1.0, pad_uncond: bool = False, twin: bool = False, freeu=None):
+               scale: float = 1.0, pad_uncond: bool = False, twin: bool = False, freeu=None, ip_n=()):
         """freeu: None, or (s1, s2, b1, b2) of UNet2DConditionModel.enable_freeu -- on / off is part of the plan key (the
         plan gains one pp_freeu launch per resnet of up blocks 0 and 1), the values live in device memory the launches read.
+        ip_n: images per loaded IP-Adapter in this call's embeds (part of the key only while adapters are loaded).
         twin: the caller vouches that the second half of every network input (x_in, ControlNet conditioning) equals the
         first -- a CFG pair built from one tensor; the step plan then runs the prompt-independent prefix on one half
         (SDNet.build_step)."""
@@ -143,6 +183,9 @@ class NetRuntime:
 
         key = (B, H, W, nctx, cin_total, freeze(wiring), cond_hw, self.gemm_tile, self.gemm_splitk, bool(pad_uncond),
                bool(twin)) + (("freeu",) if freeu is not None else ())      # (without FreeU: the key of a plan that never had it)
+        ip = getattr(getattr(self, "net", None), "ip", None)
+        if ip:
+            key += (("ip", tuple(ip), tuple(int(n) for n in ip_n)),)
         if isinstance(scale, (list, tuple)):
             scale = tuple(float(v) for v in scale)       # (one representation: a list never equals the stored tuple)
         if key == self.key:
@@ -154,10 +197,10 @@ class NetRuntime:
         #  workgroups placed on the XCDs round-robin by linear id?  Plans combine split-K in-kernel only if so.)
         self.xcd_placement_ok = bool(self.lib.pp_xcd_placement_ok())
         dry = Arena()
-        self._build(dry, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None)
+        self._build(dry, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None, ip_n)
         self.arena = Arena(_align(dry.peak, 4096), self.device)
         self.lay, self.setup_plan, self.step_plan, self.outputs = self._build(
-            self.arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None)
+            self.arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None, ip_n)
         self.twin = bool(twin)
         self.pad_uncond = bool(pad_uncond)
         self.key = key
