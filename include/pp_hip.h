@@ -481,11 +481,12 @@ int pp_add_bf16(const void* a, const void* b, void* out, long long n, int dtype,
  * Replaces pipeline_PowerPaint.py:1018-1023 / pipeline_PowerPaint_Brushnet_CA.py:1444-1449:
  *     eps = eps_u + g * (eps_c - eps_u);  latents = scheduler.step(eps, t, latents)
  * eps2 : fp32 [2*n] (uncond half first, pipeline_PowerPaint.py:516) when cfg != 0, else [n].
- * The step is the linear form  x_next = cx * x + ce * eps_or_x0 + cm * m_prev  with per-step coefficients read from a
- * DEVICE table coef[step][8] = {cx, c0, cm, a_inv, s_over_a, _, _, _} and a device step counter:
- *     x0   = a_inv * x - s_over_a * eps          (DPM-Solver++ data prediction; DDIM: folded into cx/c0)
- *     kind 0 (DDIM, eta=0): x_next = cx * x + c0 * eps
- *     kind 1 (DPM-Solver++ 2M): x_next = cx * x + c0 * x0 + cm * m_prev ; m_prev <- x0
+ * Per-step coefficients are read from a DEVICE table coef[step][8] = {c0 .. c5, _, _} and a device step counter:
+ *     x0   = (x - c0 * eps) / c1                  (c0 = sqrt(1 - a_t), c1 = sqrt(a_t): the data prediction)
+ *     kind 0 (DDIM): x_next = c2 * x0 + c3 * eps   (c2 = sqrt(a_prev), c3 = sqrt(1 - a_prev - std_dev_t^2); c4 = std_dev_t is
+ *             read by pp_ddim_variance_noise only)
+ *     kind 1 (DPM-Solver++ 2M): d1 = c5 * (x0 - m_prev);  x_next = c2 * x - c3 * x0 - c4 * d1;  m_prev <- x0
+ *             (c2 = sigma_next / sigma_t, c3 = alpha_next (exp(-h) - 1), c4 = c3 / 2 or 0 on first-order steps, c5 = 1 / r0)
  *     kind 2 (PNDM / PLMS, PNDMScheduler(skip_prk_steps=True) -- the scheduler the SD-1.5 checkpoint config names):
  *             table rows are 16 floats {w0..w3, a, b, slot(h1), slot(h2), slot(h3), push_slot | -1, use_saved, save};
  *             m = w0 eps + w1 h1 + w2 h2 + w3 h3;  x_next = a * (use_saved ? saved : x) + b * m;  `m_prev` is the state
@@ -701,6 +702,9 @@ int pp_embed_splice(const void* table, const void* ext, const int32_t* src_row, 
  * kernel; pp_attention_fwd covers the UNet's head dims only.  lds / ldp: row strides in elements (multiples of 4).
  * (ABI v29) Columns [n, ldp) of every row of p are WRITTEN as zeros: a caller whose second GEMM needs K % 64 == 0 pads ldp
  * to it and multiplies the pad columns with zero-padded V^T columns (pp_transpose_v), whatever the buffer held before.
+ * CONTRACT: every logit times scale * log2(e) must be FINITE in fp32.  The running maximum starts at -inf, so a thread whose
+ * first four logits are all -inf (or overflow to it) forms exp2(-inf - -inf) = NaN and the whole row is NaN; a masked logit
+ * is a large finite negative number, not -inf.  +-FLT_MAX / 2 at scale 0.5 is inside the contract (tests/small_cases.py).
  */
 int pp_softmax_rows(const float* s, long long lds, int rows, int n, float scale, void* p, long long ldp, int dtype,
                     void* stream);

@@ -981,6 +981,11 @@ template <int EDT>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ s, long long lds, int n,
                                                            float scale_log2e, uint16_t* __restrict__ p,
                                                            long long ldp) {
+  // No fused multiply-subtract in here: exp2f(s * l - M) with the product left unrounded inside an fma differs from the
+  // rounded product that M was taken from by up to |s l| 2^-24 in the EXPONENT -- nothing for attention logits, but the row
+  // maximum itself then gives exp2f(+-7e30) instead of exp2f(0) once |s l| reaches 1e38, and the row is NaN although every
+  // logit is finite (pp_hip.h: the contract is finite logits, no more).  Every pass sees the same rounded s * l.
+#pragma clang fp contract(off)
   __shared__ float red_m[4], red_s[4];
   const float* row = s + (long long)blockIdx.x * lds;
   uint16_t* out = p + (long long)blockIdx.x * ldp;

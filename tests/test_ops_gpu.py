@@ -503,7 +503,8 @@ def test_conv_direct(cin, cout, stride):
 @pytest.mark.parametrize("B,H,cin", [(2, 16, 320),      # UNet conv_out: the MFMA kernel (cin % 32 == 0)
                                      (1, 6, 128),       # 36 pixels: a ragged last 16-pixel group; VAE decoder width
                                      (3, 5, 32),        # one 32-deep step: three of the four waves contribute zeros
-                                     (1, 8, 416),       # 13 steps: a second load round with one live step
+                                     (1, 8, 384),       # twelve 32-deep steps: the MFMA kernel's full load, all three rounds live
+                                     (1, 8, 416),       # cin > 384: the host routes it to the scalar kernel
                                      (2, 8, 24)])       # cin % 32 != 0: the scalar kernel
 def test_conv_smallcout(B, H, cin):
     x = bf(rnd(B, H, H, cin, seed=1))
