@@ -569,7 +569,17 @@ int pp_cfg_ksampler_step(const float* eps2, int cfg, float guidance, float* late
  * up to the fp32 summation order.  pp_tfront_supported() = 1 for c = 320, 128-row tiles inside one batch item.
  * q_scale (ABI v20): the Q third is multiplied by it in fp32 before its one rounding to 16 bits -- 1.0 for
  * pp_attention_fwd, head_dim^-0.5 * log2(e) for PP_ATTN_PIPE_LOG2.  hs and qk: 16-byte aligned, ldhs % 8 == ldqk % 8 == 0
- * (round 6: the rows leave as whole 128-byte lines). */
+ * (round 6: the rows leave as whole 128-byte lines).
+ * Pinned by tests/test_tblock_exact_gpu.py:
+ *   - gn_acc is TRUSTED as given: mean = sum / n, var = max(q / n - mean^2, 0) in fp64 with n = rows_per_batch * (c / gn_groups),
+ *     rstd = (float)(1 / sqrt(var + gn_eps)); the kernel never looks at whether x has those moments.  One table per batch item
+ *     b = (first row of the 128-row tile) / rows_per_batch; gn_groups: every divisor of 320 up to 32.
+ *   - rounding points: the normalised row x * (rstd gamma) + (beta - mean rstd gamma) once to 16 bits; hs = that . w1^T + b1 once to
+ *     16 bits; the LayerNorm1 moments from the STORED hs; each of Q * q_scale, K, V once.  q_scale touches the Q third only:
+ *     two calls that differ in q_scale alone leave hs, K and V^T bit-identical.
+ *   - V^T of tile rows [m0, m0 + 128) goes to vt[b][channel][m0 - b * rows_per_batch ..]; ldvt >= rows_per_batch, ldvt % 8 == 0,
+ *     ldx >= c, ldhs >= c, ldqk >= 2 c (PP_ERR_BAD_ARG otherwise).  x may carry anything (NaN included) in the columns behind c;
+ *     nothing is written outside the [M][c], [M][2 c] and [batch][c][rows_per_batch] windows. */
 int pp_tfront_supported(int M, int c, int rows_per_batch, int gn_groups);
 int pp_tfront(const void* x, int ldx, const void* gn_acc, const float* gn_gamma, const float* gn_beta, float gn_eps, int gn_groups,
               const void* w1, const float* b1, const void* w2p, const float* cs2, const float* b2, float ln_eps, void* hs,
@@ -611,7 +621,20 @@ int pp_tfront(const void* x, int ldx, const void* gn_acc, const float* gn_gamma,
  *     P   = pp_gemm_bf16(x, w = gt, w_batch_stride = 640 c, bias = gbias, ln_colsum = gcs, vec_batch_stride = 640,
  *                        ln_stats, act = PP_ACT_SOFTMAX80)                          [M][640] probabilities
  *     out = pp_gemm_bf16(P, w = ht, w_batch_stride = 640 c, bias = bias_o, res1 = h, row_stats_out)
- * with half the multiplications of the chain at C = 1280 (2 x 640 c per row instead of 2 c^2 + 4 * 77 c). */
+ * with half the multiplications of the chain at C = 1280 (2 x 640 c per row instead of 2 c^2 + 4 * 77 c).
+ * Pinned by tests/test_tblock_exact_gpu.py:
+ *   - pp_xattn_fold: gt = round16(fl32(fl32(sum) * fl32(scale * log2 e))), one rounding to 16 bits; gbias the same product kept in
+ *     fp32; ht = round16(sum); gcs = 0 without q_colsum, else the fp32 sum of the STORED gt row (q_colsum itself is only a
+ *     flag: its values are not read); padded keys (key >= nctx): gt row 0, gbias -inf, ht column 0.  kperm: bit 0 permutes the
+ *     channel index of gt (C = 320 only), bit 1 leaves the contraction index of ht in natural order; 3 is PP_ERR_BAD_ARG.
+ *     k may carry anything behind column c (ldk >= c), vt behind column nctx (ldvt >= nctx); gt / gcs / gbias / ht are dense.
+ *   - pp_xattn_block: the probabilities are rounded once to 16 bits, the output once; the tables of batch item
+ *     b = (first row of the tile) / rows_per_batch (of the FULL batch under src_wrap_rows); row_stats_out splits a row at every
+ *     160 columns.  pre_w: h is rounded once, parked in the tile's own rows of `out` (never wrapped) and read back as the
+ *     residual; x, res and ln_stats are wrapped, `out`, row_stats_out and the folded operands are not.  C = 640 / 1280
+ *     (64-row tiles, one 320-column group per workgroup): no pre_w, no src_wrap_rows (PP_ERR_UNSUPPORTED).
+ *     x / res may carry anything behind column c; out and res 16-byte aligned, ldx, ldo, ldres >= c and multiples of 8,
+ *     src_wrap_rows a multiple of rows_per_batch with M <= 2 src_wrap_rows, pre_b only with pre_w (PP_ERR_BAD_ARG otherwise). */
 int pp_xattn_block_supported(int M, int c, int rows_per_batch, int nctx, int heads);
 int pp_xattn_fold(const void* k, int ldk, const void* vt, int ldvt, int batch, int nctx, int heads, int c, const void* wq,
                   const float* q_colsum, const float* q_bias, const void* wo, float scale, void* gt, float* gcs,
@@ -639,7 +662,21 @@ int pp_xattn_block(const void* x, int ldx, const void* res, int ldres, const flo
  *   b1 / cs1 : [2560] fp32 bias (incl. W beta) and column sums of w1 (cs1 may be NULL when ln_stats is NULL);
  *   ln_stats : row moments of hs in the layout of PPGemmArgs.ln_stats (ln_tiles partials per row) or NULL (no LayerNorm folded).
  * Arithmetic = the two-launch chain up to the fp32 summation order of the second GEMM (the GEGLU values are rounded to the
- * 16-bit format exactly where the chain stores them).  pp_ff_fused_supported(): c == 320, M and rows_per_batch multiples of 128. */
+ * 16-bit format exactly where the chain stores them).  pp_ff_fused_supported(): c == 320, M and rows_per_batch multiples of 128.
+ * w2_kperm: 1 = W2' with the hidden index permuted as above (four waves, the GEGLU chained in registers); 0 = W2' in NATURAL
+ * hidden order (eight waves, the activations exchanged through LDS).  Both forms compute the same thing.
+ * Pinned by tests/test_tblock_exact_gpu.py:
+ *   - rounding points: h (.) gelu(g) once to 16 bits (gelu_fast_f: the gate +-16 gives exactly 16 / 0), the output once;
+ *   - epilogue order: out = (acc + bias) * scale + (res1 + res2) -- the scale does NOT touch the residuals;
+ *   - res1_wrap_rows > 0: res1 holds that many rows, M <= 2 res1_wrap_rows; the wrap is decided per 64-row PASS of the epilogue
+ *     (rows [m0, m0 + 64) read res1 rows m0 - wrap when m0 >= wrap), so res1_wrap_rows % 64 == 0 is all that is needed: a wrap
+ *     of 64 in the middle of a 128-row tile is honoured;
+ *   - gn_acc: the moments of the values AS STORED, per batch item (first row of the tile) / rows_per_batch, one slot set per
+ *     160-column half; gn_cg >= 8; the caller sizes gn_groups so that (gn_c0 + 319) / gn_cg < gn_groups (not checked);
+ *     integer accumulation: a repeated call gives equal bits;
+ *   - x2 / res1 / res2 may carry anything (NaN included) behind column 320; ldx2, ldo, ldres1, ldres2 >= 320 and multiples of
+ *     8; x2, out, res1 and res2 16-byte aligned (PP_ERR_BAD_ARG otherwise; the last two conditions are refused since these
+ *     tests: a short ldres or a misaligned base used to be launched). */
 int pp_ff_fused_supported(int M, int c, int rows_per_batch);
 int pp_ff_fused(const PPGemmArgs* g2, const void* w1, const float* b1, const float* cs1, const float* ln_stats, int ln_tiles,
                 float ln_eps, int w2_kperm, void* stream);

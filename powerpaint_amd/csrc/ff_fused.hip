@@ -783,7 +783,12 @@ extern "C" int pp_ff_fused(const PPGemmArgs* g2, const void* w1, const float* b1
   if (!pp_dt_ok(a.dtype) || a.x_mode != PP_X_PLAIN || !a.x2 || !a.w || !a.out) return PP_ERR_BAD_ARG;
   if (a.N != FF_C || a.K != FF_K2 || a.c1 != FF_HID || a.c2 != FF_C) return PP_ERR_UNSUPPORTED;
   if (!pp_ff_fused_supported(a.M, a.N, a.rows_per_batch > 0 ? a.rows_per_batch : FF_BM)) return PP_ERR_UNSUPPORTED;
-  if (a.ldx2 < FF_C || (a.ldx2 & 7) || a.ldo < FF_C || (a.ldo & 7) || (a.res1 && (a.ldres1 & 7)) || (a.res2 && (a.ldres2 & 7)))
+  if (a.ldx2 < FF_C || (a.ldx2 & 7) || a.ldo < FF_C || (a.ldo & 7) || (a.res1 && (a.ldres1 < FF_C || (a.ldres1 & 7))) ||
+      (a.res2 && (a.ldres2 < FF_C || (a.ldres2 & 7))))
+    return PP_ERR_BAD_ARG;
+  // (rows are read and written as 16-byte pieces: as pp_tfront and pp_xattn_block refuse a misaligned base)
+  if ((reinterpret_cast<uintptr_t>(a.x2) | reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.res1) |
+       reinterpret_cast<uintptr_t>(a.res2)) & 15)
     return PP_ERR_BAD_ARG;
   if (a.act != PP_ACT_NONE || a.out_f32 || a.out_vt || a.rowvec || a.row_stats_out || a.ln_stats || a.gn_next_out ||
       a.out_dup_rows || a.splitk > 1 || a.gn_in_acc)

@@ -91,6 +91,30 @@ def _view2d(t, rows: int, cols: int, dtype, like: torch.Tensor, what: str) -> to
     return t
 
 
+def _rows_in(t, cols: int, like: torch.Tensor, what: str) -> int:
+    """Row stride of a strided 2-D input [rows, cols] (a window of a larger buffer): unit column stride, rows that do not
+    overlap, the format and device of `like`.  What lies in the pad columns is never read."""
+    if t.dim() != 2 or t.shape[1] != cols or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < cols) or t.dtype != like.dtype \
+            or t.device != like.device:
+        raise L.PPError(f"{what}: must be a [rows, {cols}] row-major view (unit column stride) of the inputs' format")
+    return t.stride(0) if t.shape[0] > 1 else cols
+
+
+def _exact(t, shape, dtype, like: torch.Tensor, what: str) -> torch.Tensor:
+    """A caller-owned output the ABI has no stride for: contiguous, of exactly this shape and format."""
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.dtype != dtype or t.device != like.device:
+        raise L.PPError(f"{what}: must be a contiguous {list(shape)} tensor of {dtype}")
+    return t
+
+
+def _vt_window(t, nb: int, cols: int, rows: int, like: torch.Tensor, what: str) -> torch.Tensor:
+    """A caller-owned V^T output: a [nb, cols, rows] window of a contiguous [nb, cols, ld] buffer (ld = the view's stride(1))."""
+    if (t.dim() != 3 or tuple(t.shape) != (nb, cols, rows) or t.stride(2) != 1 or t.dtype != like.dtype or t.device != like.device
+            or t.stride(1) < rows or (nb > 1 and t.stride(0) != cols * t.stride(1))):
+        raise L.PPError(f"{what}: must be a [{nb}, {cols}, {rows}] window of a contiguous [nb, cols, ld] buffer of the inputs' format")
+    return t
+
+
 def _nhwc_view(t, shape, like: torch.Tensor, what: str) -> torch.Tensor:
     """A caller-owned NHWC conv output [B, H, W, C]: dense pixels whose channel stride (the kernel's ldo) is the view's pixel
     stride, i.e. a column window of a [B*H*W, ldo] buffer."""
@@ -438,54 +462,95 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, batch: int, he
 
 
 def xattn_fold(k: torch.Tensor, vt: torch.Tensor, batch: int, nctx: int, heads: int, wq: torch.Tensor, wo: torch.Tensor,
-               q_colsum=None, q_bias=None, scale: Optional[float] = None, kperm: bool = False):
+               q_colsum=None, q_bias=None, scale: Optional[float] = None, kperm=False, gt=None, gcs=None, gbias=None,
+               ht=None):
     """Once per prompt (pp_xattn_fold): k [batch*nctx, >=c], vt [batch, c, ldvt], wq / wo [c, c] ([out][in]) ->
-    (gt [batch, heads*80, c], gcs [batch, heads*80] fp32, gbias [batch, heads*80] fp32, ht [batch, c, heads*80])."""
+    (gt [batch, heads*80, c], gcs [batch, heads*80] fp32, gbias [batch, heads*80] fp32, ht [batch, c, heads*80]).
+    k may be a column window of wider rows (its row stride is ldk), vt a [batch, c, nctx] window of a contiguous
+    [batch, c, ldvt] buffer; what lies behind column c / nctx is not read.  kperm: False / True / 2 (include/pp_hip.h).
+    gt / gcs / gbias / ht: the caller's outputs, contiguous and of exactly those shapes (the ABI has no stride for them)."""
     c = wq.shape[0]
     dev, dt = k.device, k.dtype
-    gt = torch.empty(batch, heads * 80, c, dtype=dt, device=dev)
-    ht = torch.empty(batch, c, heads * 80, dtype=dt, device=dev)
-    gcs = torch.empty(batch, heads * 80, dtype=torch.float32, device=dev)
-    gb = torch.empty(batch, heads * 80, dtype=torch.float32, device=dev)
-    L.check(L.lib().pp_xattn_fold(_p(k), k.stride(0), _p(vt), vt.stride(1), batch, nctx, heads, c, _p(wq), _p(q_colsum),
+    if k.dim() != 2 or k.shape[0] != batch * nctx or k.shape[1] < c or k.stride(1) != 1 or (k.shape[0] > 1 and k.stride(0) < c):
+        raise L.PPError(f"xattn_fold: `k` must be [{batch * nctx}, >= {c}] rows with unit column stride")
+    if (vt.dim() != 3 or vt.shape[0] != batch or vt.shape[1] != c or vt.shape[2] < nctx or vt.stride(2) != 1 or vt.dtype != dt
+            or vt.stride(1) < nctx or (batch > 1 and vt.stride(0) != c * vt.stride(1))):
+        raise L.PPError(f"xattn_fold: `vt` must be a [{batch}, {c}, >= {nctx}] window of a contiguous [batch, c, ldvt] buffer")
+    for w_, nm in ((wq, "wq"), (wo, "wo")):
+        if tuple(w_.shape) != (c, c) or not w_.is_contiguous() or w_.dtype != dt:
+            raise L.PPError(f"xattn_fold: `{nm}` must be a contiguous [{c}, {c}] matrix of the inputs' format")
+    n = heads * 80
+    gt = torch.empty(batch, n, c, dtype=dt, device=dev) if gt is None else _exact(gt, (batch, n, c), dt, k, "xattn_fold: `gt`")
+    ht = torch.empty(batch, c, n, dtype=dt, device=dev) if ht is None else _exact(ht, (batch, c, n), dt, k, "xattn_fold: `ht`")
+    gcs = torch.empty(batch, n, dtype=torch.float32, device=dev) if gcs is None else \
+        _exact(gcs, (batch, n), torch.float32, k, "xattn_fold: `gcs`")
+    gb = torch.empty(batch, n, dtype=torch.float32, device=dev) if gbias is None else \
+        _exact(gbias, (batch, n), torch.float32, k, "xattn_fold: `gbias`")
+    L.check(L.lib().pp_xattn_fold(_p(k), k.stride(0) if k.shape[0] > 1 else k.shape[1], _p(vt), vt.stride(1), batch, nctx, heads, c, _p(wq), _p(q_colsum),
                                   _p(q_bias), _p(wo), scale if scale is not None else (c // heads) ** -0.5, _p(gt),
                                   _p(gcs), _p(gb), _p(ht), int(kperm), L.dtype_code(dt), _s()), "pp_xattn_fold")
     return gt, gcs, gb, ht
 
 
 def xattn_block(x: torch.Tensor, folded, bias_o=None, res=None, ln_stats=None, ln_eps: float = 1e-5,
-                rows_per_batch: int = 0, row_stats: bool = False, twin: bool = False, pre_w=None, pre_b=None,
-                ln_fold: bool = False):
+                rows_per_batch: int = 0, row_stats=False, twin: bool = False, pre_w=None, pre_b=None,
+                ln_fold: bool = False, out=None):
     """out = softmax_per_head(LNfold(x) gt^T) ht^T + bias_o + res  (pp_xattn_block); x [M, c], folded = xattn_fold(...).
     twin: x / res / ln_stats hold ONE half of a CFG pair (M rows) whose other half is identical; the output has 2 M rows
-    (src_wrap_rows = M) and `folded` is per batch item of the full batch."""
+    (src_wrap_rows = M) and `folded` is per batch item of the full batch.
+    x / res may be windows of wider rows (unit column stride; the pad columns are not read).  out: the caller's [M, c] view
+    with unit column stride (its row stride is ldo; what lies outside it is the caller's); row_stats: True, or the caller's
+    contiguous [M, c / 160, 2] fp32 tensor."""
     gt, gcs, gb, ht = folded
     wrap = x.shape[0] if twin else 0
     M, c = x.shape[0] * (2 if twin else 1), x.shape[1]
-    out = torch.empty(M, c, dtype=x.dtype, device=x.device)
-    st = torch.zeros(M, c // 160, 2, dtype=torch.float32, device=x.device) if row_stats else None
+    ldx = _rows_in(x, c, x, "xattn_block: `x`")
+    ldres = _rows_in(res, c, x, "xattn_block: `res`") if res is not None else 0
+    if res is not None and res.shape[0] != x.shape[0]:
+        raise L.PPError("xattn_block: `res` must have the rows of `x`")
+    nb = M // (rows_per_batch or M)
+    _exact(gt, (nb, 640, c), x.dtype, x, "xattn_block: folded gt")
+    _exact(ht, (nb, c, 640), x.dtype, x, "xattn_block: folded ht")
+    _exact(gcs, (nb, 640), torch.float32, x, "xattn_block: folded gcs")
+    _exact(gb, (nb, 640), torch.float32, x, "xattn_block: folded gbias")
+    out = torch.empty(M, c, dtype=x.dtype, device=x.device) if out is None else _view2d(out, M, c, x.dtype, x, "xattn_block: `out`")
+    if torch.is_tensor(row_stats):
+        st = _exact(row_stats, (M, c // 160, 2), torch.float32, x, "xattn_block: `row_stats`")
+        row_stats = True
+    else:
+        st = torch.zeros(M, c // 160, 2, dtype=torch.float32, device=x.device) if row_stats else None
     # pre_w / pre_b: the Linear in front (h = x pre_w^T + pre_b + res) in the same launch; `folded` must come from
     # xattn_fold(kperm=True); ln_fold = a LayerNorm of h is folded into `folded` (row moments are computed in the kernel)
     tiles = ln_stats.shape[1] if ln_stats is not None else (c // 160 if (pre_w is not None and ln_fold) else 0)
-    L.check(L.lib().pp_xattn_block(_p(x), x.stride(0), _p(res), res.stride(0) if res is not None else 0, _p(ln_stats),
+    L.check(L.lib().pp_xattn_block(_p(x), ldx, _p(res), ldres, _p(ln_stats),
                                    tiles, ln_eps, _p(gt), _p(gcs), _p(gb), _p(ht),
-                                   _p(bias_o), _p(out), c, _p(st), M, c, rows_per_batch or M, wrap, _p(pre_w), _p(pre_b),
+                                   _p(bias_o), _p(out), out.stride(0) if M > 1 else c, _p(st), M, c, rows_per_batch or M, wrap, _p(pre_w), _p(pre_b),
                                    L.dtype_code(x.dtype), _s()), "pp_xattn_block")
     return (out, st) if row_stats else out
 
 
 def ff_fused(hs: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2kp: torch.Tensor, bias2=None, cs1=None, ln_stats=None,
              ln_eps: float = 1e-5, res1=None, res2=None, res1_wrap: int = 0, rows_per_batch: int = 0, gn=None,
-             w2_kperm: bool = True):
-    """pp_ff_fused: out = [h (.) gelu(g) | hs] w2kp^T + bias2 + res1 + res2 with h | g = FF1(LayerNorm-folded hs), one launch.
+             w2_kperm: bool = True, scale: float = 1.0, out=None):
+    """pp_ff_fused: out = ([h (.) gelu(g) | hs] w2kp^T + bias2) * scale + res1 + res2 with h | g = FF1(LayerNorm-folded hs), one
+    launch.  hs / res1 / res2 may be windows of wider rows (unit column stride; the pad columns are not read; res1 holds
+    res1_wrap rows when that is set); out: the caller's [M, 320] view with unit column stride (its row stride is ldo).
     hs [M, 320]; w1 [2560, 320] (GEGLU-interleaved rows, gamma folded); w2kp [320, 1600]: w2_kperm=True -> hidden index
     permuted (engine._kperm_geglu; the 4-wave kernel that chains the GEGLU in registers), False -> natural order (the 8-wave
     kernel, activations exchanged through LDS); ln_stats [M, 2, 2] row moments of hs or None; gn: as ops.gemm takes them."""
     M, Cc = hs.shape
-    out = torch.empty(M, Cc, dtype=hs.dtype, device=hs.device)
-    a = L.gemm_args(L.dtype_code(hs.dtype), M, Cc, 4 * Cc, _p(hs), _p(w2kp), _p(out), x2=_p(hs), K2=Cc, ldx2=hs.stride(0),
-                    ldres1=res1.stride(0) if res1 is not None else 0, ldres2=res2.stride(0) if res2 is not None else 0,
-                    rows_per_batch=rows_per_batch)
+    ldx = _rows_in(hs, Cc, hs, "ff_fused: `hs`")
+    ld1 = _rows_in(res1, Cc, hs, "ff_fused: `res1`") if res1 is not None else 0
+    ld2 = _rows_in(res2, Cc, hs, "ff_fused: `res2`") if res2 is not None else 0
+    if res1 is not None and res1.shape[0] != (res1_wrap or M):
+        raise L.PPError(f"ff_fused: `res1` must have {res1_wrap or M} rows")
+    if res2 is not None and res2.shape[0] != M:
+        raise L.PPError(f"ff_fused: `res2` must have {M} rows")
+    if tuple(w1.shape) != (8 * Cc, Cc) or not w1.is_contiguous() or tuple(w2kp.shape) != (Cc, 5 * Cc) or not w2kp.is_contiguous():
+        raise L.PPError("ff_fused: `w1` / `w2kp` must be contiguous [2560, 320] / [320, 1600] matrices")
+    out = torch.empty(M, Cc, dtype=hs.dtype, device=hs.device) if out is None else _view2d(out, M, Cc, hs.dtype, hs, "ff_fused: `out`")
+    a = L.gemm_args(L.dtype_code(hs.dtype), M, Cc, 4 * Cc, _p(hs), _p(w2kp), _p(out), x2=_p(hs), K2=Cc, ldx2=ldx,
+                    ldo=out.stride(0) if M > 1 else Cc, ldres1=ld1, ldres2=ld2, rows_per_batch=rows_per_batch, scale=scale)
     a.bias, a.res1, a.res2, a.res1_wrap_rows = _p(bias2), _p(res1), _p(res2), res1_wrap
     _set_gn(a, gn, rows_per_batch)
     L.check(L.lib().pp_ff_fused(C.byref(a), _p(w1), _p(b1), _p(cs1), _p(ln_stats),
@@ -580,16 +645,26 @@ def linear_skinny(x: torch.Tensor, w: torch.Tensor, bias=None, act_in: int = 0, 
 
 
 def tfront(x: torch.Tensor, acc: torch.Tensor, gamma, beta, w1: torch.Tensor, b1, w2p: torch.Tensor, cs2, b2, rows_per_batch: int,
-           gn_eps: float = 1e-6, ln_eps: float = 1e-5, groups: int = 32, q_scale: float = 1.0):
+           gn_eps: float = 1e-6, ln_eps: float = 1e-5, groups: int = 32, q_scale: float = 1.0, hs=None, qk=None, vt=None):
     """pp_tfront: hs = proj_in(GroupNorm(x)); q | k | v = QKV(LayerNorm1(hs)), V transposed.  x [M, 320] raw rows, acc the
     int64 GroupNorm accumulators of x, w2p the gamma-folded QKV weight with engine._kperm applied.  -> (hs, qk [M, 640], vt).
-    q_scale multiplies the Q third before its rounding (head_dim^-0.5 * log2 e for L.PP_ATTN_PIPE_LOG2)."""
+    q_scale multiplies the Q third before its rounding (head_dim^-0.5 * log2 e for L.PP_ATTN_PIPE_LOG2).
+    x may be a window of wider rows (unit column stride; the pad columns are not read).  hs / qk: the caller's [M, 320] /
+    [M, 640] views with unit column stride (their row strides are ldhs / ldqk); vt: the caller's [nb, 320, rows_per_batch]
+    window of a contiguous [nb, 320, ldvt] buffer.  What lies outside the views is the caller's."""
     M, c = x.shape
+    if rows_per_batch <= 0 or M % rows_per_batch:
+        raise L.PPError("tfront: M must be a multiple of rows_per_batch")
     nb = M // rows_per_batch
-    hs = torch.empty(M, c, dtype=x.dtype, device=x.device)
-    qk = torch.empty(M, 2 * c, dtype=x.dtype, device=x.device)
-    vt = torch.empty(nb, c, rows_per_batch, dtype=x.dtype, device=x.device)
-    L.check(L.lib().pp_tfront(_p(x), x.stride(0), _p(acc), _p(gamma), _p(beta), gn_eps, groups, _p(w1), _p(b1), _p(w2p), _p(cs2),
-                              _p(b2), ln_eps, _p(hs), c, _p(qk), 2 * c, _p(vt), rows_per_batch, M, c, rows_per_batch,
+    ldx = _rows_in(x, c, x, "tfront: `x`")
+    if tuple(acc.shape) != (nb, groups, 2) or acc.dtype != torch.int64 or not acc.is_contiguous():
+        raise L.PPError(f"tfront: `acc` must be a contiguous int64 [{nb}, {groups}, 2] tensor")
+    hs = torch.empty(M, c, dtype=x.dtype, device=x.device) if hs is None else _view2d(hs, M, c, x.dtype, x, "tfront: `hs`")
+    qk = torch.empty(M, 2 * c, dtype=x.dtype, device=x.device) if qk is None else _view2d(qk, M, 2 * c, x.dtype, x, "tfront: `qk`")
+    vt = torch.empty(nb, c, rows_per_batch, dtype=x.dtype, device=x.device) if vt is None else \
+        _vt_window(vt, nb, c, rows_per_batch, x, "tfront: `vt`")
+    L.check(L.lib().pp_tfront(_p(x), ldx, _p(acc), _p(gamma), _p(beta), gn_eps, groups, _p(w1), _p(b1), _p(w2p), _p(cs2),
+                              _p(b2), ln_eps, _p(hs), hs.stride(0) if M > 1 else c, _p(qk), qk.stride(0) if M > 1 else 2 * c, _p(vt),
+                              vt.stride(1), M, c, rows_per_batch,
                               float(q_scale), L.dtype_code(x.dtype), _s()), "pp_tfront")
     return hs, qk, vt

@@ -403,11 +403,21 @@ def folded_pre(x, w16, cs, t, eps: float, terms):
     return z + td, dz
 
 
-def gate_folded_ln(x, w16, cs, t, eps: float, tiles: int, dtype, geglu: bool = False, terms=None):
+def plain_pre(x, w16, t):
+    """no LayerNorm folded (ln_stats NULL: mean = 0, rstd = 1): -> (ref = x w16^T + t, dz), as folded_pre: K u32 of the
+    absolute products, the (exact) multiplication by rstd = 1 and the addition of t: 3 u32"""
+    x, w = x.double(), w16.double()
+    td = t.double()
+    tabs = torch.where(torch.isfinite(td), td.abs(), torch.zeros_like(td))
+    z = x @ w.t()
+    return z + td, x.shape[1] * U32 * (x.abs() @ w.abs().t()) + 3.0 * U32 * (z.abs() + tabs)
+
+
+def gate_folded_ln(x, w16, cs, t, eps: float, tiles: int, dtype, geglu: bool = False, terms=None, fold: bool = True):
     """x [M, K] 16-bit, w16 [N, K] 16-bit (gamma folded in), cs [N] fp32 column sums, t [N] fp32 (bias + W beta) ->
     (ref, gate) fp64 [M, N] (GEGLU: [M, N / 2], value columns first, gate columns second).  terms: the moments' error
-    terms, default folded_ln_eps(tiles) (moments given, rounded once to fp32)"""
-    ref, dz = folded_pre(x, w16, cs, t, eps, terms or folded_ln_eps(tiles))
+    terms, default folded_ln_eps(tiles) (moments given, rounded once to fp32); fold=False: no LayerNorm (plain_pre)"""
+    ref, dz = folded_pre(x, w16, cs, t, eps, terms or folded_ln_eps(tiles)) if fold else plain_pre(x, w16, t)
     if geglu:
         h = ref.shape[1] // 2
         a, g, da, dg = ref[:, :h], ref[:, h:], dz[:, :h], dz[:, h:]
@@ -422,27 +432,36 @@ def quad_perm(n: int, device="cpu") -> torch.Tensor:
     return torch.cat([torch.stack([4 * q, 4 * q + 1], 1).reshape(-1), torch.stack([4 * q + 2, 4 * q + 3], 1).reshape(-1)])
 
 
-def gate_ff_fused(hs, w1, b1, cs1, w2, bias2, eps: float, dtype):
+def gate_ff_fused(hs, w1, b1, cs1, w2, bias2, eps: float, dtype, tiles: int = 0, fold: bool = True, scale: float = 1.0, res=()):
     """pp_ff_fused: out = round16(GEGLU(LN(hs) w1^T + b1)) w2a^T + hs w2b^T + bias2, w1 [8C, C] in interleaved quads with the
     LayerNorm's gamma folded in, w2 = [w2a | w2b] [C, 4C + C] in natural order.  The GEGLU values carry the folded-LayerNorm
     gate (their 16-bit rounding included); the second GEMM adds K2 u32 of its absolute products (K2 = 5C, any order) and
-    propagates the first through |w2a|.  -> (ref, gate) fp64 [M, C]"""
+    propagates the first through |w2a|.  tiles: partial moments per row (default C / 160); fold=False: ln_stats NULL (cs1 is not
+    read); the epilogue (acc + bias2) * scale + res[0] + res[1] (full [M, C] tensors, a wrapped one already expanded) adds
+    the product and the additions: 4 u32 of the magnitudes.  -> (ref, gate) fp64 [M, C]"""
     C = hs.shape[1]
     perm = quad_perm(w1.shape[0], w1.device)
-    act, g_act = gate_folded_ln(hs, w1[perm], cs1[perm], b1[perm], eps, C // 160, dtype, geglu=True)
+    act, g_act = gate_folded_ln(hs, w1[perm], cs1[perm] if fold else None, b1[perm], eps, tiles or C // 160, dtype, geglu=True,
+                                fold=fold)
     w2a, w2b = w2[:, :4 * C].double(), w2[:, 4 * C:].double()
     hd = hs.double()
-    ref = act @ w2a.t() + hd @ w2b.t() + bias2.double()
-    d = g_act @ w2a.abs().t() + 5 * C * U32 * ((act.abs() + g_act) @ w2a.abs().t() + hd.abs() @ w2b.abs().t() + bias2.double().abs())
+    b2 = bias2.double() if bias2 is not None else torch.zeros(C, dtype=torch.float64, device=hs.device)
+    ref = act @ w2a.t() + hd @ w2b.t() + b2
+    d = g_act @ w2a.abs().t() + 5 * C * U32 * ((act.abs() + g_act) @ w2a.abs().t() + hd.abs() @ w2b.abs().t() + b2.abs())
+    if scale != 1.0 or len(res):
+        rs = sum((r.double() for r in res), torch.zeros_like(ref))
+        ra = sum((r.double().abs() for r in res), torch.zeros_like(ref))
+        d = d * abs(scale) + 4 * U32 * (ref.abs() * abs(scale) + ra)
+        ref = ref * scale + rs
     return ref, _finish(ref, d, ref, False, dtype)
 
 
-def gate_tfront_hs(x, gg, gb, w1, b1, dtype):
+def gate_tfront_hs(x, gg, gb, w1, b1, dtype, groups: int = 32):
     """pp_tfront, first half: hs = round16(GroupNorm(x)) w1^T + b1, statistics from accumulators (x [B, hw, C], 32 groups,
     eps 1e-6, no SiLU).  The normalised values carry their GroupNorm gate (rounding included) through |w1|; the GEMM adds
     C u32 of its absolute products.  -> (ref, gate) fp64 [B * hw, C]"""
     C = x.shape[2]
-    n, gn = gate_groupnorm(x, None, 32, gg, gb, 1e-6, False, dtype, acc_eps())
+    n, gn = gate_groupnorm(x, None, groups, gg, gb, 1e-6, False, dtype, acc_eps())
     n, gn = n.reshape(-1, C), gn.reshape(-1, C)
     wa = w1.double().abs().t()
     ref = n @ w1.double().t() + b1.double()
@@ -450,9 +469,17 @@ def gate_tfront_hs(x, gg, gb, w1, b1, dtype):
     return ref, _finish(ref, d, ref, False, dtype)
 
 
-def gate_tfront_qkv(hs_stored, wf, cs, tb, dtype):
-    """pp_tfront, second half, from the hs the kernel stored: LayerNorm1 -> QKV with the moments formed in the kernel"""
-    return gate_folded_ln(hs_stored, wf, cs, tb, 1e-5, 2, dtype, terms=kernel_moments_eps())
+def gate_tfront_qkv(hs_stored, wf, cs, tb, dtype, q_scale: float = 1.0):
+    """pp_tfront, second half, from the hs the kernel stored: LayerNorm1 -> QKV with the moments formed in the kernel.
+    q_scale: the Q third (the first N / 3 columns) is multiplied by it in fp32 before its one rounding: one more u32"""
+    if q_scale == 1.0:
+        return gate_folded_ln(hs_stored, wf, cs, tb, 1e-5, 2, dtype, terms=kernel_moments_eps())
+    ref, dz = folded_pre(hs_stored, wf, cs, tb, 1e-5, kernel_moments_eps())
+    n = ref.shape[1] // 3
+    qs = float(np.float32(q_scale))
+    ref = torch.cat([ref[:, :n] * qs, ref[:, n:]], 1)
+    dz = torch.cat([dz[:, :n] * qs + U32 * ref[:, :n].abs(), dz[:, n:]], 1)
+    return ref, _finish(ref, dz, ref, False, dtype)
 
 
 XA_HEADS, XA_KP = 8, 80
@@ -465,13 +492,18 @@ def xattn_kk(device="cpu") -> torch.Tensor:
     return 32 * s32 + 16 * (j // 4) + 4 * kg + (j % 4)
 
 
-def gate_xattn_block(x, st_tiles: int, folded, bo, res, rows_per_batch: int, eps: float, dtype):
+def gate_xattn_block(x, st_tiles: int, folded, bo, res, rows_per_batch: int, eps: float, dtype, fold: bool = True, terms=None):
     """pp_xattn_block with the moments given: l = LN(x) gt^T + gbias (exp2 domain), p = softmax2 per head over 80 key slots,
     out = round16(p) ht^T + bo + res.  A logit error <= D (fp32 products included: 2 u32 (|l| + |max|)) moves a probability by
     at most p (2^(2 D) - 1); the sum of 80 exponentials, v_exp, v_rcp and the product add 88 u32 p; p is rounded to 16
     bits (u p); the second GEMM adds 640 u32 of its absolute products, the bias and residual adds 2 u32.
+    x [M, K] (K = C: 320, 640 or 1280), bo / res may be None; fold=False: ln_stats NULL (plain_pre; gcs is not used); terms:
+    the moments' error terms, default folded_ln_eps(st_tiles) (kernel_moments_eps() where the kernel forms them: pre_w).
     -> (ref, gate) fp64 [M, C]"""
     gt, gcs, gb, ht = folded
+    zc = torch.zeros(x.shape[1], dtype=torch.float64, device=x.device)
+    bo = zc if bo is None else bo.double()
+    res = torch.zeros(x.shape, dtype=torch.float64, device=x.device) if res is None else res.double()
     u = unit_roundoff(dtype)
     M, C = x.shape
     kk = xattn_kk(x.device)
@@ -479,7 +511,7 @@ def gate_xattn_block(x, st_tiles: int, folded, bo, res, rows_per_batch: int, eps
     d = torch.empty_like(ref)
     for b in range(M // rows_per_batch):
         r = slice(b * rows_per_batch, (b + 1) * rows_per_batch)
-        l, dl = folded_pre(x[r], gt[b], gcs[b], gb[b], eps, folded_ln_eps(st_tiles))
+        l, dl = folded_pre(x[r], gt[b], gcs[b], gb[b], eps, terms or folded_ln_eps(st_tiles)) if fold else plain_pre(x[r], gt[b], gb[b])
         lh = l.reshape(-1, XA_HEADS, XA_KP)
         live = torch.isfinite(lh)
         mx = torch.where(live, lh, torch.full_like(lh, -1e300)).max(-1, keepdim=True).values
@@ -491,8 +523,8 @@ def gate_xattn_block(x, st_tiles: int, folded, bo, res, rows_per_batch: int, eps
         hta = ht[b].double()                                                   # [C, 640], position kp holds key kk[kp]
         o = p[:, kk] @ hta.t()
         A = p[:, kk] @ hta.abs().t()
-        ref[r] = o + bo.double() + res[r].double()
-        d[r] = dp[:, kk] @ hta.abs().t() + 640 * U32 * A + 2 * U32 * (o.abs() + bo.double().abs() + res[r].double().abs())
+        ref[r] = o + bo + res[r]
+        d[r] = dp[:, kk] @ hta.abs().t() + 640 * U32 * A + 2 * U32 * (o.abs() + bo.abs() + res[r].abs())
     return ref, _finish(ref, d, ref, False, dtype)
 
 
@@ -566,9 +598,10 @@ FF_M, FF_C = 128, 320                    # the smallest shape pp_ff_fused accept
 FUSED_REGIMES = ("offset16", "outlier")
 
 
-def build_ff_case(regime: str, dtype):
-    """hs [128, 320] of the regime and a feed-forward's weights in the layouts of tests/test_ff_fused_gpu.py::_case"""
-    C, M = FF_C, FF_M
+def build_ff_case(regime: str, dtype, M: int = FF_M, tiles: int = 2):
+    """hs [M, 320] of the regime and a feed-forward's weights in the layouts of tests/test_ff_fused_gpu.py::_case; the row
+    moments st in `tiles` partials per row (column tiles of 320 / tiles)"""
+    C = FF_C
     hs = build_x(regime, dtype, M, 1, C, 1, 0.0, key=3).reshape(M, C)
     g = _gen(17, C)
     gam = torch.randn(C, generator=g) * 0.3 + 1.0
@@ -580,7 +613,7 @@ def build_ff_case(regime: str, dtype):
     w1 = (w_ff1 * gam[None, :])[inv].to(dtype).contiguous()
     b1 = b_ff1[inv].contiguous()
     cs1 = w1.double().sum(1).float()
-    S, Q, _ = row_tile_sums(hs)
+    S, Q, _ = row_tile_sums(hs, C // tiles)
     return dict(hs=hs, w1=w1, b1=b1, cs1=cs1, w2=w2.contiguous(), bias2=bias2, st=torch.stack([S, Q], -1).float().contiguous())
 
 
@@ -804,11 +837,11 @@ TF_B, TF_HW, TF_C = 1, 128, 320              # the smallest shape pp_tfront acce
 XA_B, XA_HW, XA_NCTX, XA_C = 2, 128, 7, 320  # ... and pp_xattn_block (one 128-row tile per batch item)
 
 
-def build_tfront_case(regime: str, dtype):
-    """x [1, 128, 320] of the regime; proj_in chosen so that the rows of hs -- what LayerNorm1 sees -- are in the regime
+def build_tfront_case(regime: str, dtype, B: int = TF_B, hw: int = TF_HW, groups: int = 32):
+    """x [B, hw, 320] of the regime; proj_in chosen so that the rows of hs -- what LayerNorm1 sees -- are in the regime
     too: offset16 adds 16 to its bias (hs has unit spread), outlier multiplies one output channel by 100."""
     C = TF_C
-    x = build_x(regime, dtype, TF_B, TF_HW, C, 32, 0.0, key=4)
+    x = build_x(regime, dtype, B, hw, C, groups, 0.0, key=4)
     g = _gen(19, C)
     gg, gb = torch.randn(C, generator=g) * 0.3 + 1.0, torch.randn(C, generator=g) * 0.2
     w1, b1 = torch.randn(C, C, generator=g) * C ** -0.5, torch.randn(C, generator=g) * 0.1
@@ -839,11 +872,12 @@ def emu_tfront(k, dtype, defect=None):
     return hs, qkv
 
 
-def build_xattn_case(regime: str, dtype):
-    """x [256, 320] of the regime and the folded matrices of a cross-attention over 7 context tokens, folded in fp64 and
+def build_xattn_case(regime: str, dtype, B: int = XA_B, hw: int = XA_HW, nctx: int = XA_NCTX, C: int = XA_C, tiles: int = 0):
+    """x [B hw, C] of the regime and the folded matrices of a cross-attention over nctx context tokens, folded in fp64 and
     rounded once: gt [B, 640, C] (logit weights, LayerNorm's gamma inside, exp2 domain), gcs = column sums of the stored gt,
-    gbias (-inf on the 73 empty key slots), ht [B, C, 640] in the k-permuted order of pp_xattn_fold."""
-    B, hw, nctx, C, H = XA_B, XA_HW, XA_NCTX, XA_C, XA_HEADS
+    gbias (-inf on the empty key slots), ht [B, C, 640] in the k-permuted order of pp_xattn_fold; st: the row moments in
+    `tiles` partials per row (default C / 160)."""
+    H = XA_HEADS
     d = C // H
     M = B * hw
     x = build_x(regime, dtype, M, 1, C, 1, 0.0, key=5).reshape(M, C)
@@ -863,7 +897,7 @@ def build_xattn_case(regime: str, dtype):
     hfull = torch.zeros(B, C, H, XA_KP, dtype=torch.float64)
     hfull[..., :nctx] = torch.einsum("nhd,bkhd->bnhk", wo.reshape(C, H, d), vc)
     ht = hfull.reshape(B, C, H * XA_KP).to(dtype)[:, :, xattn_kk()].contiguous()
-    S, Q, _ = row_tile_sums(x)
+    S, Q, _ = row_tile_sums(x, C // tiles if tiles else 160)
     return dict(x=x, gt=gt, gcs=gt.double().sum(-1).float().contiguous(), gb=gb.reshape(B, H * XA_KP).contiguous(), ht=ht,
                 bo=torch.randn(C, generator=g) * 0.1, st=torch.stack([S, Q], -1).float().contiguous())
 

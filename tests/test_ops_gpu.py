@@ -730,7 +730,8 @@ def test_fused_cross_attention_block(B, hw, nctx, C, fold, dtype):
     hf = h.float()
     if fold:
         tiles = C // 160
-        st = torch.stack([hf.reshape(M, tiles, 160).sum(-1), (hf * hf).reshape(M, tiles, 160).sum(-1)], -1).contiguous()
+        hd = h.double()                                    # (fp64 sums rounded once: what the derived gate below assumes)
+        st = torch.stack([hd.reshape(M, tiles, 160).sum(-1), (hd * hd).reshape(M, tiles, 160).sum(-1)], -1).float().contiguous()
         wqf = (wq * g2[None, :]).to(dtype).contiguous()
         cs, tq = wqf.float().sum(1).contiguous(), (wq @ b2).contiguous()
         x_in, kw_q, kw_f, ln = h, dict(ln_stats=st, ln_colsum=cs, ln_dim=C, bias=tq), dict(q_colsum=cs, q_bias=tq), st
@@ -752,6 +753,14 @@ def test_fused_cross_attention_block(B, hw, nctx, C, fold, dtype):
     o = torch.einsum("bhqk,bhdk->bqhd", p, vf).reshape(M, C)
     ref = o @ wod.float().t() + bo + hf
     check(out, ref, 1.0e-2 * tol, 4e-3 * tol, "fused cross-attention block vs fp32")
+    # ... and the derived gate of tests/norm_cases.py (rounding counts, nothing fitted) against fp64, from the folded operands
+    # as stored (pp_xattn_fold itself: tests/test_tblock_exact_gpu.py, bit for bit)
+    ref64, gate = NC.gate_xattn_block(x_in, C // 160, folded, bo, h, hw, 1e-5, dtype, fold=fold)
+    ratio = NC.worst_ratio(out, ref64, gate)
+    share = float((gate > 1.0e-2 * tol + 4e-3 * tol * ref64.abs()).double().mean())
+    print(f"[xattn_block] B={B} hw={hw} nctx={nctx} C={C} fold={fold} {dtype}: error / derived gate {ratio:.3f}; the gate is looser "
+          f"than the tolerance on {100 * share:.2f} % of the elements")
+    assert ratio <= 1.0, ("fused cross-attention block vs the derived gate", ratio)
     # (b) the chain it replaces
     q = ops.gemm(x_in, wqf, **kw_q)
     ao = ops.attention(q, k, vtp, B, heads, hw, nctx, d)
@@ -839,9 +848,7 @@ def test_transformer_front_end_in_one_launch(B, hw, dtype):
     M = B * hw
     tol = 4.0 if dtype == torch.bfloat16 else 1.0
     x = (rnd(M, C, seed=1, scale=1.4) + 0.3).to(dtype)
-    xf = x.float().reshape(B, hw, groups, C // groups)
-    acc = torch.stack([(xf.sum((1, 3)).double() * 2 ** 24).round().long(),
-                       ((xf * xf).sum((1, 3)).double() * 2 ** 20).round().long()], -1).contiguous()
+    acc = NC.build_acc(x.view(B, hw, C), None, groups).contiguous()       # (fp64 sums rounded once: what the derived gate assumes)
     gg, gb = rnd(C, seed=2) * 0.3 + 1.0, rnd(C, seed=3) * 0.2
     w1, b1 = rnd(C, C, seed=4, scale=C ** -0.5).to(dtype).contiguous(), rnd(C, seed=5) * 0.1
     g1, be1 = rnd(C, seed=6) * 0.3 + 1.0, rnd(C, seed=7) * 0.2
@@ -864,12 +871,23 @@ def test_transformer_front_end_in_one_launch(B, hw, dtype):
     qkvt = F.layer_norm(hs.float(), (C,), g1, be1, 1e-5) @ wqkv.t()        # (from the kernel's own 16-bit hs: isolates GEMM 2)
     check(qk, qkvt[:, :2 * C], 1.5e-2 * tol, 6e-3 * tol, "Q | K vs fp32")
     check(vt, qkvt[:, 2 * C:].reshape(B, hw, C).permute(0, 2, 1), 1.5e-2 * tol, 6e-3 * tol, "V^T vs fp32")
+    # ... and the derived gates of tests/norm_cases.py (rounding counts, nothing fitted) against fp64
+    r1, g1_ = NC.gate_tfront_hs(x.view(B, hw, C), gg, gb, w1, b1, dtype)
+    r2, g2_ = NC.gate_tfront_qkv(hs, wf, cs, tb, dtype)
+    ratios = (NC.worst_ratio(hs, r1, g1_), NC.worst_ratio(qk, r2[:, :2 * C], g2_[:, :2 * C]),
+              NC.worst_ratio(vt, r2[:, 2 * C:].reshape(B, hw, C).permute(0, 2, 1), g2_[:, 2 * C:].reshape(B, hw, C).permute(0, 2, 1)))
+    shares = [float((g > 1.5e-2 * tol + 6e-3 * tol * r.abs()).double().mean()) for r, g in ((r1, g1_), (r2, g2_))]
+    print(f"[tfront] B={B} hw={hw} {dtype}: error / derived gate hs {ratios[0]:.3f} Q|K {ratios[1]:.3f} V^T {ratios[2]:.3f}; the gates "
+          f"are looser than the tolerance on {100 * shares[0]:.2f} % (hs) and {100 * shares[1]:.2f} % (QKV) of the elements")
+    assert max(ratios) <= 1.0, ("pp_tfront vs the derived gates", ratios)
     # (c) q_scale (ABI v20): only the Q third changes -- multiplied in fp32 before its one rounding
     qs = 40 ** -0.5 * LOG2E
     hs2, qk2, vt2 = ops.tfront(x, acc, gg, gb, w1, b1, _kperm(wf).contiguous(), cs, tb, hw, q_scale=qs)
     assert torch.equal(hs2, hs) and torch.equal(vt2, vt) and torch.equal(qk2[:, C:], qk[:, C:])
     check(qk2[:, :C], qkvt[:, :C] * qs, 1.5e-2 * tol * qs, 6e-3 * tol, "pre-multiplied Q vs fp32")
     check(qk2[:, :C], qk[:, :C].float() * qs, 2 * ulp, 2 * ulp, "pre-multiplied Q vs the rounded plain Q")
+    r3, g3_ = NC.gate_tfront_qkv(hs, wf, cs, tb, dtype, q_scale=qs)
+    assert NC.worst_ratio(qk2[:, :C], r3[:, :C], g3_[:, :C]) <= 1.0, "pre-multiplied Q vs the derived gate"
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

@@ -7,11 +7,16 @@ the first self-attention on ONE half.  Everything here is an exactness statement
 rows as the full-batch ones (same kernels, the K walk of a row does not depend on the row count unless the split-K
 factor changes), the twice-stored tensor and the wrap-addressed reads are bit copies.
 """
+import os
+import sys
+
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import norm_cases as NC  # noqa: E402
 from powerpaint_amd import _lib as L  # noqa: E402
 from powerpaint_amd import ops  # noqa: E402
 from powerpaint_amd.engine import SDNet  # noqa: E402
@@ -104,9 +109,9 @@ def test_cross_attention_block_reads_the_half_batch_with_wrap(fold, dtype):
     st = None
     qcs = qb = None
     if fold:
-        xf = x.float()
+        xf = x.double()                                            # (fp64 sums rounded once: what the derived gate below assumes)
         st = torch.stack([torch.stack([xf[:, :160].sum(1), (xf[:, :160] ** 2).sum(1)], 1),
-                          torch.stack([xf[:, 160:].sum(1), (xf[:, 160:] ** 2).sum(1)], 1)], 1).contiguous()
+                          torch.stack([xf[:, 160:].sum(1), (xf[:, 160:] ** 2).sum(1)], 1)], 1).float().contiguous()
         qcs = wq.float().sum(1).contiguous()
         qb = rnd(C, seed=8, dtype=torch.float32)
     folded = ops.xattn_fold(k, vt, B, nctx, heads, wq, wo, q_colsum=qcs, q_bias=qb)
@@ -116,6 +121,11 @@ def test_cross_attention_block_reads_the_half_batch_with_wrap(fold, dtype):
     assert out.shape == (B * hw, C)
     assert torch.equal(out, ref) and torch.equal(rs, rs_ref)
     assert not torch.equal(out[:Bh * hw], out[Bh * hw:])           # (the halves do differ: different prompts)
+    # ... and both are the sub-block: the derived gate of tests/norm_cases.py against fp64, from the folded operands as stored
+    ref64, gate = NC.gate_xattn_block(torch.cat([x, x]), 2, folded, bo, torch.cat([res, res]), hw, 1e-5, dtype, fold=fold)
+    ratio = NC.worst_ratio(out, ref64, gate)
+    print(f"[twin xattn] fold={fold} {dtype}: error / derived gate {ratio:.3f}")
+    assert ratio <= 1.0, ratio
 
 
 NETS = {
@@ -243,3 +253,12 @@ def test_attn1_to_out_in_front_of_the_cross_attention_block(Bh, hw, nctx, twin, 
     src = (32 * s32 + 16 * (j // 4) + 4 * kg + (j % 4)).to(DEV)
     assert torch.equal(perm[0], plain[0][:, :, src]) and torch.equal(perm[2], plain[2]) and torch.equal(perm[3], plain[3])
     assert torch.allclose(perm[1], plain[1], rtol=1e-5, atol=1e-5)       # (column sums of the stored G^T: another fp32 order)
+    # the derived gate of tests/norm_cases.py against fp64.  h is parked in `out` and overwritten, but the same launch with
+    # H^T = 0 and no bias returns exactly it (round16(0 + h)); the sub-block is then gated FROM that h, with the row moments
+    # formed in the kernel (kernel_moments_eps); h itself: tests/test_tblock_exact_gpu.py
+    hk = ops.xattn_block(ao, (perm[0], perm[1], perm[2], torch.zeros_like(perm[3])), res=h0, rows_per_batch=hw, twin=twin, pre_w=w1,
+                         pre_b=b1, ln_fold=True)
+    ref64, gate = NC.gate_xattn_block(hk, 2, plain, bo, hk, hw, 1e-5, dtype, terms=NC.kernel_moments_eps())
+    ratio = NC.worst_ratio(out, ref64, gate)
+    print(f"[pre_w xattn] Bh={Bh} hw={hw} nctx={nctx} twin={twin} {dtype}: error / derived gate {ratio:.3f}")
+    assert ratio <= 1.0, ratio
