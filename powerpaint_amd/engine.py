@@ -12,9 +12,10 @@ Design (MI355X-first):
     coefficients, step counter), so a captured step replays with zero host->device traffic.
 """
 import ctypes as C
+import enum
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -693,6 +694,172 @@ class PackVec:
     keys: Tuple[str, ...]
 
 
+class XAttnForm(enum.Enum):
+    """How the cross-attention sub-block of a transformer (norm2 -> to_q -> attention over the prompt -> to_out + residual)
+    runs.  SDNet.xattn_form decides; the value is the `kperm` pp_xattn_fold lays the folded operands out with."""
+    CHAIN = None        # to_q -> attention -> to_out, three launches, nothing folded
+    BLOCK = 0           # one pp_xattn_block launch
+    BLOCK_PRE = 1       # ... with attn1.to_out (+ residual) in front, in the same launch
+    TWO_GEMM = 2        # two GEMMs with per-prompt weights (PP_ACT_SOFTMAX80 in the first one's epilogue)
+
+
+class XAttnFold(NamedTuple):
+    """Folded cross-attention operands of one transformer (written by pp_xattn_fold in the setup plan) and the step
+    geometry their form was resolved for."""
+    gt: int
+    gcs: int
+    gb: int
+    ht: int
+    kperm: int
+    rows: int           # of the full batch
+    hw: int             # positions per batch item
+
+    @property
+    def form(self) -> XAttnForm:
+        return XAttnForm(self.kperm)
+
+
+class _TransformerBlock:
+    """One transformer being compiled (SDNet._transformer): what its three stages share.  rows: of the input x (ONE half of
+    a CFG pair under `twin`); rows_o: of the full batch, which everything behind the first cross-attention runs on."""
+
+    def __init__(self, net: "SDNet", pb: "Builder", pre: str, x: Act, twin: bool):
+        self.net, self.pb, self.pre, self.x, self.twin = net, pb, pre, x, twin
+        self.tb = f"{pre}.transformer_blocks.0"
+        self.rows, self.hw = x.rows, x.H * x.W
+        self.rows_o = 2 * x.rows if twin else x.rows
+        self.tiles = (x.C + 159) // 160
+
+    def producer(self, rows: int) -> int:
+        """Row-moment buffer written by the GEMM that produces the next LayerNorm's input."""
+        return self.pb.alloc(rows * self.tiles * 8) if self.net.fold_ln else 0
+
+    def normed(self, h: int, st: int, nrm: str, lin: str, rows: int):
+        """-> (x pointer, kwargs) for the Linear `lin` applied to LayerNorm_nrm(h)."""
+        P, tb, Cc = self.net.P, self.tb, self.x.C
+        if self.net.fold_ln:
+            return h, dict(bias=P[f"{tb}.{lin}.bias"], ln_stats=st, ln_colsum=P[f"{tb}.{lin}.colsum"],
+                           ln_tiles=self.tiles, ln_dim=Cc, ln_eps=1e-5)
+        xn = self.pb.layernorm(h, rows, Cc, P[f"{tb}.{nrm}.weight"], P[f"{tb}.{nrm}.bias"])
+        return xn, (dict(bias=P[f"{tb}.{lin}.bias"]) if lin == "ff1" else {})
+
+    def self_attention(self) -> Tuple[int, int]:
+        """norm -> proj_in -> norm1 -> QKV -> attention.  -> (hs, a): the hidden state behind proj_in and attn1's output in
+        front of its to_out, which belongs to whichever launch the cross-attention form gives it to."""
+        net, pb, P, x, pre, tb = self.net, self.pb, self.net.P, self.x, self.pre, self.tb
+        Cc, rows, hw, d = x.C, self.rows, self.hw, x.C // net.heads
+        if net.fold_ln and net.fuse_tfront and f"{tb}.attn1.qkv.weight_kp" in P and \
+                pb.lib.pp_tfront_supported(rows, Cc, hw, net.groups):
+            acc = pb._subscribe_gn_stats(x, None, net.groups)
+            if acc:
+                hs = pb.alloc(rows * Cc * 2)
+                vt = pb.alloc(x.B * Cc * hw * 2)
+                qk = pb.alloc(rows * 2 * Cc * 2)
+                # (round 5) Q leaves the front end as Q * d^-0.5 * log2(e) where the pipelined attention kernel covers the
+                # shape: its scores then come out of the MFMA as exp2 arguments (PP_ATTN_PIPE_LOG2)
+                log2q = bool(net.attn_log2 and pb.lib.pp_attention_log2_ok(hw, hw, d))
+                pb.plan.add("tfront", pb.lib.pp_tfront, x.ptr, Cc, acc, P[f"{pre}.norm.weight"], P[f"{pre}.norm.bias"], 1e-6,
+                            net.groups, P[f"{pre}.proj_in.weight"], P[f"{pre}.proj_in.bias"],
+                            P[f"{tb}.attn1.qkv.weight_kp"], P[f"{tb}.attn1.qkv.colsum"], P[f"{tb}.attn1.qkv.bias"], 1e-5, hs, Cc,
+                            qk, 2 * Cc, vt, hw, rows, Cc, hw, (float(d) ** -0.5) * 1.4426950408889634 if log2q else 1.0, pb.dt)
+                pb.plan.count("tfront", 2.0 * rows * Cc * Cc + 2.0 * rows * 3 * Cc * Cc)     # (proj_in + QKV)
+                return hs, pb.attention(qk, 2 * Cc, qk + 2 * Cc, 2 * Cc, vt, hw, x.B, net.heads, hw, hw, d, log2q=log2q)
+        st = self.producer(rows)
+        n = pb.groupnorm(x, P[f"{pre}.norm.weight"], P[f"{pre}.norm.bias"], 1e-6, False, groups=net.groups)
+        hs = pb.linear(n.ptr, rows, Cc, P[f"{pre}.proj_in.weight"], Cc, P[f"{pre}.proj_in.bias"], row_stats_out=st,
+                       name="conv1x1")
+        ln, kw = self.normed(hs, st, "norm1", "attn1.qkv", rows)
+        if hw % 8 == 0:       # fused QKV GEMM, V written transposed by the epilogue
+            vt = pb.alloc(x.B * Cc * hw * 2)
+            qk = pb.linear(ln, rows, Cc, P[f"{tb}.attn1.qkv.weight"], 3 * Cc, out_vt=vt, vt_col0=2 * Cc, vt_ld=hw,
+                           rows_per_batch=hw, name="linear", **kw)
+            return hs, pb.attention(qk, 2 * Cc, qk + 2 * Cc, 2 * Cc, vt, hw, x.B, net.heads, hw, hw, d)
+        # tiny latents (hw < 8, e.g. 2x2): V^T rows must be 16-byte aligned and zero padded -> unfused transpose
+        ldvt = _align(hw, 8)
+        vt = pb.alloc(x.B * Cc * ldvt * 2)
+        qkv = pb.linear(ln, rows, Cc, P[f"{tb}.attn1.qkv.weight"], 3 * Cc, name="linear", **kw)
+        pb.plan.add("transpose_v", pb.lib.pp_transpose_v, qkv + 4 * Cc, 3 * Cc, x.B, hw, Cc, vt, ldvt)
+        return hs, pb.attention(qkv, 3 * Cc, qkv + 2 * Cc, 3 * Cc, vt, ldvt, x.B, net.heads, hw, hw, d)
+
+    def cross_attention(self, hs: int, a: int, xa: Optional[XAttnFold], kv: Tuple[int, int, int, int]) -> Tuple[int, int]:
+        """attn1.to_out + residual, then the cross-attention sub-block in the form build_setup resolved (xa: its folded
+        operands, None for the chain; kv: the hoisted K / V^T the chain reads).  -> (hs, st) on rows_o rows."""
+        net, pb, P, x, tb = self.net, self.pb, self.net.P, self.x, self.tb
+        Cc, rows, rows_o, hw, tiles, fold = x.C, self.rows, self.rows_o, self.hw, self.tiles, self.net.fold_ln
+        form = xa.form if xa is not None else XAttnForm.CHAIN
+        if xa is not None and (xa.rows, xa.hw) != (rows_o, hw):
+            raise L.PPError(f"{self.pre}: the cross-attention operands were folded for {xa.rows} rows of {xa.hw} positions "
+                            f"per batch item, the step reaches it with {rows_o} of {hw} (build_setup's hw0)")
+        if self.twin and form not in (XAttnForm.BLOCK, XAttnForm.BLOCK_PRE):
+            raise L.PPError("twin prefix without the fused cross-attention block (build_step checks twin_prefix_ok first)")
+        wrap = rows if self.twin else 0
+        if form is XAttnForm.BLOCK_PRE:
+            # attn1.to_out + residual in front of the cross-attention sub-block, same launch (G^T was folded with kperm = 1)
+            st = self.producer(rows_o)
+            o = pb.alloc(rows_o * Cc * 2)
+            pb.plan.add("xattn_block", pb.lib.pp_xattn_block, a, Cc, hs, Cc, None, tiles, 1e-5, xa.gt, xa.gcs, xa.gb, xa.ht,
+                        P[f"{tb}.attn2.to_out.bias"], o, Cc, st or None, rows_o, Cc, hw, wrap,
+                        P[f"{tb}.attn1.to_out.weight"], P[f"{tb}.attn1.to_out.bias"], pb.dt)
+            pb.plan.count("xattn_block", 6.0 * rows_o * Cc * Cc + 4.0 * rows_o * net._nctx * Cc)   # (+ attn1.to_out)
+            return o, st
+        st = self.producer(rows)
+        hs = pb.linear(a, rows, Cc, P[f"{tb}.attn1.to_out.weight"], Cc, P[f"{tb}.attn1.to_out.bias"], res1=hs,
+                       row_stats_out=st, name="linear")
+        ln, kw = self.normed(hs, st, "norm2", "attn2.to_q", rows)
+        if form is XAttnForm.TWO_GEMM:
+            # the folded sub-block as two GEMMs with one (G^T, H^T) per batch item (setup plan: pp_xattn_fold(kperm = 2))
+            S = net.heads * 80
+            stats = dict(ln_stats=kw["ln_stats"], ln_colsum=xa.gcs, ln_tiles=tiles, ln_dim=Cc, ln_eps=1e-5) if fold else {}
+            prob = pb.linear(ln, rows, Cc, xa.gt, S, bias=xa.gb, act=L.PP_ACT_SOFTMAX80, rows_per_batch=hw,
+                             w_batch_stride=S * Cc, vec_batch_stride=S, name="linear", **stats)
+            st = self.producer(rows)
+            hs = pb.linear(prob, rows, S, xa.ht, Cc, P[f"{tb}.attn2.to_out.bias"], res1=hs, row_stats_out=st,
+                           rows_per_batch=hw, w_batch_stride=Cc * S, name="linear")
+        elif form is XAttnForm.BLOCK:
+            st = self.producer(rows_o)
+            o = pb.alloc(rows_o * Cc * 2)
+            pb.plan.add("xattn_block", pb.lib.pp_xattn_block, ln, Cc, hs, Cc, kw.get("ln_stats"), tiles if fold else 0,
+                        1e-5, xa.gt, xa.gcs, xa.gb, xa.ht, P[f"{tb}.attn2.to_out.bias"], o, Cc, st or None, rows_o, Cc, hw,
+                        wrap, None, None, pb.dt)
+            # (the FLOPs of the chain it stands for: the folded form multiplies twice as much)
+            pb.plan.count("xattn_block", 4.0 * rows_o * Cc * Cc + 4.0 * rows_o * net._nctx * Cc)
+            hs = o
+        else:
+            # K / V^T hoisted out of the step: encoder_hidden_states are step-invariant
+            q = pb.linear(ln, rows, Cc, P[f"{tb}.attn2.to_q.weight"], Cc, name="linear", **kw)
+            a = pb.attention(q, Cc, kv[0], kv[1], kv[2], kv[3], x.B, net.heads, hw, net._nctx, Cc // net.heads)
+            # IP-Adapter: a += scale_i * softmax(q K_i^T / sqrt(d)) V_i per adapter, in place, in front of to_out
+            for (k_ip, v_ip, nk_ip), cell in zip(net.ip_kv.get(self.pre, ()), net.ip_scale_cells):
+                pb.ip_attn_add(q, Cc, k_ip, v_ip, a, Cc, x.B, net.heads, hw, nk_ip, Cc // net.heads, cell)
+            st = self.producer(rows)
+            hs = pb.linear(a, rows, Cc, P[f"{tb}.attn2.to_out.weight"], Cc, P[f"{tb}.attn2.to_out.bias"], res1=hs,
+                           row_stats_out=st, name="linear")
+        return hs, st
+
+    def feed_forward(self, hs: int, st: int, out: int, res2: int):
+        """norm3 -> GEGLU -> FF2 -> proj_out + the transformer's residual (+ res2), into `out`.  -> the launch that wrote it."""
+        net, pb, P, x, pre, tb = self.net, self.pb, self.net.P, self.x, self.pre, self.tb
+        Cc, rows = x.C, self.rows_o
+        wrap = self.rows if self.twin else 0          # the transformer's input (the proj_out residual) holds one half only
+        w2n = f"{pre}.ff2_proj_out.weight" + ("" if net.ff_w8 else "_kp")
+        if net.fold_ln and net.fuse_ff and net.merge_ff2_proj_out and w2n in P and \
+                pb.lib.pp_ff_fused_supported(rows, Cc, self.hw):
+            return pb.ff_fused(hs, rows, Cc, self.hw, P[f"{tb}.ff1.weight"], P[f"{tb}.ff1.bias"], P[f"{tb}.ff1.colsum"],
+                               st, self.tiles, P[w2n], P[f"{pre}.ff2_proj_out.bias"], out,
+                               res1=x.ptr, res1_wrap=wrap, res2=res2, w2_kperm=not net.ff_w8)
+        # GEGLU fused into the first GEMM's epilogue
+        ln, kw = self.normed(hs, st, "norm3", "ff1", rows)
+        g = pb.linear(ln, rows, Cc, P[f"{tb}.ff1.weight"], 8 * Cc, act=L.PP_ACT_GEGLU, name="linear_geglu", **kw)
+        if net.merge_ff2_proj_out:
+            pb.linear(g, rows, 4 * Cc, P[f"{pre}.ff2_proj_out.weight"], Cc, P[f"{pre}.ff2_proj_out.bias"], x2=hs, K2=Cc,
+                      ldx2=Cc, res1=x.ptr, res1_wrap=wrap, res2=res2, out=out, name="linear")
+        else:
+            hs = pb.linear(g, rows, 4 * Cc, P[f"{tb}.ff2.weight"], Cc, P[f"{tb}.ff2.bias"], res1=hs, name="linear")
+            pb.linear(hs, rows, Cc, P[f"{pre}.proj_out.weight"], Cc, P[f"{pre}.proj_out.bias"], res1=x.ptr, res1_wrap=wrap,
+                      res2=res2, out=out, name="conv1x1")
+        return pb.last_gemm
+
+
 class SDNet:
     """One network of the SD-1.5 family ("unet" | "brushnet" | "controlnet") compiled to HIP launch plans.
 
@@ -775,6 +942,14 @@ class SDNet:
         self.temb_total = 0
         # IP-Adapters (set_ip_adapters): per adapter (tokens per image, image-embed dimension); empty = a network without any
         self.ip: List[Tuple[int, int]] = []
+        # what build_setup leaves for build_step (per plan: every build_setup starts them afresh)
+        self._nctx = 0                                          # context tokens
+        self.kv: Dict[str, Tuple[int, int, int, int]] = {}      # transformer -> hoisted cross-attention (K, ldk, V^T, ldvt)
+        self.xa: Dict[str, XAttnFold] = {}                      # ... -> folded cross-attention operands (none: the chain)
+        self.ip_kv: Dict[str, List[Tuple[int, int, int]]] = {}  # ... -> per IP-Adapter (K_i, V_i, tokens)
+        self.ip_scale_cells: list = []                          # per IP-Adapter: its ctypes.c_float scale cell
+        self.upfold: Dict[str, int] = {}                        # upsampler conv -> its sub-pixel folded weights
+        self.cond_emb: Optional[Act] = None                     # (controlnet) the conditioning embedding
         for c in self.boc:
             if c % 64 or (c // heads) not in (40, 80, 160):
                 raise L.PPError(f"unsupported channel width {c} (need multiple of 64 and head_dim in 40/80/160)")
@@ -1304,170 +1479,63 @@ class SDNet:
         pb.release(m)
         return out
 
+    def xattn_form(self, lib, c: int, hw: int, B: int, nctx: int) -> XAttnForm:
+        """The form of the cross-attention sub-block of a transformer of width c whose level has hw positions per batch item,
+        at full batch B: the ONE place that reads the fuse_xattn* switches and probes pp_xattn_block_supported (DESIGN.md
+        "Cross-attention forms").  build_setup folds by it, the step plan runs what was folded, twin_prefix_ok asks it."""
+        if not (self.fuse_xattn and not self.ip and lib.pp_xattn_block_supported(128, c, 128, nctx, self.heads)):
+            return XAttnForm.CHAIN
+        wide = self.fuse_xattn_wide and c <= self.xattn_wide_max_c
+        if self.fuse_xattn_2g and c > 320 and hw > 0 and hw % 64 == 0 and not wide:
+            return XAttnForm.TWO_GEMM          # whole 64-row GEMM tiles per batch item
+        if not (hw > 0 and lib.pp_xattn_block_supported(B * hw, c, hw, nctx, self.heads)):
+            return XAttnForm.CHAIN
+        if c == 320 and self.fold_ln and self.fuse_xattn_pre:
+            return XAttnForm.BLOCK_PRE
+        return XAttnForm.BLOCK if (c == 320 or wide) else XAttnForm.CHAIN
+
+    def xattn_forms(self, lib, B: int, H: int, W: int, nctx: int) -> Dict[str, Tuple[XAttnForm, int]]:
+        """transformer -> (form, positions per batch item) for a step over H x W latents at batch B."""
+        nl = len(self.boc)
+        sizes = level_sizes(H, W, nl)
+        out = {}
+        for pre, c in self._attn_specs():
+            part = pre.split(".")
+            lvl = int(part[1]) if part[0] == "down_blocks" else (nl - 1 if part[0] == "mid_block" else nl - 1 - int(part[1]))
+            hw = sizes[lvl][0] * sizes[lvl][1]
+            out[pre] = (self.xattn_form(lib, c, hw, B, nctx), hw)
+        return out
+
     def _transformer(self, pb: Builder, pre: str, x: Act, kv: Tuple[int, int, int, int], res2: int = 0,
                      twin: bool = False) -> Act:
         """kv = (k_ptr, ldk, vt_ptr, ldvt) of the hoisted cross-attention K / V^T; nk = ctx tokens in self._nctx.
         twin: x is ONE half of a CFG pair whose halves are identical up to here (build_step): norm / proj_in / attn1 run on
         that half, the fused cross-attention block -- the first consumer that mixes the prompt in -- reads it with batch-wrap
         addressing, and everything behind it (and the returned Act) is the full batch."""
-        P = self.P
-        Cc, rows, hw = x.C, x.rows, x.H * x.W
-        d = Cc // self.heads
-        tb = f"{pre}.transformer_blocks.0"
-        Bo = 2 * x.B if twin else x.B          # batch / rows behind the first cross-attention
-        rows_o = Bo * hw
-        out = pb.new_act(Bo, x.H, x.W, Cc)
+        t = _TransformerBlock(self, pb, pre, x, twin)
+        out = pb.new_act(2 * x.B if twin else x.B, x.H, x.W, x.C)
         m = pb.mark()
-        fold = self.fold_ln
-        tiles = (Cc + 159) // 160
-
-        def producer(r=None):     # row-moment buffer written by the GEMM that produces the next LayerNorm's input
-            return pb.alloc((r or rows) * tiles * 8) if fold else 0
-
-        def normed(h, st, nrm, lin):
-            """-> (x pointer, kwargs) for the Linear `lin` applied to LayerNorm_nrm(h)."""
-            if fold:
-                return h, dict(bias=P[f"{tb}.{lin}.bias"], ln_stats=st, ln_colsum=P[f"{tb}.{lin}.colsum"],
-                               ln_tiles=tiles, ln_dim=Cc, ln_eps=1e-5)
-            xn = pb.layernorm(h, rows, Cc, P[f"{tb}.{nrm}.weight"], P[f"{tb}.{nrm}.bias"])
-            return xn, (dict(bias=P[f"{tb}.{lin}.bias"]) if lin == "ff1" else {})
-
-        front = None
-        if fold and self.fuse_tfront and f"{tb}.attn1.qkv.weight_kp" in P and \
-                pb.lib.pp_tfront_supported(rows, Cc, hw, self.groups):
-            acc = pb._subscribe_gn_stats(x, None, self.groups)
-            if acc:
-                hs = pb.alloc(rows * Cc * 2)
-                vt = pb.alloc(x.B * Cc * hw * 2)
-                qk = pb.alloc(rows * 2 * Cc * 2)
-                # (round 5) Q leaves the front end as Q * d^-0.5 * log2(e) where the pipelined attention kernel covers the
-                # shape: its scores then come out of the MFMA as exp2 arguments (PP_ATTN_PIPE_LOG2)
-                log2q = bool(self.attn_log2 and pb.lib.pp_attention_log2_ok(hw, hw, d))
-                pb.plan.add("tfront", pb.lib.pp_tfront, x.ptr, Cc, acc, P[f"{pre}.norm.weight"], P[f"{pre}.norm.bias"], 1e-6,
-                            self.groups, P[f"{pre}.proj_in.weight"], P[f"{pre}.proj_in.bias"],
-                            P[f"{tb}.attn1.qkv.weight_kp"], P[f"{tb}.attn1.qkv.colsum"], P[f"{tb}.attn1.qkv.bias"], 1e-5, hs, Cc,
-                            qk, 2 * Cc, vt, hw, rows, Cc, hw, (float(d) ** -0.5) * 1.4426950408889634 if log2q else 1.0, pb.dt)
-                pb.plan.count("tfront", 2.0 * rows * Cc * Cc + 2.0 * rows * 3 * Cc * Cc)     # (proj_in + QKV)
-                front = pb.attention(qk, 2 * Cc, qk + 2 * Cc, 2 * Cc, vt, hw, x.B, self.heads, hw, hw, d, log2q=log2q)
-        if front is not None:
-            a = front
-        else:
-            st = producer()
-            n = pb.groupnorm(x, P[f"{pre}.norm.weight"], P[f"{pre}.norm.bias"], 1e-6, False, groups=self.groups)
-            hs = pb.linear(n.ptr, rows, Cc, P[f"{pre}.proj_in.weight"], Cc, P[f"{pre}.proj_in.bias"], row_stats_out=st,
-                           name="conv1x1")
-            # self-attention: fused QKV GEMM, V written transposed by the epilogue
-            ln, kw = normed(hs, st, "norm1", "attn1.qkv")
-        if front is not None:
-            pass
-        elif hw % 8 == 0:
-            vt = pb.alloc(x.B * Cc * hw * 2)
-            qk = pb.linear(ln, rows, Cc, P[f"{tb}.attn1.qkv.weight"], 3 * Cc, out_vt=vt, vt_col0=2 * Cc, vt_ld=hw,
-                           rows_per_batch=hw, name="linear", **kw)
-            a = pb.attention(qk, 2 * Cc, qk + 2 * Cc, 2 * Cc, vt, hw, x.B, self.heads, hw, hw, d)
-        else:
-            # tiny latents (hw < 8, e.g. 2x2): V^T rows must be 16-byte aligned and zero padded -> unfused transpose
-            ldvt = _align(hw, 8)
-            vt = pb.alloc(x.B * Cc * ldvt * 2)
-            qkv = pb.linear(ln, rows, Cc, P[f"{tb}.attn1.qkv.weight"], 3 * Cc, name="linear", **kw)
-            pb.plan.add("transpose_v", pb.lib.pp_transpose_v, qkv + 4 * Cc, 3 * Cc, x.B, hw, Cc, vt, ldvt)
-            a = pb.attention(qkv, 3 * Cc, qkv + 2 * Cc, 3 * Cc, vt, ldvt, x.B, self.heads, hw, hw, d)
-        xa = getattr(self, "xa", {}).get(pre)
-        if xa is not None and len(xa) > 4 and xa[4] == 1 and fold and \
-                pb.lib.pp_xattn_block_supported(rows_o, Cc, hw, self._nctx, self.heads):
-            # attn1.to_out + residual in front of the cross-attention sub-block, same launch (G^T was folded with kperm = 1)
-            st2 = producer(rows_o)
-            o = pb.alloc(rows_o * Cc * 2)
-            pb.plan.add("xattn_block", pb.lib.pp_xattn_block, a, Cc, hs, Cc, None, tiles, 1e-5, xa[0], xa[1], xa[2], xa[3],
-                        P[f"{tb}.attn2.to_out.bias"], o, Cc, st2 or None, rows_o, Cc, hw, rows if twin else 0,
-                        P[f"{tb}.attn1.to_out.weight"], P[f"{tb}.attn1.to_out.bias"], pb.dt)
-            pb.plan.count("xattn_block", 6.0 * rows_o * Cc * Cc + 4.0 * rows_o * self._nctx * Cc)   # (+ attn1.to_out)
-            hs, st = o, st2
-            xa = "done"
-        else:
-            st = producer()
-            hs = pb.linear(a, rows, Cc, P[f"{tb}.attn1.to_out.weight"], Cc, P[f"{tb}.attn1.to_out.bias"], res1=hs,
-                           row_stats_out=st, name="linear")
-        # cross-attention (K / V^T hoisted out of the step: encoder_hidden_states are step-invariant)
-        if xa == "done":
-            pass
-        elif xa is not None and len(xa) > 4 and xa[4] == 2 and hw % 64 == 0 and not twin:
-            # the folded sub-block as two GEMMs with one (G^T, H^T) per batch item (setup plan: pp_xattn_fold(kperm = 2))
-            S = self.heads * 80
-            ln, kw = normed(hs, st, "norm2", "attn2.to_q")
-            stats = dict(ln_stats=kw["ln_stats"], ln_colsum=xa[1], ln_tiles=tiles, ln_dim=Cc, ln_eps=1e-5) if fold else {}
-            prob = pb.linear(ln, rows, Cc, xa[0], S, bias=xa[2], act=L.PP_ACT_SOFTMAX80, rows_per_batch=hw,
-                             w_batch_stride=S * Cc, vec_batch_stride=S, name="linear", **stats)
-            st = producer()
-            hs = pb.linear(prob, rows, S, xa[3], Cc, P[f"{tb}.attn2.to_out.bias"], res1=hs, row_stats_out=st,
-                           rows_per_batch=hw, w_batch_stride=Cc * S, name="linear")
-        elif xa is not None and len(xa) > 4 and xa[4] == 2:
-            raise L.PPError("H^T was folded for the two-GEMM cross-attention, which this shape does not take (build_setup "
-                            "folds it only for step geometries with whole 64-row tiles per batch item)")
-        elif xa is not None and len(xa) > 4 and xa[4] == 1:
-            raise L.PPError("G^T was folded for the chained cross-attention block, which this shape does not take")
-        elif xa is not None and pb.lib.pp_xattn_block_supported(rows_o, Cc, hw, self._nctx, self.heads):
-            ln, kw = normed(hs, st, "norm2", "attn2.to_q")
-            st2 = producer(rows_o)
-            o = pb.alloc(rows_o * Cc * 2)
-            pb.plan.add("xattn_block", pb.lib.pp_xattn_block, ln, Cc, hs, Cc, kw.get("ln_stats"), tiles if fold else 0,
-                        1e-5, xa[0], xa[1], xa[2], xa[3], P[f"{tb}.attn2.to_out.bias"], o, Cc, st2 or None, rows_o, Cc, hw,
-                        rows if twin else 0, None, None, pb.dt)
-            # (the FLOPs of the chain it stands for: the folded form multiplies twice as much)
-            pb.plan.count("xattn_block", 4.0 * rows_o * Cc * Cc + 4.0 * rows_o * self._nctx * Cc)
-            hs, st = o, st2
-        elif twin:
-            raise L.PPError("twin prefix without the fused cross-attention block (build_step checks _twin_ok first)")
-        else:
-            ln, kw = normed(hs, st, "norm2", "attn2.to_q")
-            q = pb.linear(ln, rows, Cc, P[f"{tb}.attn2.to_q.weight"], Cc, name="linear", **kw)
-            a = pb.attention(q, Cc, kv[0], kv[1], kv[2], kv[3], x.B, self.heads, hw, self._nctx, d)
-            # IP-Adapter: a += scale_i * softmax(q K_i^T / sqrt(d)) V_i per adapter, in place, in front of to_out
-            for (k_ip, v_ip, nk_ip), cell in zip(getattr(self, "ip_kv", {}).get(pre, ()), getattr(self, "ip_scale_cells", ())):
-                pb.ip_attn_add(q, Cc, k_ip, v_ip, a, Cc, x.B, self.heads, hw, nk_ip, d, cell)
-            st = producer()
-            hs = pb.linear(a, rows, Cc, P[f"{tb}.attn2.to_out.weight"], Cc, P[f"{tb}.attn2.to_out.bias"], res1=hs,
-                           row_stats_out=st, name="linear")
-        # feed-forward: GEGLU fused into the first GEMM's epilogue
-        rows_h, rows = rows, rows_o           # (from here on: the full batch)
-        wrap = rows_h if twin else 0          # the transformer's input (the proj_out residual) holds one half only
-        w2n = f"{pre}.ff2_proj_out.weight" + ("" if self.ff_w8 else "_kp")
-        if fold and self.fuse_ff and self.merge_ff2_proj_out and w2n in P and pb.lib.pp_ff_fused_supported(rows, Cc, hw):
-            out.producer = pb.ff_fused(hs, rows, Cc, hw, P[f"{tb}.ff1.weight"], P[f"{tb}.ff1.bias"], P[f"{tb}.ff1.colsum"],
-                                       st, tiles, P[w2n], P[f"{pre}.ff2_proj_out.bias"], out.ptr,
-                                       res1=x.ptr, res1_wrap=wrap, res2=res2, w2_kperm=not self.ff_w8)
-            pb.release(m)
-            return out
-        ln, kw = normed(hs, st, "norm3", "ff1")
-        g = pb.linear(ln, rows, Cc, P[f"{tb}.ff1.weight"], 8 * Cc, act=L.PP_ACT_GEGLU, name="linear_geglu", **kw)
-        if self.merge_ff2_proj_out:
-            pb.linear(g, rows, 4 * Cc, P[f"{pre}.ff2_proj_out.weight"], Cc, P[f"{pre}.ff2_proj_out.bias"], x2=hs, K2=Cc,
-                      ldx2=Cc, res1=x.ptr, res1_wrap=wrap, res2=res2, out=out.ptr, name="linear")
-            out.producer = pb.last_gemm
-        else:
-            hs = pb.linear(g, rows, 4 * Cc, P[f"{tb}.ff2.weight"], Cc, P[f"{tb}.ff2.bias"], res1=hs, name="linear")
-            pb.linear(hs, rows, Cc, P[f"{pre}.proj_out.weight"], Cc, P[f"{pre}.proj_out.bias"], res1=x.ptr, res1_wrap=wrap,
-                      res2=res2, out=out.ptr, name="conv1x1")
-            out.producer = pb.last_gemm
+        hs, a = t.self_attention()
+        hs, st = t.cross_attention(hs, a, self.xa.get(pre), kv)
+        out.producer = t.feed_forward(hs, st, out.ptr, res2)
         pb.release(m)
         return out
 
     # ---------------------------------------------------------------- setup plan: step-invariant work
-    def build_setup(self, pb: Builder, B: int, nctx: int, ehs: int, cond: Optional[Act] = None,
-                    hw0: Optional[Tuple[int, int]] = None, ip_in: Sequence[Tuple[int, int]] = (), ip_scales=()):
+    def build_setup(self, pb: Builder, B: int, nctx: int, ehs: int, cond: Optional[Act] = None, *,
+                    hw0: Tuple[int, int], ip_in: Sequence[Tuple[int, int]] = (), ip_scales=()):
         """Cross-attention K and V^T for every transformer from encoder_hidden_states (bf16 [B*nctx][ctx_dim] at
         `ehs`); for ControlNet also the conditioning embedding of `cond` (NHWC bf16 image).  hw0 = (H, W) of the latents the
-        step plan will be built for (the folded cross-attention operands of a transformer depend on which kernel runs it).
+        step plan will be built for (xattn_forms: which cross-attention operands are folded, and in which layout).
         ip_in (a UNet with IP-Adapters, one entry per adapter): (pointer, n) of the call's image embeds, 16-bit [B][n][D rounded
         up to 64] with zero pad columns; ip_scales: the adapters' ctypes.c_float scale cells.  The image tokens
         e_i = LayerNorm(reshape(proj(embeds))) [B][n T][ctx] and, per transformer, K_i = to_k_ip(e_i) and V_i = to_v_ip(e_i),
         row-major [B][n T][C] each, are step-invariant: computed here, read by the step plan's pp_ip_attn_add launches.  While
-        adapters are loaded no cross-attention is folded (self.xa stays empty): every attn2 runs to_q -> attention -> to_out."""
+        adapters are loaded every cross-attention is XAttnForm.CHAIN (self.xa stays empty): to_q -> attention -> to_out."""
         self._nctx = nctx
         if len(ip_in) != len(self.ip) or len(ip_scales) != len(self.ip):
             raise L.PPError(f"{len(self.ip)} IP-Adapters are loaded, the setup plan was given {len(ip_in)} image-embed buffers")
-        self.ip_kv: Dict[str, List[Tuple[int, int, int]]] = {}
-        self.ip_scale_cells = list(ip_scales)
+        self.ip_kv, self.ip_scale_cells = {}, list(ip_scales)
         ip_tok = []
         for i, ((T, D), (src, n)) in enumerate(zip(self.ip, ip_in)):
             if n < 1 or n * T > L.PP_IP_MAX_TOKENS:
@@ -1478,19 +1546,8 @@ class SDNet:
             e = pb.layernorm(y, B * n * T, self.ctx_dim, self.P[f"{Pn}.norm.weight"], self.P[f"{Pn}.norm.bias"])
             ip_tok.append((e, n * T))
         ldvt = _align(nctx, 8)
-        pre_hw: Dict[str, bool] = {}        # transformer -> the fused block kernel takes its step geometry
-        pre_hw64: Dict[str, bool] = {}      # transformer -> whole 64-row GEMM tiles per batch item (the two-GEMM form)
-        nl = len(self.boc)
-        sizes = level_sizes(hw0[0], hw0[1], nl) if hw0 is not None else None
-        if hw0 is not None:
-            for pre, c in self._attn_specs():
-                part = pre.split(".")
-                lvl = int(part[1]) if part[0] == "down_blocks" else (nl - 1 if part[0] == "mid_block" else nl - 1 - int(part[1]))
-                hw = sizes[lvl][0] * sizes[lvl][1]
-                pre_hw[pre] = hw > 0 and bool(pb.lib.pp_xattn_block_supported(B * hw, c, hw, nctx, self.heads))
-                pre_hw64[pre] = hw > 0 and hw % 64 == 0
-        self.kv: Dict[str, Tuple[int, int, int, int]] = {}
-        self.xa: Dict[str, Tuple[int, int, int, int]] = {}       # folded cross-attention operands (pp_xattn_fold)
+        forms = self.xattn_forms(pb.lib, B, hw0[0], hw0[1], nctx)
+        self.kv, self.xa = {}, {}
         for pre, c in self._attn_specs():
             tb = f"{pre}.transformer_blocks.0"
             vt = pb.alloc(B * c * ldvt * 2)
@@ -1502,33 +1559,27 @@ class SDNet:
                 k_ip = pb.linear(e, B * nk_ip, self.ctx_dim, w, c, name="linear")
                 v_ip = pb.linear(e, B * nk_ip, self.ctx_dim, w + c * self.ctx_dim * 2, c, name="linear")
                 self.ip_kv.setdefault(pre, []).append((k_ip, v_ip, nk_ip))
-            if self.ip:
-                continue
-            tbq = f"{tb}.attn2.to_q"
-            two_gemm = bool(self.fuse_xattn and self.fuse_xattn_2g and c > 320 and pre_hw64.get(pre) and
-                            not (self.fuse_xattn_wide and c <= self.xattn_wide_max_c))
             # (no folded operands for a step geometry none of the folded forms takes -- they were dead weight
             #  in the arena and in the setup plan)
-            block_ok = bool(pre_hw.get(pre)) if hw0 is not None else True
-            if self.fuse_xattn and (two_gemm or (block_ok and (c == 320 or (self.fuse_xattn_wide and c <= self.xattn_wide_max_c)))) and \
-                    pb.lib.pp_xattn_block_supported(128, c, 128, nctx, self.heads):
+            form, hw = forms[pre]
+            if form is not XAttnForm.CHAIN:
+                tbq = f"{tb}.attn2.to_q"
                 S = self.heads * 80
                 gt, ht = pb.alloc(B * S * c * 2), pb.alloc(B * c * S * 2)
                 gcs, gb = pb.alloc(B * S * 4), pb.alloc(B * S * 4)
                 fold = self.fold_ln
-                # C = 320: attn1.to_out runs in front of the sub-block in the same launch, whose logits then take their B
-                # operand from that GEMM's accumulators -> G^T with its channel index permuted (pre_hw: the step geometry
-                # must be one the block kernel takes, else the step plan keeps the chain and the plain layout)
-                kperm = 2 if two_gemm else int(bool(c == 320 and fold and self.fuse_xattn_pre and pre_hw.get(pre)))
+                # BLOCK_PRE: attn1.to_out runs in front of the sub-block in the same launch, whose logits then take their B
+                # operand from that GEMM's accumulators -> G^T with its channel index permuted (kperm = 1)
                 pb.plan.add("xattn_fold", pb.lib.pp_xattn_fold, k, c, vt, ldvt, B, nctx, self.heads, c,
                             self.P[f"{tbq}.weight"], self.P[f"{tbq}.colsum"] if fold else None,
                             self.P[f"{tbq}.bias"] if fold else None, self.P[f"{tb}.attn2.to_out.weight"],
-                            float(c // self.heads) ** -0.5, gt, gcs, gb, ht, int(kperm), pb.dt)
-                self.xa[pre] = (gt, gcs, gb, ht, kperm)
+                            float(c // self.heads) ** -0.5, gt, gcs, gb, ht, form.value, pb.dt)
+                self.xa[pre] = XAttnFold(gt, gcs, gb, ht, form.value, B * hw, hw)
         # Upsample2D convs in their sub-pixel form (PPGemmArgs.subpix): the folded weights are a cache derived from the packed
         # conv weight, rebuilt with everything else here whenever ParamPack.version has moved (NetRuntime.set_context)
-        self.upfold: Dict[str, int] = {}
-        if UPCONV_SUBPIX and hw0 is not None and self.kind in ("unet", "brushnet") and not (pb.gemm_tile or pb.gemm_splitk):
+        self.upfold = {}
+        sizes = level_sizes(hw0[0], hw0[1], len(self.boc))
+        if UPCONV_SUBPIX and self.kind in ("unet", "brushnet") and not (pb.gemm_tile or pb.gemm_splitk):
             rev = list(reversed(self.boc))
             for i in range(len(rev) - 1):
                 lvl = len(rev) - 1 - i
@@ -1563,10 +1614,9 @@ class SDNet:
         """Can build_step(twin=True) run the CFG-identical prefix of this network on one half of the batch?  Needs the
         fused cross-attention block at the first level (it is the launch that reads the half batch with wrap addressing)
         and an input that nothing prompt-dependent touches before it: no BrushNet adds inside the down path."""
-        pre = "down_blocks.0.attentions.0"
         return (TWIN_PREFIX and not brush and B >= 2 and B % 2 == 0 and self.L >= 1 and self.boc[0] == 320 and
-                self.down_types[0] == "CrossAttnDownBlock2D" and pre in getattr(self, "xa", {}) and (H * W) % 128 == 0 and
-                bool(lib.pp_xattn_block_supported(B * H * W, 320, H * W, nctx, self.heads)))
+                self.down_types[0] == "CrossAttnDownBlock2D" and (H * W) % 128 == 0 and        # (down_blocks.0.attentions.0:)
+                self.xattn_form(lib, 320, H * W, B, nctx) in (XAttnForm.BLOCK, XAttnForm.BLOCK_PRE))
 
     def build_step(self, pb: Builder, x_in: Act, t_dev: int, add_down: Optional[List[int]] = None,
                    add_mid: int = 0, add_up: Optional[List[int]] = None, ctrl_down: Optional[List[int]] = None,
@@ -1719,7 +1769,7 @@ class SDNet:
                 # the upsampler resizes to the size of the skip tensor the next block pops: 2 h or, behind an odd level of the
                 # down path, 2 h - 1 per axis (`upsample_size`, unet_2d_condition.py:1311-1312; BrushNet_CA.py:874)
                 tgt = (skips[-1].H, skips[-1].W)
-                if pre in getattr(self, "upfold", {}) and tgt == (2 * s.H, 2 * s.W):
+                if pre in self.upfold and tgt == (2 * s.H, 2 * s.W):
                     s = pb.conv3x3_up_subpix(s, self.upfold[pre], rev[i], P[pre + ".bias"], res2=pop(add_up))
                 else:
                     s = pb.conv3x3(s, P[pre + ".weight"], rev[i], P[pre + ".bias"], up=True, up_size=tgt,

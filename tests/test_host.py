@@ -646,3 +646,74 @@ def test_twin_prefix_plans_at_the_headline_shapes():
     shapes = rt._residual_shapes(8, 64, 64, True)
     rt.ensure(8, 64, 64, 77, 4, ("brushnet", {k: [0] * len(v) for k, v in shapes.items()}), twin=True)
     assert not [a for a in rt.step_plan.keep if a.out_dup_rows or a.res1_wrap_rows]
+
+
+def _forms_against_plans(net, B, H, W, twin=False, **ensure_kw):
+    """Build the plans of `net` and hold them against SDNet.xattn_forms, the resolver's answer per transformer:
+    -> ((BLOCK_PRE, BLOCK, TWO_GEMM) counts, the runtime)."""
+    from powerpaint_amd import _lib as L
+    from powerpaint_amd.engine import XAttnForm as F
+    rt = NetRuntime(net, "cpu")
+    rt.ensure(B, H, W, 77, net.cin0, ("plain",), cond_hw=(8 * H, 8 * W) if net.kind == "controlnet" else None, twin=twin,
+              **ensure_kw)
+    forms = [f for f, _ in net.xattn_forms(rt.lib, B, H, W, 77).values()]
+    folded = [f for f in forms if f is not F.CHAIN]
+    # the setup plan folds exactly the transformers whose form is not the chain, each in its form's layout (kperm) ...
+    assert [c[1][17] for c in rt.setup_plan.calls if c[2] == "xattn_fold"] == [f.value for f in folded]
+    assert [v.form for v in net.xa.values()] == folded and {f.value for f in folded} <= {0, 1, 2}
+    # ... and the step plan runs each in that form: the block launches with / without attn1.to_out in front, the first GEMM
+    # of the two-GEMM form by its softmax epilogue, and the attn2 chain's 77-key attention where nothing was folded
+    blocks = [c for c in rt.step_plan.calls if c[2] == "xattn_block"]
+    got = (sum(1 for c in blocks if c[1][19]), sum(1 for c in blocks if not c[1][19]),
+           sum(1 for a in rt.step_plan.keep if getattr(a, "act", 0) == L.PP_ACT_SOFTMAX80))
+    assert got == (forms.count(F.BLOCK_PRE), forms.count(F.BLOCK), forms.count(F.TWO_GEMM)), (got, forms)
+    assert [c[2] for c in rt.step_plan.calls].count("attention") == len(forms) + forms.count(F.CHAIN)
+    return got, rt
+
+
+def _full_net(kind="unet", cin=9, off=(), **kw):
+    net = SDNet(kind, cin, **kw)
+    for switch in off:                    # (per instance, before packing: the switches also decide what is packed)
+        setattr(net, switch, False)
+    net.load_state_dict(net.synthetic_state_dict(meta=True), "cpu", materialize=False)
+    return net
+
+
+def test_forms_resolved_in_setup_are_the_forms_the_step_runs():
+    """SDNet.xattn_form is the one place a cross-attention form is decided: what build_setup folds and what the step plan
+    launches are both its answer, at every geometry class of the full networks (counts as measured on the parent commit:
+    (BLOCK_PRE, BLOCK, TWO_GEMM) of the 16 / 7 transformers, the rest on the chain)."""
+    from powerpaint_amd.engine import TWIN_PREFIX
+    if not all(getattr(SDNet, s) for s in ("fold_ln", "fuse_xattn", "fuse_xattn_pre", "fuse_xattn_wide", "fuse_xattn_2g")) \
+            or SDNet.xattn_wide_max_c != 640 or not TWIN_PREFIX:
+        pytest.skip("lab switches")
+    for (H, W, twin, want, n_tv) in ((64, 64, False, (5, 5, 6), 0), (32, 32, False, (5, 5, 5), 0), (16, 16, False, (5, 5, 0), 1),
+                                     (16, 8, True, (5, 0, 0), None), (8, 8, False, (0, 0, 0), None),
+                                     (13, 10, False, (0, 0, 0), 16), (29, 32, False, (0, 0, 5), None)):
+        got, rt = _forms_against_plans(_full_net(), 2, H, W, twin)
+        assert got == want, (H, W, got)
+        if n_tv is not None:
+            assert [c[2] for c in rt.step_plan.calls].count("transpose_v") == n_tv, (H, W)
+        # the twin prefix is taken where asked for (16x8: 128 positions, one tile of the block kernel per batch item)
+        assert bool([a for a in rt.step_plan.keep if a.out_dup_rows]) == twin
+        assert rt.net.twin_prefix_ok(rt.lib, 2, H, W, 77) == ((H * W) % 128 == 0)
+    got, _ = _forms_against_plans(_full_net("controlnet", 4, conditioning_channels=3), 2, 32, 32)
+    assert got == (2, 2, 2)
+    # one IP-Adapter loaded: every cross-attention on the chain (its adds sit between attention and to_out), no twin prefix
+    net = _full_net()
+    kv = {pre: (torch.zeros(c, 768), torch.zeros(c, 768)) for pre, c in net._attn_specs()}
+    net.set_ip_adapters([{"proj.weight": torch.zeros(4 * 768, 32), "proj.bias": torch.zeros(4 * 768),
+                          "norm.weight": torch.ones(768), "norm.bias": torch.zeros(768), "kv": kv}])
+    got, rt = _forms_against_plans(net, 2, 64, 64, twin=True, ip_n=[1])
+    assert got == (0, 0, 0) and not net.xa and not net.twin_prefix_ok(rt.lib, 2, 64, 64, 77)
+    assert not [a for a in rt.step_plan.keep if a.out_dup_rows]
+
+
+@pytest.mark.parametrize("H,W", [(64, 64), (29, 32)])
+@pytest.mark.parametrize("switch", ["fold_ln", "merge_ff2_proj_out", "fuse_xattn", "fuse_tfront", "fuse_xattn_pre", "fuse_ff",
+                                    "ff_w8", "attn_log2", "fuse_xattn_wide", "fuse_xattn_2g"])
+def test_forms_agree_with_each_transformer_switch_off(switch, H, W):
+    """Every transformer lab switch, taken off on the instance, still compiles, and setup and step still agree on the forms."""
+    got, _ = _forms_against_plans(_full_net(off=(switch,)), 2, H, W, twin=True)
+    if switch == "fuse_xattn":
+        assert got == (0, 0, 0)

@@ -1,22 +1,30 @@
 #!/usr/bin/env python
 """usage: tools/plan_dump.py OUT [TREE] -- every launch of the compiled plans on a CPU arena, no GPU: launch names in order, every
 field of each PPGemmArgs and every scalar argument of the other launches, pointers as offsets into the arena (A+) or the
-packed weights (W+).  Both UNets (the 4-channel one behind a BrushNet), BrushNet and ControlNet, setup and step plans, twin
-prefix asked for and not, at 64x64 latents batch 8 and 16x16 batch 2, and the VAE plans.  Two trees whose dumps are equal
-byte for byte compile the same plans (TREE: the checkout to import from, default this one): how a change to the plan
-compiler shows that it leaves the shipped shapes alone."""
+packed weights (W+), and per plan the FLOP accounting (flops, flops_skipped, flops_by_kind) and the arena's peak.
+In full text: both UNets (the 4-channel one behind a BrushNet), BrushNet and ControlNet, setup and step plans, twin prefix
+asked for and not, at 64x64 latents batch 8 and 16x16 batch 2; the full UNet at batch 2 at 32x32, 16x8 (twin), 8x8, 29x32 and
+13x10, and in fp16 at 64x64; the VAE plans.  As one sha256 line per case: the full UNet at batch 2 with every one and every
+pair of the transformer switches taken off on the instance, at 64x64, 32x32, 29x32 and 13x10, twin asked for and not, and with
+the wide cross-attention block let up to C = 1280.  Two trees whose dumps are equal byte for byte compile the same plans
+(TREE: the checkout to import from, default this one): how a change to the plan compiler shows that it leaves them alone."""
+import hashlib
+import itertools
 import os
 import sys
 
 out = sys.argv[1]
 tree = sys.argv[2] if len(sys.argv) > 2 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, tree)
+import torch
 from powerpaint_amd import _lib as L
 from powerpaint_amd.engine import SDNet
 from powerpaint_amd.runtime import NetRuntime
 from powerpaint_amd.vae import VAENet
 from powerpaint_amd.engine import Arena, Builder, Act
 
+SWITCHES = ("fold_ln", "merge_ff2_proj_out", "fuse_xattn", "fuse_tfront", "fuse_xattn_pre", "fuse_ff", "ff_w8", "attn_log2",
+            "fuse_xattn_wide", "fuse_xattn_2g")
 
 RANGES = []
 def norm(x):
@@ -27,7 +35,7 @@ def norm(x):
             return f"{tag}+{x - lo}"
     return x
 
-def desc(plan, base):
+def desc(plan):
     rows = []
     for fn, args, name in plan.calls:
         a = getattr(args[0], "_obj", None) if args else None
@@ -45,34 +53,67 @@ def desc(plan, base):
             rows.append(name + " " + " ".join(str(norm(x)) if not hasattr(x, '_obj') else 'ref' for x in args))
     return rows
 
+def totals(plan):
+    kinds = " ".join(f"{k}={v!r}" for k, v in sorted(plan.flops_by_kind.items()))
+    return f"flops={plan.flops!r} flops_skipped={plan.flops_skipped!r} by_kind: {kinds}"
+
+def compiled(kind, cin, cfg, B, H, W, twin, off=(), **attrs):
+    """-> lines of the setup and the step plan of one network, built as NetRuntime builds them."""
+    net = SDNet(kind, cin, **cfg)
+    for name in off:
+        setattr(net, name, False)
+    for name, v in attrs.items():
+        setattr(net, name, v)
+    net.load_state_dict(net.synthetic_state_dict(meta=True), "cpu", materialize=False)
+    rt = NetRuntime(net, "cpu")
+    wiring = ("plain",)
+    if kind == "unet" and cin == 4:
+        sh = rt._residual_shapes(B, H, W, with_up=True)
+        wiring = ("brushnet", {k: [0] * len(v) for k, v in sh.items()})
+    rt.ensure(B, H, W, 77, net.cin0, wiring, cond_hw=(8 * H, 8 * W) if kind == "controlnet" else None, twin=twin)
+    base, pb_ = rt.arena.base, net.params.buf
+    RANGES[:] = [("A", base, base + rt.arena.size + 4096), ("W", pb_.data_ptr(), pb_.data_ptr() + pb_.numel() + 4096)]
+    rows = []
+    for tag, plan in (("setup", rt.setup_plan), ("step", rt.step_plan)):
+        rows.append(f"## {kind} cin={cin} {net.dtype} B={B} {H}x{W} twin={twin} {tag}: {len(plan.calls)} launches")
+        rows += desc(plan)
+        rows.append(f"# {tag} {totals(plan)}")
+    rows.append(f"# arena peak={rt.arena.peak}")
+    return rows
+
 lines = []
-for (B, hw) in ((8, 64), (2, 16)):
-    for kind, cin, cfg in (("unet", 9, {}), ("unet", 4, {}), ("brushnet", 4, dict(conditioning_channels=5)), ("controlnet", 4, dict(conditioning_channels=3))):
-        for twin in (False, True):
-            net = SDNet(kind, cin, **cfg)
-            net.load_state_dict(net.synthetic_state_dict(meta=True), "cpu", materialize=False)
-            rt = NetRuntime(net, "cpu")
-            wiring = ("plain",)
-            if kind == "unet" and cin == 4:
-                sh = rt._residual_shapes(B, hw, hw, with_up=True)
-                wiring = ("brushnet", {k: [0] * len(v) for k, v in sh.items()})
-            rt.ensure(B, hw, hw, 77, net.cin0, wiring, cond_hw=(8 * hw, 8 * hw) if kind == "controlnet" else None, twin=twin)
-            base = rt.arena.base
-            pb_ = net.params.buf
-            RANGES[:] = [("A", base, base + rt.arena.size + 4096), ("W", pb_.data_ptr(), pb_.data_ptr() + pb_.numel() + 4096)]
-            pbase = 0
-            for tag, plan in (("setup", rt.setup_plan), ("step", rt.step_plan)):
-                lines.append(f"## {kind} cin={cin} B={B} {hw}x{hw} twin={twin} {tag}: {len(plan.calls)} launches")
-                lines += desc(plan, min(base, pbase))
+n_full = 0
+NETS = (("unet", 9, {}), ("unet", 4, {}), ("brushnet", 4, dict(conditioning_channels=5)), ("controlnet", 4, dict(conditioning_channels=3)))
+full = [(kind, cin, cfg, B, hw, hw, twin) for (B, hw) in ((8, 64), (2, 16)) for kind, cin, cfg in NETS for twin in (False, True)]
+full += [("unet", 9, {}, 2, H, W, twin) for H, W, twin in ((32, 32, False), (16, 8, True), (8, 8, False), (29, 32, False), (13, 10, False))]
+full += [("unet", 9, dict(dtype=torch.float16), 2, 64, 64, False)]
+for case in full:
+    lines += compiled(*case)
+    n_full += 2
 # VAE
 net = VAENet(); net.load_state_dict(net.synthetic_state_dict(seed=1), "cpu")
 for hw in (64, 16):
     dry = Arena(); pb = Builder(dry)
     net.build_decode(pb, Act(dry.alloc(hw * hw * 16), 1, hw, hw, 8), dry.alloc(4 * 64 * hw * hw * 4))
     RANGES[:] = [("A", dry.base, dry.base + (1 << 40)), ("W", net.params.buf.data_ptr(), net.params.buf.data_ptr() + net.params.buf.numel() + 4096)]
-    lines.append(f"## vae decode {hw}"); lines += desc(pb.plan, dry.base)
+    lines.append(f"## vae decode {hw}"); lines += desc(pb.plan); lines.append(f"# {totals(pb.plan)} peak={dry.peak}")
     dry = Arena(); pb = Builder(dry)
     net.build_encode(pb, Act(dry.alloc(64 * hw * hw * 16), 1, 8 * hw, 8 * hw, 8))
-    lines.append(f"## vae encode {hw}"); lines += desc(pb.plan, dry.base)
+    lines.append(f"## vae encode {hw}"); lines += desc(pb.plan); lines.append(f"# {totals(pb.plan)} peak={dry.peak}")
+    n_full += 2
+# switched-off plans, one digest line each
+n_digest = 0
+def digest(tag, *a, **kw):
+    global n_digest
+    text = "\n".join(compiled("unet", 9, {}, 2, *a, **kw))
+    lines.append(f"sha256 {hashlib.sha256(text.encode()).hexdigest()} {tag}")
+    n_digest += 1
+
+for (H, W) in ((64, 64), (32, 32), (29, 32), (13, 10)):
+    for twin in (False, True):
+        for off in itertools.chain(((),), itertools.combinations(SWITCHES, 1), itertools.combinations(SWITCHES, 2)):
+            digest(f"{H}x{W} twin={twin} off={','.join(off) or '-'}", H, W, twin, off)
+for hw in (64, 32, 16):
+    digest(f"{hw}x{hw} twin=False xattn_wide_max_c=1280", hw, hw, False, xattn_wide_max_c=1280)
 open(out, "w").write("\n".join(lines) + "\n")
-print(len(lines), "lines")
+print(len(lines), "lines,", n_full, "full-text plans,", n_digest, "digest cases, library", L.build_id())
