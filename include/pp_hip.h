@@ -247,6 +247,14 @@ typedef struct PPGemmArgs {
    * only, one pass (splitk <= 1), one source tensor, no 1x1 tail, no gn_in_* / gn_next_* / out_dup_rows / res1_wrap_rows:
    * PP_ERR_UNSUPPORTED otherwise (pp_upconv_subpix_supported() tells).  0: every request of ABI v27 as before. */
   int32_t subpix;
+  /* (added under ABI 29 as the LAST field; 0 = every request as before -- a caller built against an older header of this
+   * version must be rebuilt: tests/test_abi.py compares the struct sizes)  The tile order of the launch.  The kernels give every XCD a contiguous range of tile ids; the ids walk groups of
+   * `tile_group_m` M panels -- inside a group the M tile runs fastest, then the N tile, the last group may be shorter -- so the
+   * workgroups resident on an XCD share tile_group_m activation panels and resident / tile_group_m weight strips in its L2.
+   * 0 = automatic (the library models the fabric reads of the launch and picks the group height: DESIGN.md section 4);
+   * > 0 forces that height, clamped to the M tiles of the form (1 = M-major, a large value = N-major); < 0: PP_ERR_BAD_ARG.
+   * Like `tile` / `splitk` a tuning wish: the result is bit for bit the same in every order. */
+  int32_t tile_group_m;
 } PPGemmArgs;
 #define PP_GN_SUM_SCALE 16777216.0f /* 2^24 */
 #define PP_GN_SQ_SCALE 1048576.0f   /* 2^20 */
@@ -352,6 +360,9 @@ size_t pp_gemm_combine_ctr_bytes(const PPGemmArgs* args);
 /* (ABI v21) 1 if pp_gemm_bf16 will combine this launch in-kernel (tile_ctr set and every condition met, incl. the
  * gn_next_* apply where requested), else 0: how many kernels the launch is. */
 int pp_gemm_combine_fused(const PPGemmArgs* args);
+/* (added under ABI 29) The tile order pp_gemm_bf16 runs this request in: the group height (see PPGemmArgs.tile_group_m) of the form the
+ * request resolves to, >= 1; 0 if the request does not run.  Pure host logic. */
+int pp_gemm_tile_group_m(const PPGemmArgs* args);
 /* (ABI v21) Launches a probe grid on the current device and SYNCHRONISES it (the one entry point that does): 1 if the
  * workgroups of dim3(tiles, splits) grids are placed on the XCDs round-robin by their linear id (what the in-kernel
  * combine's co-location rests on), else 0.  Cached per device. */

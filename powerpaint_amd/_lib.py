@@ -48,6 +48,7 @@ class PPGemmArgs(C.Structure):
         ("gn_next_sub", i32), ("gn_dup_mask", i32), ("vec_batch_stride", i32),
         ("tile_ctr", vp), ("combine_fault", vp),
         ("subpix", i32),
+        ("tile_group_m", i32),
     ]
 
 
@@ -129,6 +130,7 @@ SIGNATURES = {
     "pp_upconv_fold": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "pp_gemm_combine_ctr_bytes": (sz, [C.POINTER(PPGemmArgs)]),
     "pp_gemm_combine_fused": (C.c_int, [C.POINTER(PPGemmArgs)]),
+    "pp_gemm_tile_group_m": (C.c_int, [C.POINTER(PPGemmArgs)]),
     "pp_xcd_placement_ok": (C.c_int, []),
     "pp_groupnorm_apply_acc": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp, vp, vp, C.c_int, vp,
                                          C.c_int, vp]),

@@ -47,7 +47,7 @@ constexpr int CG_LDS = CG_TAB + 3584;           // 163,328 B of the CU's 163,840
 static_assert(CG_LDS <= 160 * 1024, "LDS budget");
 
 struct CGDerived {
-  int tiles_m, tiles_n, n_major;
+  int tiles_m, tiles_n, group_m;   // group_m: the tile order (tile_order.h)
   int nch1, nch;        // 64-channel chunks of x1, of concat(x1, x2)
   int ntail3, ntail;    // 64-deep K tiles of x3, of concat(x3, x4) (the 1x1 tail)
   int hp;               // pixels of the halo tile = BM + 2 W
@@ -111,13 +111,7 @@ __global__ void __launch_bounds__(CG_T, 2) pp_conv_gn_kernel(const PPGemmArgs a,
   const int par = SUBPIX ? (lid & 3) : 0, pa = par >> 1, pb = par & 1;
   if constexpr (SUBPIX) lid >>= 2;
   int tile_m, tile_n;
-  if (d.n_major) {
-    tile_n = lid / d.tiles_m;
-    tile_m = lid - tile_n * d.tiles_m;
-  } else {
-    tile_m = lid / d.tiles_n;
-    tile_n = lid - tile_m * d.tiles_n;
-  }
+  pp_tile_decode(lid, d.tiles_m, d.tiles_n, d.group_m, &tile_m, &tile_n);
   const int m_blk = tile_m * BM, n_blk = tile_n * BN;
   const int split = blockIdx.y, splits = gridDim.y;
   // every split takes an equal share of the chunks AND of the tail tiles
@@ -880,13 +874,13 @@ CGChoice cg_choose(const PPGemmArgs& a) {
 }
 
 template <int BM, int HPW, bool PP, int NMODE, int EDT>
-int cg_launch(const PPGemmArgs& a, int splitk, hipStream_t st) {
+int cg_launch(const PPGemmArgs& a, int splitk, int group_m, hipStream_t st) {
   auto kern = pp_conv_gn_kernel<BM, HPW, PP, NMODE, EDT>;
   if (pp_func_lds(reinterpret_cast<const void*>(kern), CG_LDS, "hipFuncSetAttribute(conv_gn)") != PP_OK) return PP_ERR_LAUNCH;
   CGDerived d;
   d.tiles_m = a.M / BM;
   d.tiles_n = (a.N + CG_BN - 1) / CG_BN;
-  d.n_major = (d.tiles_m < d.tiles_n && d.tiles_m <= 8) ? 1 : 0;
+  d.group_m = group_m < 1 ? 1 : group_m > d.tiles_m ? d.tiles_m : group_m;
   d.nch1 = a.c1 / 64;
   d.nch = (a.c1 + a.c2) / 64;
   d.ntail3 = a.c3 / 64;
@@ -902,18 +896,18 @@ int cg_launch(const PPGemmArgs& a, int splitk, hipStream_t st) {
 // halo strips per wave for a tile: ceil((BM + 2 W) / 64), rounded up to an instantiated count
 //   BM = 256: W = 64 -> 6, W = 32 / 16 -> 5;  BM = 128: W = 128 -> 6, 64 -> 4, <= 32 -> 3;  BM = 64: W = 64 -> 3, <= 32 -> 2
 template <int BM, bool PP, int NMODE, int EDT>
-int cg_launch_hpw(const PPGemmArgs& a, int splitk, hipStream_t st) {
+int cg_launch_hpw(const PPGemmArgs& a, int splitk, int group_m, hipStream_t st) {
   const int need = (BM + 2 * a.wout + 63) / 64;
   if constexpr (BM == 256) {
-    if (need <= 5) return cg_launch<256, 5, PP, NMODE, EDT>(a, splitk, st);
-    return cg_launch<256, 6, PP, NMODE, EDT>(a, splitk, st);
+    if (need <= 5) return cg_launch<256, 5, PP, NMODE, EDT>(a, splitk, group_m, st);
+    return cg_launch<256, 6, PP, NMODE, EDT>(a, splitk, group_m, st);
   } else if constexpr (BM == 128) {
-    if (need <= 3) return cg_launch<128, 3, PP, NMODE, EDT>(a, splitk, st);
-    if (need <= 4) return cg_launch<128, 4, PP, NMODE, EDT>(a, splitk, st);
-    return cg_launch<128, 6, PP, NMODE, EDT>(a, splitk, st);
+    if (need <= 3) return cg_launch<128, 3, PP, NMODE, EDT>(a, splitk, group_m, st);
+    if (need <= 4) return cg_launch<128, 4, PP, NMODE, EDT>(a, splitk, group_m, st);
+    return cg_launch<128, 6, PP, NMODE, EDT>(a, splitk, group_m, st);
   } else {
-    if (need <= 2) return cg_launch<64, 2, PP, NMODE, EDT>(a, splitk, st);
-    return cg_launch<64, 3, PP, NMODE, EDT>(a, splitk, st);
+    if (need <= 2) return cg_launch<64, 2, PP, NMODE, EDT>(a, splitk, group_m, st);
+    return cg_launch<64, 3, PP, NMODE, EDT>(a, splitk, group_m, st);
   }
 }
 
@@ -926,10 +920,10 @@ int cg_dispatch(const PPGemmArgs& a, const CGChoice& c, hipStream_t st) {
   if (!pp || nm != 1) {
 #define CG_CASE(BM_)                                                                        \
     case BM_:                                                                               \
-      if (!pp) return cg_launch_hpw<BM_, false, 1, EDT>(a, c.splitk, st);                   \
-      if (nm == 0) return cg_launch_hpw<BM_, true, 0, EDT>(a, c.splitk, st);                \
-      if (nm == 2) return cg_launch_hpw<BM_, true, 2, EDT>(a, c.splitk, st);                \
-      return cg_launch_hpw<BM_, true, 3, EDT>(a, c.splitk, st);
+      if (!pp) return cg_launch_hpw<BM_, false, 1, EDT>(a, c.splitk, c.group_m, st);                   \
+      if (nm == 0) return cg_launch_hpw<BM_, true, 0, EDT>(a, c.splitk, c.group_m, st);                \
+      if (nm == 2) return cg_launch_hpw<BM_, true, 2, EDT>(a, c.splitk, c.group_m, st);                \
+      return cg_launch_hpw<BM_, true, 3, EDT>(a, c.splitk, c.group_m, st);
     switch (c.bm) {
       CG_CASE(256)
       CG_CASE(128)
@@ -941,22 +935,22 @@ int cg_dispatch(const PPGemmArgs& a, const CGChoice& c, hipStream_t st) {
 #endif
   if (a.subpix) {                     // the sub-pixel form of an upsampling conv (cg_subpix_ok)
     switch (c.bm) {
-      case 256: return cg_launch_hpw<256, true, 4, EDT>(a, 1, st);
-      case 128: return cg_launch_hpw<128, true, 4, EDT>(a, 1, st);
-      default: return cg_launch_hpw<64, true, 4, EDT>(a, 1, st);
+      case 256: return cg_launch_hpw<256, true, 4, EDT>(a, 1, c.group_m, st);
+      case 128: return cg_launch_hpw<128, true, 4, EDT>(a, 1, c.group_m, st);
+      default: return cg_launch_hpw<64, true, 4, EDT>(a, 1, c.group_m, st);
     }
   }
   if (!a.gn_in_acc) {                 // plain conv: the loop without the normalisation (cg_raw_ok)
     switch (c.bm) {
-      case 256: return cg_launch_hpw<256, true, 2, EDT>(a, c.splitk, st);
-      case 128: return cg_launch_hpw<128, true, 2, EDT>(a, c.splitk, st);
-      default: return cg_launch_hpw<64, true, 2, EDT>(a, c.splitk, st);
+      case 256: return cg_launch_hpw<256, true, 2, EDT>(a, c.splitk, c.group_m, st);
+      case 128: return cg_launch_hpw<128, true, 2, EDT>(a, c.splitk, c.group_m, st);
+      default: return cg_launch_hpw<64, true, 2, EDT>(a, c.splitk, c.group_m, st);
     }
   }
   switch (c.bm) {
-    case 256: return cg_launch_hpw<256, true, 1, EDT>(a, c.splitk, st);
-    case 128: return cg_launch_hpw<128, true, 1, EDT>(a, c.splitk, st);
-    default: return cg_launch_hpw<64, true, 1, EDT>(a, c.splitk, st);
+    case 256: return cg_launch_hpw<256, true, 1, EDT>(a, c.splitk, c.group_m, st);
+    case 128: return cg_launch_hpw<128, true, 1, EDT>(a, c.splitk, c.group_m, st);
+    default: return cg_launch_hpw<64, true, 1, EDT>(a, c.splitk, c.group_m, st);
   }
 }
 
@@ -978,6 +972,14 @@ int pp_conv_gn_form(const PPGemmArgs& a, CGChoice* c) {
   }
   *c = cg_choose(a);
   return 1;
+}
+// tile_order.h's operands of a halo-tile launch: a panel is the tile's rows plus one image row above and below, over the
+// source channels (not the nine taps), plus the rows of the 1x1 tail; the sub-pixel form reads four folded matrices per
+// (tile, strip) -- its parities are neighbours in the id -- so its strip is the four of them
+void pp_conv_gn_operand_bytes(const PPGemmArgs& a, int bm, long long* panel, long long* strip) {
+  const long long px = bm + 2 * a.wout;               // halo-tile pixels; (a.up) gathered from a quarter as many source pixels
+  *panel = (a.up ? (px + 3) / 4 : px) * (a.c1 + a.c2) * 2ll + (long long)bm * (a.c3 + a.c4) * 2ll;
+  *strip = (long long)(a.N < CG_BN ? a.N : CG_BN) * a.K * 2ll * (a.subpix ? 4 : 1);
 }
 int pp_conv_gn_run(const PPGemmArgs& a, const CGChoice& c, hipStream_t st) {
   if (c.splitk > 1 && !a.workspace) return PP_ERR_WORKSPACE;

@@ -16,8 +16,13 @@
 //   * buffer loads with out-of-range offsets return 0: the 3x3 halo, nearest-2x upsample, stride-2 and the two-source
 //     channel concat of the up blocks are pure address arithmetic in the loader -- no im2col / concat / upsample
 //     tensor ever touches HBM;
-//   * workgroup id -> tile mapping is XCD-aware (8 XCDs, private 4 MiB L2 each): the blocks resident on one XCD walk
-//     consecutive N tiles of the same M panel, so the activation panel is fetched from HBM once per XCD.
+//   * workgroup id -> tile mapping is XCD-aware (8 XCDs, private 4 MiB L2 each): every XCD owns a contiguous range of
+//     tile ids, and the ids walk groups of `group_m` M panels (tile_order.h) -- the blocks resident on one XCD share a few
+//     activation panels AND a few weight strips in its L2, the split chosen per launch from the modelled fabric reads.
+#include <array>
+#include <map>
+#include <mutex>
+
 #include "pp_common.h"
 #include "gemm_gn.h"
 #include "gemm_combine.h"
@@ -29,7 +34,7 @@ namespace {
 
 struct GemmDerived {
   int tiles_m, tiles_n, kt_total, kt_per_split, ctiles;
-  int n_major;   // 1: consecutive tile ids walk the M tiles of one N tile (the blocks of an XCD share the W strip)
+  int group_m;   // tile order (tile_order.h): ids walk groups of group_m M panels; 1 = M-major, tiles_m = N-major
 };
 
 // Folded LayerNorm: per-row (mean, rstd) from the producer's per-N-tile (sum, sum of squares) partials.
@@ -134,17 +139,9 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) pp_gemm_kernel(const PPGemmArg
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
     lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
-  // the blocks resident on one XCD take consecutive tile ids: M-major ids walk the N tiles of one M panel (the activation
-  // panel is fetched into that XCD's L2 once), N-major ids the M tiles of one N strip (small-M launches, where the
-  // weight strip is the big operand: every XCD would otherwise pull the whole matrix through the fabric)
+  // the blocks resident on one XCD take consecutive tile ids, which walk groups of d.group_m M panels (tile_order.h)
   int tile_m, tile_n;
-  if (d.n_major) {
-    tile_n = lid / d.tiles_m;
-    tile_m = lid - tile_n * d.tiles_m;
-  } else {
-    tile_m = lid / d.tiles_n;
-    tile_n = lid - tile_m * d.tiles_n;
-  }
+  pp_tile_decode(lid, d.tiles_m, d.tiles_n, d.group_m, &tile_m, &tile_n);
   const int m_blk = tile_m * BM, n_blk = tile_n * BN;
   const int split = blockIdx.y;
   const int kt_begin = split * d.kt_per_split;
@@ -399,17 +396,9 @@ pp_gemm_kernel_v2(const PPGemmArgs a, const GemmDerived d) {   // 2nd bound = wa
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
     lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
-  // the blocks resident on one XCD take consecutive tile ids: M-major ids walk the N tiles of one M panel (the activation
-  // panel is fetched into that XCD's L2 once), N-major ids the M tiles of one N strip (small-M launches, where the
-  // weight strip is the big operand: every XCD would otherwise pull the whole matrix through the fabric)
+  // the blocks resident on one XCD take consecutive tile ids, which walk groups of d.group_m M panels (tile_order.h)
   int tile_m, tile_n;
-  if (d.n_major) {
-    tile_n = lid / d.tiles_m;
-    tile_m = lid - tile_n * d.tiles_m;
-  } else {
-    tile_m = lid / d.tiles_n;
-    tile_n = lid - tile_m * d.tiles_n;
-  }
+  pp_tile_decode(lid, d.tiles_m, d.tiles_n, d.group_m, &tile_m, &tile_n);
   const int m_blk = tile_m * BM, n_blk = tile_n * BN;
   const int split = blockIdx.y;
   const int kt_begin = split * d.kt_per_split;
@@ -1513,8 +1502,9 @@ bool reduce_lean_ok(const PPGemmArgs& a) {
 struct TileForm {
   int id, bm;
   bool pp, v2;
+  int waves, stages;   // waves of a workgroup, LDS pipeline stages (V2): what decides how many workgroups a CU holds
 };
-#define PP_ROW(ID, BM_, WM_, NS_, PP_, V2_) {ID, BM_, PP_, V2_},
+#define PP_ROW(ID, BM_, WM_, NS_, PP_, V2_) {ID, BM_, PP_, V2_, WM_ * 2, NS_},
 constexpr TileForm TILE_FORMS[] = {PP_TILE_FORMS(PP_ROW)};
 #undef PP_ROW
 const TileForm* tile_form(int id) {
@@ -1527,7 +1517,7 @@ struct Choice {
   int tile, splitk;
 };
 bool gemm_pingpong();
-bool gemm_n_major();
+bool gemm_tile_order();
 
 // v2 (LDS-direct pipeline + staged 16-byte epilogue) needs 16-byte aligned rows on every tensor the epilogue touches
 bool v2_ok(const PPGemmArgs& a) {
@@ -1669,24 +1659,24 @@ int launch_combine(const PPGemmArgs& a, int splitk, hipStream_t st) {
   return PP_OK;
 }
 
-GemmDerived derive(const PPGemmArgs& a, int bm, int bn, int splitk) {
+GemmDerived derive(const PPGemmArgs& a, int bm, int bn, int splitk, int group_m) {
   GemmDerived d;
   d.tiles_m = (a.M + bm - 1) / bm;
   d.tiles_n = (a.N + bn - 1) / bn;
   d.kt_total = a.K / 64;
   d.kt_per_split = (d.kt_total + splitk - 1) / splitk;
   d.ctiles = (a.c1 + a.c2) / 64;
-  d.n_major = (gemm_n_major() && d.tiles_m < d.tiles_n && d.tiles_m <= 8) ? 1 : 0;
+  d.group_m = group_m < 1 ? 1 : group_m > d.tiles_m ? d.tiles_m : group_m;
   return d;
 }
 
 template <int BM, int BN, int WM, int WN, int XMODE, int EDT>
-int launch(const PPGemmArgs& a, int splitk, hipStream_t st) {
+int launch(const PPGemmArgs& a, int splitk, int group_m, hipStream_t st) {
   constexpr int T = WM * WN * 64;
   constexpr int LDS = 2 * (BM + BN) * 128;
   auto kern = pp_gemm_kernel<BM, BN, WM, WN, XMODE, EDT>;
   if (pp_func_lds(reinterpret_cast<const void*>(kern), LDS, "hipFuncSetAttribute(gemm)") != PP_OK) return PP_ERR_LAUNCH;
-  const GemmDerived d = derive(a, BM, BN, splitk);
+  const GemmDerived d = derive(a, BM, BN, splitk, group_m);
   dim3 grid(d.tiles_m * d.tiles_n, splitk, 1);
   hipLaunchKernelGGL(kern, grid, dim3(T), LDS, st, a, d);
   PP_CHECK_LAUNCH("pp_gemm_kernel");
@@ -1694,8 +1684,9 @@ int launch(const PPGemmArgs& a, int splitk, hipStream_t st) {
   return PP_OK;
 }
 
-// (lab build) PP_GEMM_NMAJOR=0|1: A/B switch for the N-major tile order of small-M launches (default 1)
-bool gemm_n_major() {
+// (lab build) PP_GEMM_NMAJOR=0|1: A/B switch of the tile order -- 0 forces group_m = 1 (M-major) on every launch that does not
+// force an order itself (PPGemmArgs.tile_group_m), 1 (default) lets the chooser of tile_order.h decide
+bool gemm_tile_order() {
   static const int v = pp_lab_env("PP_GEMM_NMAJOR", 1);
   return v != 0;
 }
@@ -1713,17 +1704,17 @@ bool gemm_dma_interleave() {
 }
 
 template <int BM, int BN, int WM, int WN, int XMODE, int NS, int EPI, bool PP, int EDT>
-int launch2(const PPGemmArgs& a, int splitk, hipStream_t st) {
+int launch2(const PPGemmArgs& a, int splitk, int group_m, hipStream_t st) {
   if constexpr (EPI == 0) {
-    if ((a.gn_acc[0] || a.gn_acc[1]) && splitk == 1) return launch2<BM, BN, WM, WN, XMODE, NS, 4, PP, EDT>(a, splitk, st);
+    if ((a.gn_acc[0] || a.gn_acc[1]) && splitk == 1) return launch2<BM, BN, WM, WN, XMODE, NS, 4, PP, EDT>(a, splitk, group_m, st);
   }
   if constexpr (XMODE == PP_X_PLAIN && EPI == 0) {
     if (a.act == PP_ACT_SOFTMAX80) {                   // (one instantiation: the 64 x 160 x 3-stage tile choose() sends it to)
-      if constexpr (BM == 64 && NS == 3 && !PP) return launch2<BM, BN, WM, WN, XMODE, NS, 5, PP, EDT>(a, splitk, st);
+      if constexpr (BM == 64 && NS == 3 && !PP) return launch2<BM, BN, WM, WN, XMODE, NS, 5, PP, EDT>(a, splitk, group_m, st);
       else return PP_ERR_UNSUPPORTED;
     }
-    if (a.act == PP_ACT_GEGLU && splitk == 1) return launch2<BM, BN, WM, WN, XMODE, NS, 2, PP, EDT>(a, splitk, st);
-    if (a.ln_stats || a.row_stats_out) return launch2<BM, BN, WM, WN, XMODE, NS, 1, PP, EDT>(a, splitk, st);
+    if (a.act == PP_ACT_GEGLU && splitk == 1) return launch2<BM, BN, WM, WN, XMODE, NS, 2, PP, EDT>(a, splitk, group_m, st);
+    if (a.ln_stats || a.row_stats_out) return launch2<BM, BN, WM, WN, XMODE, NS, 1, PP, EDT>(a, splitk, group_m, st);
   }
   constexpr bool LNF = EPI == 1 || EPI == 2 || EPI == 5;
   constexpr int T = WM * WN * 64;
@@ -1731,7 +1722,7 @@ int launch2(const PPGemmArgs& a, int splitk, hipStream_t st) {
   constexpr int LDS = NS * (BM + BN) * 128 + (LNF ? 2048 + BM * 32 : 0);
   static_assert(LDS <= 160 * 1024 || (LNF && NS > 2), "LDS budget");
   if constexpr (LDS > 160 * 1024) {   // 256x160 x 3 stages has no room for the prefetch: drop to 2 stages (lock-step)
-    return launch2<BM, BN, WM, WN, XMODE, 2, EPI, false, EDT>(a, splitk, st);
+    return launch2<BM, BN, WM, WN, XMODE, 2, EPI, false, EDT>(a, splitk, group_m, st);
   } else {
   // (2-stage pipelines need their single in-flight refill as early as possible: the spread costs them time)
 #ifdef PP_LAB
@@ -1743,7 +1734,7 @@ int launch2(const PPGemmArgs& a, int splitk, hipStream_t st) {
   auto kern = pp_gemm_kernel_v2<BM, BN, WM, WN, XMODE, NS, EPI, (NS >= 3 && !PP), PP, EDT>;
 #endif
   if (pp_func_lds(reinterpret_cast<const void*>(kern), LDS, "hipFuncSetAttribute(gemm v2)") != PP_OK) return PP_ERR_LAUNCH;
-  const GemmDerived d = derive(a, BM, BN, splitk);
+  const GemmDerived d = derive(a, BM, BN, splitk, group_m);
   dim3 grid(d.tiles_m * d.tiles_n, splitk, 1);
   hipLaunchKernelGGL(kern, grid, dim3(T), LDS, st, a, d);
   PP_CHECK_LAUNCH("pp_gemm_kernel_v2");
@@ -1764,7 +1755,7 @@ bool gn_stats_supported(const PPGemmArgs& a) {
 }
 
 int validate(const PPGemmArgs& a) {
-  if (a.M <= 0 || a.N <= 0 || a.K <= 0 || !pp_dt_ok(a.dtype)) return PP_ERR_BAD_ARG;
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0 || !pp_dt_ok(a.dtype) || a.tile_group_m < 0) return PP_ERR_BAD_ARG;
   if (a.K % 64 != 0 || a.N % 4 != 0) return PP_ERR_BAD_ARG;
   if (!a.x1 || !a.w || !a.out) return PP_ERR_BAD_ARG;
   if (a.x_mode == PP_X_PLAIN) {
@@ -1851,10 +1842,70 @@ struct LaunchForm {
   int bm, tiles;   // rows of an output tile, output tiles of the launch
   int splitk;      // K splits that run (> 1: fp32 slabs in the workspace, combined in-kernel or by a launch behind it)
   bool pp_tile;    // an 8-wave ping-pong tile (every halo-tile kernel that ships is one)
+  int group_m = 1; // the tile order (tile_order.h): tile ids walk groups of group_m M panels
   // A V1 launch splits K and combines with the separate kernels like the others, but its register-staged epilogue has no
   // GroupNorm statistics, no row moments and no in-kernel combine, and pp_gemm_bf16 hands its combine no consumer norm.
   bool staged_epilogue() const { return family != Family::V1; }
 };
+
+// The tile order of a resolved form: PPGemmArgs.tile_group_m where the caller forces one, else the chooser of tile_order.h on
+// the operand sizes of THIS form -- lds / waves: LDS bytes and waves of one workgroup, from which the workgroups an XCD holds
+// at a time follow (the kernels are built for at most two per CU; wgs_per_tile of them run one tile id); CUs and L2 from
+// the device.  Per-item weight matrices (w_batch_stride) share no strip across batch items: the order they had.
+int form_group_m(const PPGemmArgs& a, const LaunchForm& f, int lds, int waves, int wgs_per_tile) {
+  const int tiles_n = (a.N + 159) / 160, tiles_m = (a.M + f.bm - 1) / f.bm;
+  if (a.tile_group_m > 0) return a.tile_group_m < tiles_m ? a.tile_group_m : tiles_m;
+  const int legacy = pp_tile_order_legacy(tiles_m, tiles_n);
+  if (a.w_batch_stride > 0) return legacy;
+  if (!gemm_tile_order()) return 1;
+  // Which launches the chooser is asked for: the halo-tile convs, the others keep the order they had.  Same-box interleaved
+  // A/Bs of the headline step, class by class against the legacy orders (profiles/tile_order_step_ab.txt): halo-tile convs
+  // -0.8 % on one box and -0.2 % on another (noise 0.2 %); tap-major convs (the 8x8 level, N-major already) 0.0 %; plain
+  // GEMMs with K splits -0.1 %; plain GEMMs in one pass +0.2 %, and per launch the 32x32-level GEGLU and QKV are 8 % SLOWER
+  // in groups of 8 panels although the model saves 57 % / 20 % of their reads (profiles/tile_order_launches.txt).  Why the
+  // bytes do not turn into time there is not measured.
+  // (lab) PP_TILE_ORDER_CLASSES = bit mask of the classes asked -- 1 halo-tile convs, 2 tap-major convs, 4 plain GEMMs with K
+  // splits, 8 plain GEMMs in one pass; PP_TILE_ORDER_MIN_PCT = the modelled saving, in percent, below which a launch keeps
+  // its order
+  static const int classes = pp_lab_env("PP_TILE_ORDER_CLASSES", 1);
+  static const int min_pct = pp_lab_env("PP_TILE_ORDER_MIN_PCT", (int)(PP_TILE_ORDER_MIN_SAVING * 100.0 + 0.5));
+  const int cls = f.family == Family::HALO ? 1 : a.x_mode == PP_X_CONV3X3 ? 2 : f.splitk > 1 ? 4 : 8;
+  if (!(classes & cls)) return legacy;
+  PPTileOrderIn in;
+  in.tiles_m = tiles_m;
+  in.tiles_n = tiles_n;
+  in.splits = f.splitk;
+  in.row_bytes = 2ll * a.K;
+  if (f.family == Family::HALO) {
+    pp_conv_gn_operand_bytes(a, f.bm, &in.panel_bytes, &in.strip_bytes);
+  } else if (a.x_mode == PP_X_CONV3X3) {
+    // tap-major implicit GEMM: the SOURCE pixels behind bm output rows (stride 2 reads 4 per row, the nearest upsample a
+    // quarter) + an image row above and below, not the nine-fold im2col view; + the rows of the 1x1 tail
+    const long long src = a.up ? (f.bm + 3) / 4 : (long long)f.bm * a.stride * a.stride;
+    in.panel_bytes = (src + 2 * a.win) * (a.c1 + a.c2) * 2ll + (long long)f.bm * (a.c3 + a.c4) * 2ll;
+    in.strip_bytes = (long long)(a.N < 160 ? a.N : 160) * a.K * 2ll;
+  } else {
+    in.panel_bytes = (long long)(a.M < f.bm ? a.M : f.bm) * a.K * 2ll;
+    in.strip_bytes = (long long)(a.N < 160 ? a.N : 160) * a.K * 2ll;
+  }
+  int per_cu = (160 * 1024) / (lds > 0 ? lds : 1);
+  if (per_cu > 32 / waves) per_cu = 32 / waves;
+  per_cu = per_cu < 1 ? 1 : per_cu > 2 ? 2 : per_cu;
+  in.resident_per_xcd = per_cu * ((pp_cu_count() + PP_XCDS - 1) / PP_XCDS) / wgs_per_tile;
+  in.l2_bytes = pp_l2_bytes();
+  // the walk costs 10 - 30 us of host time at the step's grids and a plan asks several times per launch: remembered per input
+  typedef std::array<long long, 9> Key;
+  static std::mutex mu;
+  static std::map<Key, int> memo;
+  const Key key = {in.tiles_m, in.tiles_n, in.splits, in.panel_bytes, in.strip_bytes, in.row_bytes, in.resident_per_xcd, in.l2_bytes,
+                   min_pct};
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = memo.find(key);
+  if (it != memo.end()) return it->second;
+  const int g = pp_tile_order_choose(in, min_pct * 0.01);
+  if (memo.size() < 4096) memo[key] = g;
+  return g;
+}
 
 // PP_OK, or why nothing runs: PP_ERR_UNSUPPORTED = gn_in_* asks for the fused-norm conv and conv_gn.hip cannot do the shape;
 // PP_ERR_BAD_ARG = PPGemmArgs.tile names no tile form
@@ -1865,12 +1916,18 @@ int resolve_form(const PPGemmArgs& a, LaunchForm* f) {
   if (halo < 0) return halo;
   if (halo) {
     *f = LaunchForm{Family::HALO, 0, cg.bm, (a.M / cg.bm) * tn * (a.subpix ? 4 : 1), cg.splitk, true};
+    // (sub-pixel form: the four parities of a tile are neighbours in front of the decode -- four workgroups per tile id)
+    f->group_m = form_group_m(a, *f, 160 * 1024, 8, a.subpix ? 4 : 1);
     return PP_OK;
   }
   const Choice c = choose(a);
   const TileForm* t = tile_form(c.tile);
   if (!t) return PP_ERR_BAD_ARG;
   *f = LaunchForm{t->v2 ? Family::V2 : Family::V1, t->id, t->bm, ((a.M + t->bm - 1) / t->bm) * tn, c.splitk, t->pp};
+  const bool lnf = t->v2 && a.x_mode == PP_X_PLAIN && (a.ln_stats || a.row_stats_out || a.act == PP_ACT_GEGLU || a.act == PP_ACT_SOFTMAX80);
+  int lds = (t->v2 ? t->stages : 2) * (t->bm + 160) * 128 + (lnf ? 2048 + t->bm * 32 : 0);
+  if (lds > 160 * 1024) lds = 2 * (t->bm + 160) * 128 + 2048 + t->bm * 32;   // (launch2: no room for the prefetch -> two stages)
+  f->group_m = form_group_m(a, *f, lds, t->waves, 1);
   return PP_OK;
 }
 
@@ -1885,9 +1942,9 @@ bool combine_fusable(const PPGemmArgs& a, const LaunchForm& f, bool with_consume
 }
 
 template <bool V2, int BM, int WM, int NS, bool PP, int XMODE, int EDT>
-int launch_tile(const PPGemmArgs& a, int splitk, hipStream_t st) {
-  if constexpr (V2) return launch2<BM, 160, WM, 2, XMODE, NS, 0, PP, EDT>(a, splitk, st);
-  else return launch<BM, 160, WM, 2, XMODE, EDT>(a, splitk, st);
+int launch_tile(const PPGemmArgs& a, int splitk, int group_m, hipStream_t st) {
+  if constexpr (V2) return launch2<BM, 160, WM, 2, XMODE, NS, 0, PP, EDT>(a, splitk, group_m, st);
+  else return launch<BM, 160, WM, 2, XMODE, EDT>(a, splitk, group_m, st);
 }
 
 template <int EDT>
@@ -1896,8 +1953,8 @@ int dispatch(const PPGemmArgs& a, const LaunchForm& f, hipStream_t st) {
   switch (f.tile) {
 #define PP_CASE(ID, BM_, WM_, NS_, PP_, V2_)                                                         \
     case ID:                                                                                         \
-      return conv ? launch_tile<V2_, BM_, WM_, NS_, PP_, PP_X_CONV3X3, EDT>(a, f.splitk, st)         \
-                  : launch_tile<V2_, BM_, WM_, NS_, PP_, PP_X_PLAIN, EDT>(a, f.splitk, st);
+      return conv ? launch_tile<V2_, BM_, WM_, NS_, PP_, PP_X_CONV3X3, EDT>(a, f.splitk, f.group_m, st) \
+                  : launch_tile<V2_, BM_, WM_, NS_, PP_, PP_X_PLAIN, EDT>(a, f.splitk, f.group_m, st);
     PP_TILE_FORMS(PP_CASE)
 #undef PP_CASE
     default:
@@ -1937,6 +1994,12 @@ extern "C" size_t pp_gemm_combine_ctr_bytes(const PPGemmArgs* args) {
 // (ADVICE round 6, item 2 -- the cached placement verdict as part of this decision -- would go here)
 static bool combine_fused(const PPGemmArgs& a, const LaunchForm& f) { return a.tile_ctr && combine_fusable(a, f, true, false); }
 
+// (added under ABI 29) the tile order the request runs in: the group height of tile_order.h, 0 = the request does not run
+extern "C" int pp_gemm_tile_group_m(const PPGemmArgs* args) {
+  LaunchForm f;
+  return query_form(args, &f) ? f.group_m : 0;
+}
+
 extern "C" int pp_gemm_combine_fused(const PPGemmArgs* args) {
   LaunchForm f;
   return (query_form(args, &f) && combine_fused(*args, f)) ? 1 : 0;
@@ -1967,7 +2030,7 @@ extern "C" int pp_gemm_bf16(const PPGemmArgs* args, void* stream) {
   if (a.gn_next_out && !gn_next_ok(a, f, a.gn_next_sub)) return PP_ERR_UNSUPPORTED;
   if (f.family == Family::HALO) {      // norm -> SiLU -> conv3x3 (or the plain conv) as one launch of the halo-tile kernel
     if ((a.gn_acc[0] || a.gn_acc[1]) && !gn_stats_supported(a)) return PP_ERR_UNSUPPORTED;
-    const int rc = pp_conv_gn_run(a, CGChoice{f.bm, f.splitk}, st);
+    const int rc = pp_conv_gn_run(a, CGChoice{f.bm, f.splitk, f.group_m}, st);
     if (rc != PP_OK || f.splitk == 1 || fused) return rc;
     return a.dtype == PP_DT_F16 ? launch_combine<PP_DT_F16>(a, f.splitk, st) : launch_combine<PP_DT_BF16>(a, f.splitk, st);
   }

@@ -47,6 +47,22 @@ int pp_cu_count() {
   return n;
 }
 
+// one XCD's L2 (cached per device; 4 MiB if the query fails: the part this library is written for)
+long long pp_l2_bytes() {
+  static std::mutex mu;
+  static std::map<int, long long> l2;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 4ll << 20;
+  std::lock_guard<std::mutex> g(mu);
+  auto it = l2.find(dev);
+  if (it != l2.end()) return it->second;
+  int n = 0;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeL2CacheSize, dev) != hipSuccess || n <= 0) n = 4 << 20;
+  if (n > (4 << 20)) n = 4 << 20;   // (a runtime that reports the sum over the XCDs: the L2 a workgroup sees is one XCD's)
+  l2[dev] = n;
+  return n;
+}
+
 // ---- workgroup -> XCD placement probe (ABI v21; what the in-kernel split-K combine's co-location rests on, gemm_combine.h)
 __global__ void __launch_bounds__(64) pp_xcc_probe_kernel(unsigned* out) {
   if (threadIdx.x == 0) {

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include "pp_hip.h"
+#include "tile_order.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
@@ -133,12 +134,18 @@ void pp_set_last_error(const char* what, hipError_t e);
 int pp_func_lds(const void* kern, int bytes, const char* what);
 // compute units of the current device (pp_api.cpp; cached)
 int pp_cu_count();
+// bytes of one XCD's L2 on the current device (pp_api.cpp; cached)
+long long pp_l2_bytes();
 // The halo-tile conv kernel (conv_gn.hip) as pp_gemm_bf16 and the queries around it (gemm.hip) see it.  pp_conv_gn_form: does
 // this validated request run on it -- 1, *c = the tile rows and K splits it runs with; 0, the tap-major implicit GEMM runs it;
 // PP_ERR_UNSUPPORTED, gn_in_* asks for the fused norm and the kernel cannot do the shape (never a silent fallback).
+// group_m: the tile order (tile_order.h), filled in where the launch form is resolved (gemm.hip: resolve_form).
 struct CGChoice {
   int bm, splitk;
+  int group_m = 1;
 };
+// bytes of one activation panel (halo rows included) and of one weight strip of the request on `bm`-row halo tiles
+void pp_conv_gn_operand_bytes(const PPGemmArgs& a, int bm, long long* panel, long long* strip);
 int pp_conv_gn_form(const PPGemmArgs& a, CGChoice* c);
 int pp_conv_gn_run(const PPGemmArgs& a, const CGChoice& c, hipStream_t st);
 #define PP_CHECK_LAUNCH(what)                         \

@@ -275,7 +275,8 @@ class Plan:
         a = getattr(args[0], "_obj", None) if args else None
         if isinstance(a, L.PPGemmArgs):
             return (f"{name} M={a.M} N={a.N} K={a.K} {'conv' if a.x_mode else 'lin'}"
-                    f"{' s2' if a.stride == 2 else ''}{' up' if a.up else ''}{' cat' if a.c2 else ''}")
+                    f"{' s2' if a.stride == 2 else ''}{' up' if a.up else ''}{' cat' if a.c2 else ''}"
+                    f" gm={L.lib().pp_gemm_tile_group_m(C.byref(a))}")
         return name
 
 

@@ -178,7 +178,7 @@ def groupnorm_apply_acc(x: torch.Tensor, acc: torch.Tensor, gamma, beta, eps: fl
 
 def gemm(x: torch.Tensor, w: torch.Tensor, bias=None, x2=None, res1=None, res2=None, scale: float = 1.0, act: int = 0,
          rowvec=None, rows_per_batch: int = 0, out_f32: bool = False, vt_col0: int = 0, tile: int = 0,
-         splitk: int = 0, row_stats: bool = False, ln_stats=None, ln_colsum=None, ln_dim: int = 0,
+         splitk: int = 0, tile_group_m: int = 0, row_stats: bool = False, ln_stats=None, ln_colsum=None, ln_dim: int = 0,
          ln_eps: float = 1e-5, gn=None, res1_wrap: int = 0, fuse_combine: bool = False, out=None, vt=None, stats=None,
          workspace=None):
     """x [M,K1] (+ x2 [M,K2]) bf16, w [N,K1+K2] bf16 -> out [M,N] (or [M,N/2] for GEGLU; (out, vt) when vt_col0).
@@ -190,6 +190,7 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias=None, x2=None, res1=None, res2=N
     w [nb, N, K]: one matrix per batch item of rows_per_batch rows (PPGemmArgs.w_batch_stride); with act =
     L.PP_ACT_SOFTMAX80 bias / ln_colsum may then be [nb, N] as well (vec_batch_stride).
     res1_wrap: res1 holds that many rows only, row m adds res1[m mod res1_wrap] (PPGemmArgs.res1_wrap_rows).
+    tile / splitk / tile_group_m: the tuning wishes of PPGemmArgs (0 = automatic); the result is the same bit for bit.
     row_stats=True additionally returns the per-row (sum, sumsq) partials [M, ceil(N/160), 2] fp32;
     ln_stats (that layout) + ln_colsum [N] fp32 apply the folded-LayerNorm correction (see include/pp_hip.h)."""
     lib = L.lib()
@@ -224,7 +225,7 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias=None, x2=None, res1=None, res2=N
         a.out_vt, a.vt_col0, a.vt_ld = _p(vt), vt_col0, vt.stride(1)
     elif vt is not None:
         raise L.PPError("gemm: `vt` without vt_col0")
-    a.tile, a.splitk = tile, splitk
+    a.tile, a.splitk, a.tile_group_m = tile, splitk, tile_group_m
     _set_gn(a, gn, rows_per_batch)
     if row_stats:
         tn = (N + 159) // 160
@@ -279,7 +280,7 @@ def _conv_request(x, cout, stride, up, x2, x3, x4, up_size=None) -> L.PPGemmArgs
 def conv3x3(x: torch.Tensor, w: torch.Tensor, bias=None, stride: int = 1, up: bool = False, x2=None, rowvec=None,
             res1=None, res2=None, scale: float = 1.0, tile: int = 0, splitk: int = 0, gn=None, x3=None, x4=None,
             gn_in=None, gn_next=None, dup: bool = False, gn_dup_mask: int = 0, res1_wrap: int = 0,
-            fuse_combine: bool = False, out=None, workspace=None, ynext=None, up_size=None):
+            fuse_combine: bool = False, out=None, workspace=None, ynext=None, up_size=None, tile_group_m: int = 0):
     """x NHWC bf16 [B,H,W,C1] (+x2 [B,H,W,C2]); w bf16 [Cout, 9*(C1+C2)] (k = (ky*3+kx)*C + c) -> NHWC bf16.
     up_size (with up): F.interpolate(size=up_size, mode="nearest") in front of the conv instead of the 2x upsample, 2 H - 1 or
     2 H rows and 2 W - 1 or 2 W columns (Upsample2D with `output_size`).
@@ -313,7 +314,7 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, bias=None, stride: int = 1, up: bo
         a.out_dup_rows = a.M
         if gn_dup_mask:
             a.gn_dup_batch, a.gn_dup_mask = B, gn_dup_mask
-    a.tile, a.splitk = tile, splitk
+    a.tile, a.splitk, a.tile_group_m = tile, splitk, tile_group_m
     _set_gn(a, gn, ho * wo)
     if gn_next is None and ynext is not None:
         raise L.PPError("conv3x3: `ynext` without gn_next")
@@ -352,7 +353,7 @@ def upconv_subpix_supported(x: torch.Tensor, cout: int) -> int:
 
 
 def conv3x3_up_subpix(x: torch.Tensor, wfold: torch.Tensor, bias=None, rowvec=None, res1=None, res2=None, scale: float = 1.0,
-                      tile: int = 0, splitk: int = 0, gn=None, out=None, workspace=None):
+                      tile: int = 0, splitk: int = 0, gn=None, out=None, workspace=None, tile_group_m: int = 0):
     """`nearest 2x -> conv3x3` of x NHWC [B,H,W,C] in its sub-pixel form (PPGemmArgs.subpix) on wfold = upconv_fold(w)
     -> NHWC [B,2H,2W,Cout]; res1 / res2 have the output's shape, `gn` subscriptions describe the output tensor.  Raises
     PPError(PP_ERR_UNSUPPORTED) where upconv_subpix_supported() is 0 or a split is forced; conv3x3(up=True) is the other,
@@ -373,7 +374,7 @@ def conv3x3_up_subpix(x: torch.Tensor, wfold: torch.Tensor, bias=None, rowvec=No
     a.ldres2 = _res_ld(res2, (B, 2 * H, 2 * W, cout), x, "conv3x3_up_subpix: `res2`")
     if rowvec is not None and rowvec.dim() == 2 and rowvec.shape[0] > 1:
         a.ld_rowvec = rowvec.stride(0)
-    a.tile, a.splitk = tile, splitk
+    a.tile, a.splitk, a.tile_group_m = tile, splitk, tile_group_m
     _set_gn(a, gn, H * W)
     a.workspace = _p(_workspace(L.lib(), a, x.device, workspace))
     L.check(L.lib().pp_gemm_bf16(C.byref(a), _s()), "pp_gemm_bf16(sub-pixel upsampling conv)")

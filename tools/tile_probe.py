@@ -2,7 +2,9 @@
 """Tile / split-K probe of the transformer GEMMs of the 16x16 and 32x32 levels (round 5): every (tile, split-K) form
 against the automatic choice, HOT (a hipGraph of 10 back-to-back launches) and COLD IN A GRAPH (10 x [256 MB memset +
 launch] minus 10 x [memset]: cold L2 / MALL as inside the step, no eager launch gaps).
-    python tools/tile_probe.py [shape-name ...]"""
+    python tools/tile_probe.py [shape-name ...]
+PP_TILE_PROBE_GROUPS=0,1,8: additionally every listed tile order (PPGemmArgs.tile_group_m; 0 = the library's choice), one
+line per (tile, group height)."""
 import os
 import sys
 
@@ -27,6 +29,7 @@ SHAPES = [("ff2_16", 2048, 1280, 5120, 1280, L.PP_ACT_NONE, True, False),
           ("w8_23040", 512, 1280, 23040, 0, L.PP_ACT_NONE, True, False)]
 TILES = tuple(int(t) for t in os.environ.get("PP_TILE_PROBE_TILES", "0,32,42,31,54,21,24,33,53").split(","))
 SPLITS = tuple(int(t) for t in os.environ.get("PP_TILE_PROBE_SPLITS", "1,2,4").split(","))
+GROUPS = tuple(int(t) for t in os.environ.get("PP_TILE_PROBE_GROUPS", "0").split(","))
 BIG = None
 
 
@@ -64,13 +67,14 @@ def main():
         b = torch.randn(N, device=dev)
         r = torch.randn(M, N, device=dev).to(dt) if res else None
         print(f"{name}: M={M} N={N} K={K + K2}", flush=True)
-        for tile in TILES:
-            line = f"   tile {tile:2d}:"
+        for tile, gm in ((t_, g_) for t_ in TILES for g_ in GROUPS):
+            line = f"   tile {tile:2d}" + (f" gm {gm:2d}" if GROUPS != (0,) else "") + ":"
             for sk in ((0,) if tile == 0 else SPLITS):
                 if rs and sk > 1:
                     continue
                 try:
-                    f = lambda: ops.gemm(x, w, b, x2=x2, res1=r, act=act, tile=tile, splitk=sk, row_stats=rs)  # noqa: E731
+                    f = lambda: ops.gemm(x, w, b, x2=x2, res1=r, act=act, tile=tile, splitk=sk, tile_group_m=gm,  # noqa: E731
+                                         row_stats=rs)
                     h = graph_us([f])
                     c = graph_us([flush, f]) - t_flush
                     line += f"   sk{sk} {h:6.1f} |{c:6.1f}"
