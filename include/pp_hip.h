@@ -98,6 +98,13 @@ const char* pp_last_error(void);
  * becomes once K and V are folded into its projections (pp_xattn_fold): probabilities = softmax_h(LN2(h) G_h); the second,
  * plain GEMM multiplies them with H = V Wo^T.  No residuals / row vector / statistics / split-K on this launch. */
 #define PP_ACT_SOFTMAX80 3
+/* (added under ABI 29) exact-erf GELU, v = v Phi(v), applied where PP_ACT_SILU is: after the residuals, before the one
+ * rounding of the store, on every path that honours PP_ACT_SILU (the staged and the register-staged epilogue, the full
+ * split-K combine), under every tile form and split count.  PP_X_PLAIN requests without ln_stats / row_stats_out only
+ * (PP_ERR_UNSUPPORTED otherwise: the staged kernel carries the GELU as instantiations of its own, so that the others keep
+ * their register budgets, and the conv and folded-LayerNorm ones have none).  Phi through the Abramowitz-Stegun 7.1.26 erfc of the GEGLU epilogue (|erf error| <= 1.5e-7).  fc1 of
+ * the CLIP vision tower (hidden_act = "gelu").  Any `act` outside 0 .. 4 is PP_ERR_BAD_ARG. */
+#define PP_ACT_GELU 4
 
 typedef struct PPGemmArgs {
   int32_t M, N, K;
@@ -293,7 +300,7 @@ typedef struct PPGemmArgs {
  *     acc = sum_k X[m][k] W[n][k]                                     fp32 (MFMA); split-K: fp32 slabs added in slab order
  *     v   = (acc [folded-LayerNorm correction] + bias[n] + rowvec[m / rows_per_batch][n]) * scale
  *     v   = v + res1[m or m - res1_wrap_rows][n] + res2[m][n]         (the residuals are NOT scaled)
- *     v   = act(v)                                                    PP_ACT_SILU | the GEGLU product | the group softmax
+ *     v   = act(v)                                                    PP_ACT_SILU | PP_ACT_GELU | the GEGLU product | the group softmax
  *     out = v rounded ONCE to the 16-bit format, to nearest even      (no rounding with out_f32)
  * every operation in fp32; nothing is rounded to 16 bits before the store (the row moments and GroupNorm accumulators are
  * formed from the values AS STORED).  With integer data whose partial sums stay below 2^24 the result is therefore exact
@@ -482,6 +489,28 @@ int pp_gn_conv3x3_smallcout(const void* x, int batch, int h, int w, int cin, int
 int pp_nchw_to_nhwc(const void* src, int src_dtype, int batch, int c, int hw, int src_batch_mod, void* dst, int ldc,
                     int c0, int dtype, void* stream);
 int pp_nhwc_to_nchw(const void* src, int batch, int c, int hw, void* dst, int dst_dtype, int dtype, void* stream);
+/* (added under ABI 29) The front of the CLIP vision tower (transformers CLIPVisionEmbeddings + pre_layrnorm; the
+ * `image_encoder` of an IP-Adapter pipeline), two launches around the patch GEMM.
+ * pp_vit_patchify : src fp32|bf16|f16 NCHW [batch][3][h][w] (src_dtype: PP_DT_*) -> dst 16-bit [batch*gh*gw][cols] with row
+ *                   stride ldo >= cols, the im2col rows of a stride-`patch` convolution: gh = h / patch, gw = w / patch
+ *                   (remainder pixels dropped, as the conv drops them); row (b*gh + gy)*gw + gx, column
+ *                   c*patch*patch + ky*patch + kx holds pixel (b, c, gy*patch + ky, gx*patch + kx) -- the flattened order of
+ *                   patch_embedding.weight [N][3][P][P], so the patch embedding is pp_gemm_bf16 against that weight
+ *                   zero-padded along K to cols.  Columns [3*patch*patch, cols) of every row are WRITTEN as zeros (cols and
+ *                   ldo multiples of 8, dst 16-byte aligned; the GEMM wants K = cols % 64 == 0: 588 -> 640 for patch 14).  A
+ *                   copy with one rounding to the 16-bit format: bit-exact on representable values.  Nothing outside rows
+ *                   [0, batch*gh*gw) x columns [0, cols) of dst is written.
+ * pp_vit_embed_ln : y[b*(np+1) + t][C] = LayerNorm(e) * gamma + beta with e = class_embedding + pos[0] for t = 0 and
+ *                   patches[(b*np + t - 1)*ldp ..] + pos[t] for t >= 1; patches (row stride ldp >= C, ldp % 8 == 0),
+ *                   class_embedding [C] and pos [np+1][C] are 16-bit, gamma / beta fp32.  The sum is formed in fp32 from the
+ *                   stored operands and is NOT rounded before the norm; the norm is pp_layernorm's (two passes, same
+ *                   arithmetic); one rounding at the store.  C % 8 == 0, C <= 2048 (PP_ERR_UNSUPPORTED above), any np >= 1,
+ *                   any batch; every pointer 16-byte aligned.  Nothing outside the batch*(np+1) rows x C columns of y is written.  This is hidden state 0
+ *                   of transformers' encoder (after pre_layrnorm). */
+int pp_vit_patchify(const void* src, int src_dtype, int batch, int h, int w, int patch, void* dst, int cols, int ldo,
+                    int dtype, void* stream);
+int pp_vit_embed_ln(const void* patches, int ldp, const void* class_embedding, const void* pos, int batch, int np, int C,
+                    const float* gamma, const float* beta, float eps, void* y, int dtype, void* stream);
 /* out = a + b on bf16 tensors of n elements (n % 8 == 0).  The residual adds that cannot ride a GEMM epilogue:
  * ControlNet `down_block_res_sample + down_block_additional_residual` on the already-consumed skip tensors
  * (/root/reference/powerpaint/models/unet_2d_condition.py:1263-1272,1296-1297). */

@@ -95,6 +95,8 @@ PP_DEVINL void epilogue4(const PPGemmArgs& a, int m, int n, f32x4_t v) {
   }
   if (a.act == PP_ACT_SILU) {
     v[0] = silu_f(v[0]); v[1] = silu_f(v[1]); v[2] = silu_f(v[2]); v[3] = silu_f(v[3]);
+  } else if (a.act == PP_ACT_GELU) {
+    v[0] = gelu_fast_f(v[0]); v[1] = gelu_fast_f(v[1]); v[2] = gelu_fast_f(v[2]); v[3] = gelu_fast_f(v[3]);
   }
   if (a.out_vt && n >= a.vt_col0) {
     const int ncols = a.N - a.vt_col0;
@@ -347,8 +349,9 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) pp_gemm_kernel(const PPGemmArg
 //   * EPI selects the epilogue family, as separate instantiations so that each keeps its register budget (64x160 and the
 //     8-wave 128x160 must stay <= 128 VGPRs for 4 waves/SIMD):  0 = standard;  1 = standard + folded LayerNorm (row
 //     moments out / mean-rstd correction in);  2 = GEGLU in registers (+ optional folded LayerNorm);  4 = standard +
-//     GroupNorm statistics of the output (gn_acc).  1 and 2 are PLAIN-only and prefetch their epilogue operands
-//     into LDS.
+//     GroupNorm statistics of the output (gn_acc);  6 = standard with the exact-erf GELU where 0 has the SiLU (PP_ACT_GELU,
+//     single pass; as a run-time branch of 0 it cost every instantiation 10 - 16 VGPRs and sent the 8-wave 128x160x2 tile to
+//     scratch).  1, 2 and 6 are PLAIN-only; 1 and 2 prefetch their epilogue operands into LDS.
 //   * PP ("ping-pong", 8-wave tiles, NS >= 3): the two waves of every SIMD run half a K step apart -- waves 0-3 issue the
 //     MFMAs of tile t while waves 4-7 read their fragments of tile t and issue the refill DMAs, then the roles swap
 //     (two raw barriers per K step, group 1 enters the loop one barrier late).  In the lock-step loop both waves of a
@@ -1147,7 +1150,10 @@ pp_gemm_kernel_v2(const PPGemmArgs a, const GemmDerived d) {   // 2nd bound = wa
               v0[2] += E16<EDT>::lo(r1[j][1]) + E16<EDT>::lo(r2[j][1]); v0[3] += E16<EDT>::hi(r1[j][1]) + E16<EDT>::hi(r2[j][1]);
               v1[0] += E16<EDT>::lo(r1[j][2]) + E16<EDT>::lo(r2[j][2]); v1[1] += E16<EDT>::hi(r1[j][2]) + E16<EDT>::hi(r2[j][2]);
               v1[2] += E16<EDT>::lo(r1[j][3]) + E16<EDT>::lo(r2[j][3]); v1[3] += E16<EDT>::hi(r1[j][3]) + E16<EDT>::hi(r2[j][3]);
-              if (a.act == PP_ACT_SILU) {
+              if constexpr (EPI == 6) {      // PP_ACT_GELU: instantiations of their own, the others keep their registers
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) { v0[jj] = gelu_fast_f(v0[jj]); v1[jj] = gelu_fast_f(v1[jj]); }
+              } else if (a.act == PP_ACT_SILU) {
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) { v0[jj] = silu_f(v0[jj]); v1[jj] = silu_f(v1[jj]); }
               }
@@ -1715,6 +1721,8 @@ int launch2(const PPGemmArgs& a, int splitk, int group_m, hipStream_t st) {
     }
     if (a.act == PP_ACT_GEGLU && splitk == 1) return launch2<BM, BN, WM, WN, XMODE, NS, 2, PP, EDT>(a, splitk, group_m, st);
     if (a.ln_stats || a.row_stats_out) return launch2<BM, BN, WM, WN, XMODE, NS, 1, PP, EDT>(a, splitk, group_m, st);
+    // (K splits: the kernel writes fp32 slabs and the full combine applies the GELU)
+    if (a.act == PP_ACT_GELU && splitk == 1) return launch2<BM, BN, WM, WN, XMODE, NS, 6, PP, EDT>(a, splitk, group_m, st);
   }
   constexpr bool LNF = EPI == 1 || EPI == 2 || EPI == 5;
   constexpr int T = WM * WN * 64;
@@ -1757,6 +1765,9 @@ bool gn_stats_supported(const PPGemmArgs& a) {
 int validate(const PPGemmArgs& a) {
   if (a.M <= 0 || a.N <= 0 || a.K <= 0 || !pp_dt_ok(a.dtype) || a.tile_group_m < 0) return PP_ERR_BAD_ARG;
   if (a.K % 64 != 0 || a.N % 4 != 0) return PP_ERR_BAD_ARG;
+  if (a.act < PP_ACT_NONE || a.act > PP_ACT_GELU) return PP_ERR_BAD_ARG;      // (an undefined code used to run as PP_ACT_NONE)
+  // the GELU epilogue: plain GEMMs without the folded LayerNorm (the staged kernel has it as instantiations of its own)
+  if (a.act == PP_ACT_GELU && (a.x_mode != PP_X_PLAIN || a.ln_stats || a.row_stats_out)) return PP_ERR_UNSUPPORTED;
   if (!a.x1 || !a.w || !a.out) return PP_ERR_BAD_ARG;
   if (a.x_mode == PP_X_PLAIN) {
     if (a.subpix) return PP_ERR_BAD_ARG;

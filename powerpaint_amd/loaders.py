@@ -134,8 +134,10 @@ def load_scheduler(d: str):
 class PipelinePretrainedMixin:
     """`Pipeline.from_pretrained(dir_or_cached_repo, **component_overrides)` over a diffusers pipeline folder
     (`model_index.json` + one sub-folder per component), as app.py:90-92,168-176 call it.  Components: `unet`, `vae`,
-    `text_encoder` -> the HIP models, `tokenizer` -> transformers' CLIPTokenizer, `scheduler` -> `load_scheduler`;
-    `safety_checker` / `feature_extractor` / `image_encoder` are left out (None).  Keyword arguments naming a component
+    `text_encoder`, `image_encoder` (where the pipeline takes one and the folder lists one: the CLIP vision tower of an
+    IP-Adapter, refused by name if it is no tower the kernels run -- pass `image_encoder=None` to leave it out) -> the HIP
+    models, `tokenizer` -> transformers' CLIPTokenizer, `scheduler` -> `load_scheduler`;
+    `safety_checker` / `feature_extractor` are left out (None).  Keyword arguments naming a component
     (e.g. `brushnet=`, `text_encoder_brushnet=`, `unet=`) are used as given instead of being loaded."""
 
     @classmethod
@@ -153,6 +155,8 @@ class PipelinePretrainedMixin:
                                                                            torch_dtype=torch_dtype),
                    "vae": lambda: PM.AutoencoderKL.from_pretrained(root, subfolder="vae", device=device),
                    "text_encoder": lambda: PM.CLIPTextModel.from_pretrained(root, subfolder="text_encoder", device=device),
+                   "image_encoder": lambda: PM.CLIPVisionModelWithProjection.from_pretrained(root, subfolder="image_encoder",
+                                                                                             device=device),
                    "scheduler": lambda: load_scheduler(os.path.join(root, "scheduler"))}
 
         def tokenizer():

@@ -610,6 +610,41 @@ def nhwc_to_nchw(src: torch.Tensor, dtype=torch.float32):
     return dst
 
 
+def vit_patchify(src: torch.Tensor, patch: int, out: Optional[torch.Tensor] = None, dtype=torch.bfloat16):
+    """src [B, 3, H, W] fp32 | bf16 | fp16 -> the im2col rows of the stride-`patch` patch conv, [B * (H // patch) * (W // patch),
+    cols] 16-bit with columns [3 patch^2, cols) written as zeros (pp_vit_patchify).  out: any [rows, cols] view with unit column
+    stride (a window of a larger buffer; its row stride is the ldo of the launch, what lies outside it is the caller's).
+    Default: cols = 3 patch^2 rounded up to 64."""
+    B, Cc, H, W = src.shape
+    if Cc != 3:
+        raise L.PPError("vit_patchify: src must be [B, 3, H, W]")
+    rows = B * (H // patch) * (W // patch)
+    if out is None:
+        out = torch.empty(rows, (3 * patch * patch + 63) // 64 * 64, dtype=dtype, device=src.device)
+    elif out.dim() != 2 or out.shape[0] != rows or out.stride(1) != 1 or out.stride(0) < out.shape[1] or out.device != src.device:
+        raise L.PPError(f"vit_patchify: `out` must be a [{rows}, cols] row-major 16-bit view on the source's device")
+    src = src.contiguous()
+    L.check(L.lib().pp_vit_patchify(_p(src), _DT[src.dtype], B, H, W, patch, _p(out), out.shape[1], out.stride(0), L.dtype_code(out.dtype),
+                                    _s()), "pp_vit_patchify")
+    return out
+
+
+def vit_embed_ln(patches: torch.Tensor, class_embedding: torch.Tensor, pos: torch.Tensor, batch: int, gamma, beta,
+                 eps: float = 1e-5, out: Optional[torch.Tensor] = None):
+    """LayerNorm([class | patches] + pos) as one launch (pp_vit_embed_ln): patches [batch * np, C] (any row stride >= C), class
+    embedding [C], pos [np + 1, C], all of one 16-bit format; gamma / beta fp32 -> [batch * (np + 1), C].  out: see _norm_out."""
+    Cc = patches.shape[1]
+    npatch = patches.shape[0] // batch
+    ldp = _rows_in(patches, Cc, patches, "vit_embed_ln: `patches`")
+    if patches.shape[0] != batch * npatch or tuple(pos.shape) != (npatch + 1, Cc) or class_embedding.numel() != Cc or \
+            pos.dtype != patches.dtype or class_embedding.dtype != patches.dtype:
+        raise L.PPError("vit_embed_ln: patches [batch * np, C], class_embedding [C], pos [np + 1, C] of one 16-bit format")
+    y = _norm_out(out, (batch * (npatch + 1), Cc), patches, "vit_embed_ln")
+    L.check(L.lib().pp_vit_embed_ln(_p(patches), ldp, _p(class_embedding.contiguous()), _p(pos.contiguous()), batch, npatch, Cc,
+                                    _p(gamma), _p(beta), eps, _p(y), L.dtype_code(patches.dtype), _s()), "pp_vit_embed_ln")
+    return y
+
+
 def add(a: torch.Tensor, b: torch.Tensor):
     out = torch.empty_like(a)
     L.check(L.lib().pp_add_bf16(_p(a), _p(b), _p(out), a.numel(), L.dtype_code(a.dtype), _s()), "pp_add_bf16")

@@ -14,6 +14,93 @@ import numpy as np
 import torch
 
 
+OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+class CLIPImageProcessor:
+    """transformers' `CLIPImageProcessor` as the `feature_extractor` of an IP-Adapter pipeline uses it (host code, PIL for the
+    resize): RGB -> shortest edge to `size` (bicubic, the long edge truncated: int(size * long / short)) -> centre crop to
+    `crop_size` -> * 1/255 -> (x - mean) / std -> NCHW float32.  Images are PIL images or HWC uint8 arrays, or lists of either;
+    `processor(images, return_tensors="pt").pixel_values` is [B, 3, crop, crop]."""
+
+    def __init__(self, size=224, crop_size=224, image_mean=OPENAI_CLIP_MEAN, image_std=OPENAI_CLIP_STD,
+                 rescale_factor: float = 1 / 255, do_resize: bool = True, do_center_crop: bool = True, do_rescale: bool = True,
+                 do_normalize: bool = True, do_convert_rgb: bool = True, resample=3, **unused):
+        if isinstance(size, dict):
+            if "shortest_edge" not in size:
+                raise ValueError(f"CLIPImageProcessor: size must name `shortest_edge`, got {size}")
+            size = size["shortest_edge"]
+        if isinstance(crop_size, dict):
+            crop_size = (crop_size["height"], crop_size["width"])
+        elif isinstance(crop_size, int):
+            crop_size = (crop_size, crop_size)
+        if int(resample) != 3:
+            raise ValueError(f"CLIPImageProcessor: only bicubic resampling (PIL code 3) is implemented, got {resample}")
+        self.size, self.crop_size = int(size), tuple(int(c) for c in crop_size)
+        self.image_mean, self.image_std, self.rescale_factor = tuple(image_mean), tuple(image_std), float(rescale_factor)
+        self.do_resize, self.do_center_crop, self.do_rescale = bool(do_resize), bool(do_center_crop), bool(do_rescale)
+        self.do_normalize, self.do_convert_rgb = bool(do_normalize), bool(do_convert_rgb)
+
+    @classmethod
+    def from_pretrained(cls, folder: str, **kw):
+        """`<folder>/preprocessor_config.json` (a local folder; nothing is downloaded)."""
+        import json
+        import os
+        f = os.path.join(str(folder), "preprocessor_config.json")
+        if not os.path.isfile(f):
+            raise FileNotFoundError(f"{f} not found")
+        with open(f) as fh:
+            cfg = json.load(fh)
+        cfg.update(kw)
+        return cls(**cfg)
+
+    def _one(self, image) -> np.ndarray:
+        import PIL.Image
+        if isinstance(image, np.ndarray):
+            if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] not in (1, 3, 4):
+                raise ValueError(f"CLIPImageProcessor: arrays must be HWC uint8, got {image.dtype} {image.shape}")
+            image = PIL.Image.fromarray(image[:, :, 0] if image.shape[2] == 1 else image)
+        if not isinstance(image, PIL.Image.Image):
+            raise ValueError(f"CLIPImageProcessor: unsupported image type {type(image)}")
+        if self.do_convert_rgb or image.mode != "RGB":
+            image = image.convert("RGB")
+        if self.do_resize:
+            w, h = image.size
+            short, long = (w, h) if w <= h else (h, w)
+            new_long = int(self.size * long / short)
+            image = image.resize((self.size, new_long) if w <= h else (new_long, self.size), resample=PIL.Image.BICUBIC)
+        x = np.asarray(image)                                               # HWC uint8
+        if self.do_center_crop:
+            ch, cw = self.crop_size
+            h, w = x.shape[:2]
+            if h < ch or w < cw:
+                raise ValueError(f"CLIPImageProcessor: a {h}x{w} image is smaller than the crop {ch}x{cw} (padding is not implemented)")
+            top, left = (h - ch) // 2, (w - cw) // 2
+            x = x[top:top + ch, left:left + cw]
+        x = x.transpose(2, 0, 1)
+        if self.do_rescale:
+            x = (x.astype(np.float64) * self.rescale_factor).astype(np.float32)
+        else:
+            x = x.astype(np.float32)
+        if self.do_normalize:
+            mean = np.array(self.image_mean, dtype=np.float32)[:, None, None]
+            std = np.array(self.image_std, dtype=np.float32)[:, None, None]
+            x = (x - mean) / std
+        return x
+
+    def __call__(self, images, return_tensors: Optional[str] = "pt", **unused):
+        from types import SimpleNamespace
+        if not isinstance(images, (list, tuple)):
+            images = [images]
+        if not images:
+            raise ValueError("CLIPImageProcessor: no image given")
+        arr = np.stack([self._one(i) for i in images], axis=0)
+        if return_tensors not in ("pt", "np", None):
+            raise ValueError(f"CLIPImageProcessor: return_tensors={return_tensors!r} (\"pt\" or \"np\")")
+        return SimpleNamespace(pixel_values=torch.from_numpy(arr) if return_tensors == "pt" else arr)
+
+
 class VaeImageProcessor:
     def __init__(self, do_resize: bool = True, vae_scale_factor: int = 8, resample: str = "lanczos",
                  do_normalize: bool = True, do_binarize: bool = False, do_convert_rgb: bool = False,

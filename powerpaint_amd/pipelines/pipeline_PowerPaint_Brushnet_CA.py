@@ -118,15 +118,32 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
         prefixes, a folder plus `weight_name` (and `subfolder`) -- or a list of those for several adapters (`subfolder` /
         `weight_name` then a value or one per adapter).  Base adapters only; Plus / FaceID files are refused by name
         (powerpaint_amd.ip_adapter.check_ip_adapter, which also states the index order of the cross-attentions).
-        No image encoder is loaded (`image_encoder_folder` must be None): register a duck-typed `image_encoder` and
-        `feature_extractor` on the pipeline, or pass `ip_adapter_image_embeds`."""
-        if image_encoder_folder is not None:
-            raise L.PPError("load_ip_adapter: image_encoder_folder is not supported (no image encoder is loaded here): pass "
-                            "image_encoder_folder=None and register pipe.image_encoder / pipe.feature_extractor yourself")
+        `image_encoder_folder` (default None: no image encoder is loaded) names the CLIP vision tower's folder as diffusers
+        resolves it -- a name without "/" lies under `subfolder` of the model path, anything else is relative to the model
+        path -- and needs a local-path source: the HIP `CLIPVisionModelWithProjection` is loaded from it into
+        `pipe.image_encoder` unless one is registered already, and a default `CLIPImageProcessor` becomes
+        `pipe.feature_extractor` unless one is.  With a state-dict source there is no path to resolve it against (diffusers
+        raises there too).  Without it, register a duck-typed `image_encoder` and `feature_extractor` yourself, or pass
+        `ip_adapter_image_embeds`."""
         if kwargs.get("ip_adapter_masks") is not None:
             raise L.PPError("load_ip_adapter: ip_adapter_masks are not implemented on the HIP path")
         srcs = pretrained_model_name_or_path_or_dict
         srcs = list(srcs) if isinstance(srcs, (list, tuple)) else [srcs]
+        if image_encoder_folder is not None:
+            import os
+            src = srcs[0]
+            if isinstance(src, dict) or not os.path.isdir(str(src)):
+                raise L.PPError("load_ip_adapter: image_encoder_folder needs a local model folder to be resolved against; a state "
+                                "dict or a file has none: pass image_encoder_folder=None and register pipe.image_encoder / "
+                                "pipe.feature_extractor yourself")
+            sub = subfolder[0] if isinstance(subfolder, (list, tuple)) else subfolder
+            folder = str(image_encoder_folder)
+            folder = os.path.join(str(src), sub or "", folder) if folder.count("/") == 0 else os.path.join(str(src), folder)
+            if not os.path.isdir(folder):
+                raise L.PPError(f"load_ip_adapter: image_encoder_folder {folder} does not exist (nothing is downloaded)")
+            encoder_folder = folder
+        else:
+            encoder_folder = None
 
         def per(v, what):
             v = list(v) if isinstance(v, (list, tuple)) else [v] * len(srcs)
@@ -137,21 +154,30 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
         sds = [IPA.read_ip_adapter(s_, sf, wn) for s_, sf, wn in zip(srcs, per(subfolder, "subfolder"),
                                                                      per(weight_name, "weight_name"))]
         self.unet._load_ip_adapter_weights(sds)
+        if encoder_folder is not None:
+            if self.image_encoder is None:
+                from ..models import CLIPVisionModelWithProjection
+                enc = CLIPVisionModelWithProjection.from_pretrained(encoder_folder, device=self.unet.device)
+                self.image_encoder = self._modules["image_encoder"] = enc
+            if self.feature_extractor is None:
+                from .image_processor import CLIPImageProcessor
+                self.feature_extractor = self._modules["feature_extractor"] = CLIPImageProcessor()
 
     def set_ip_adapter_scale(self, scale):
         self.unet.set_ip_adapter_scale(scale)
 
     def unload_ip_adapter(self):
-        """diffusers' `unload_ip_adapter`: the UNet of before `load_ip_adapter` (a registered image encoder stays: it was
-        never loaded here)."""
+        """diffusers' `unload_ip_adapter`: the UNet of before `load_ip_adapter` (the image encoder and feature
+        extractor stay registered, whether `load_ip_adapter` loaded them or the caller brought them)."""
         self.unet._unload_ip_adapter()
 
     def encode_image(self, image, device, num_images_per_prompt, output_hidden_states=None):
         """pipeline_PowerPaint_Brushnet_CA.py:632-654 through the registered (duck-typed) `image_encoder` /
         `feature_extractor`; the unconditional embeds of a base adapter are zeros."""
         if self.image_encoder is None:
-            raise ValueError("`ip_adapter_image` needs an `image_encoder` registered on the pipeline (none is: the HIP path has no "
-                             "CLIP vision tower of its own); register one, or pass `ip_adapter_image_embeds`")
+            raise ValueError("`ip_adapter_image` needs an `image_encoder` registered on the pipeline (none is): load one with "
+                             "load_ip_adapter(<folder>, image_encoder_folder=...), register a "
+                             "powerpaint_amd.models.CLIPVisionModelWithProjection, or pass `ip_adapter_image_embeds`")
         if output_hidden_states:
             raise L.PPError("encode_image(output_hidden_states=True) serves IP-Adapter Plus, which is not implemented")
         dtype = next(self.image_encoder.parameters()).dtype
