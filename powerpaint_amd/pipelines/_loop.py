@@ -1,29 +1,21 @@
 """The fused denoising loop: one launch program per step, replayed eagerly or as a hipGraph.
 
-Per step (reference: /root/reference/powerpaint/pipelines/pipeline_PowerPaint.py:988-1041,
-pipeline_PowerPaint_Brushnet_CA.py:1384-1466, pipeline_PowerPaint_ControlNet.py:1663-1741):
-    (round 5: the next two lines and the zeroing of the GroupNorm accumulators are ONE launch, pp_step_head)
-    temb_all     <- temb_table[step]                                  (one row copy, pp_embed_splice indexed by the device
-                                                                       step counter: the sinusoid -> time_embedding MLP ->
-                                                                       every resnet's time_emb_proj chain depends on t
-                                                                       alone, unet_2d_condition.py:1155-1156, so it is run
-                                                                       once per schedule row when the timesteps change,
-                                                                       not four launches per network and step)
-    x_in[:, 0:4] <- cat([latents] * 2)                                (pp_nchw_to_nhwc with batch wrap, no copy of the cat)
-    [BrushNet | ControlNet forward]                                   (own launch plan, residuals stay in HBM as NHWC)
-    eps          <- UNet(x_in, t, ctx, residuals)
-    latents      <- scheduler.step(eps_u + g (eps_c - eps_u), t, latents)   (pp_cfg_sched_step, fp32; an LCMScheduler:
-                                                                       pp_cfg_lcm_step, which adds the step's noise as well;
-                                                                       Euler / Euler ancestral: pp_cfg_sigma_step, and the
-                                                                       head launch is pp_step_head_scaled -- the networks see
-                                                                       latents / sqrt(sigma^2 + 1), `scale_model_input`;
-                                                                       Heun / DPM2 / DPM2 ancestral / LMS: the same head and
-                                                                       pp_cfg_ksampler_step, one "step" per table row, i.e.
-                                                                       per network evaluation)
-    [latents     <- (1 - m) add_noise(x0, noise, t_next) + m latents]       (pp_latent_blend; ppt-v1 with a 4-channel UNet)
-    step         <- step + 1                                          (pp_step_advance; round 5: by the last block of
-                                                                       pp_cfg_sched_step when nothing behind it reads the counter)
-No host->device traffic and no host synchronisation inside the loop.
+One step (reference: /root/reference/powerpaint/pipelines/pipeline_PowerPaint.py:988-1041,
+pipeline_PowerPaint_Brushnet_CA.py:1384-1466, pipeline_PowerPaint_ControlNet.py:1663-1741): per network one head launch
+(time-embedding row of the per-schedule table, x_in[:, 0:4] <- cat([latents] * 2) without a copy of the cat, GroupNorm
+accumulators zeroed) and the network's plan, side networks first, their residuals staying in HBM as NHWC; then the
+scheduler's step launch on the fp32 latents (CFG combine + step), by family (schedulers.py: `step_launch`, `noise_for`):
+
+    family                       head launch           step launch            state (`_keep[2]`)   noise `run` draws per row
+    DDIM                         pp_step_head          pp_cfg_sched_step      none                 eta > 0: every row
+    DPM-Solver++, PNDM, UniPC    pp_step_head          pp_cfg_sched_step      1, 5, 4 slots        none
+    LCM                          pp_step_head          pp_cfg_lcm_step        none                 every row but the last
+    Euler, Euler a               pp_step_head_scaled   pp_cfg_sigma_step      none                 Euler a: every row; Euler drops
+    Heun, DPM2, DPM2 a, LMS      pp_step_head_scaled   pp_cfg_ksampler_step   4 slots              DPM2 a: every row; else none
+(pp_step_head_scaled: the networks see latents / sqrt(sigma^2 + 1), `scale_model_input`; one row = one network evaluation.)
+Behind it pp_ddim_variance_noise (DDIM, eta > 0) and pp_latent_blend (ppt-v1 with a 4-channel UNet: the known region noised
+to the next timestep).  The step launch's last block moves the step counter on where nothing behind it reads the counter;
+else pp_step_advance does.  No host->device traffic and no host synchronisation inside the loop.
 
 Several ControlNets (`side` = a MultiControlNetModel, pipeline_PowerPaint_ControlNet.py:306,1678-1694): one runtime per
 net (own arena, time-embedding table, hoisted control-image embedding, twin-prefix decision); the step is
@@ -47,7 +39,7 @@ import torch
 
 from .. import _lib as L
 from ..engine import Plan
-from ..schedulers import _SchedulerBase, variance_noise
+from ..schedulers import _SchedulerBase
 
 
 def _temb_table_enabled() -> bool:
@@ -99,19 +91,11 @@ class DenoiseLoop:
         side network sees only the conditional half of a CFG pair (its inputs -- `prompt_embeds_side`, conditioning
         latents / control image -- arrive un-duplicated) with its residual scales log-spaced from 0.1 to 1; the
         unconditional half of the UNet batch gets zeros."""
-        dev = self.unet.device
-        B, Cl, h, w = latents_shape
-        Be = 2 * B if do_cfg else B
-        sch = self.scheduler
+        B, sch = latents_shape[0], self.scheduler
         if self.latents is None or tuple(self.latents.shape) != tuple(latents_shape):
-            self.latents = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
+            self.latents = torch.zeros(latents_shape, dtype=torch.float32, device=self.unet.device)
         lat = self.latents
-        prog = Plan()
-        lib = self.lib
-        cin = self.unet.config.in_channels
-        side_rt = None
-        wiring_kw = {}
-        self._eta = float(eta) if (not self.foreign and sch.kind == 0) else 0.0
+        self._eta = float(eta) if (not self.foreign and sch.takes_eta) else 0.0
         self._gen, self._noise_dtype = generator, noise_dtype
         self._extra_step_kwargs = {}
         if self.foreign:                                     # prepare_extra_step_kwargs for a duck-typed scheduler
@@ -120,32 +104,73 @@ class DenoiseLoop:
             self._extra_step_kwargs = {k: v for k, v in (("eta", eta), ("generator", generator)) if k in names}
         else:
             sch.set_eta(self._eta)
-        # does the bound scheduler's step consume noise the host draws per step?  (stochastic DDIM, LCM)
+        # does the bound scheduler's step consume noise the host draws per step?  (stochastic DDIM, LCM, the ancestral classes)
         self._noisy = (not self.foreign) and bool(sch.step_noise)
-        # a sigma-space scheduler (Euler, Euler ancestral; Heun, DPM2, DPM2 ancestral, LMS): the networks' input is scaled
-        # per row of the schedule, at the head of the step
-        sigma = (not self.foreign) and 5 <= sch.kind <= 10
-        ksampler = sigma and sch.kind >= 7                   # ... that keeps state between the evaluations
-        if ksampler and blend is not None and getattr(sch, "blend_refused", None):
+        if blend is not None and not self.foreign and sch.blend_refused:
             raise L.PPError(f"{type(sch).__name__}: the known-region blend of a 4-channel UNet is not implemented -- "
                             f"{sch.blend_refused}")
-        in_div = sch.in_div_table() if sigma else None
-        if sigma and not _temb_table_enabled():
+        # a sigma-space scheduler: the networks' input is scaled per row of the schedule, at the head of the step
+        in_div = sch.in_div_table() if (not self.foreign and sch.scales_input) else None
+        if in_div is not None and not _temb_table_enabled():
             raise L.PPError(f"{type(sch).__name__} needs the time-embedding table: without it (PP_TEMB_TABLE=0) the step has "
                             f"no head launch to scale the network input in")
-        self._blend = None
-        if blend is not None:
-            # loop-owned fp32 copies at stable addresses (a captured graph reads them); first image / first mask only
-            x0, mk, nz = blend
-            want = ((1, Cl, h, w), (1, 1, h, w), tuple(latents_shape))
-            bufs = getattr(self, "_blend_bufs", None)
-            if bufs is None or tuple(tuple(b.shape) for b in bufs) != want:
-                bufs = self._blend_bufs = tuple(torch.zeros(sh, dtype=torch.float32, device=dev) for sh in want)
-            for b_, v in zip(bufs, (x0[:1], mk[:1], nz)):
-                b_.copy_(v.to(device=dev, dtype=torch.float32).reshape(b_.shape))
-            self._blend = bufs
+        self._blend = self._blend_buffers(blend, latents_shape)
         half = bool(guess_mode and do_cfg)                   # side network on the conditional half only
-        # a MultiControlNetModel: its nets, one runtime each.  A wrapper around ONE net is that net (same plans, same launches)
+        Be = 2 * B if do_cfg else B
+        Bs = B if half else Be
+        nets, side, controlnet_cond, side_scale = self._resolve_side(controlnet_cond, side_scale, guess_mode)
+        multi = nets is not None and len(nets) > 1
+        rt, side_rt, side_rts = self._prepare_runtimes(
+            latents_shape, Be, Bs, do_cfg, half, guess_mode, nets, side, prompt_embeds, prompt_embeds_side, static_inputs,
+            side_static_inputs, controlnet_cond, side_scale, timestep_cond, added_cond_kwargs)
+        if self.foreign:
+            ts, step, src, mp = self._foreign_state(latents_shape, do_cfg, guidance_scale)
+        else:
+            # scheduler state: DPM m_{i-1}; PNDM history + saved sample; UniPC; Heun / DPM2 / DPM2 ancestral / LMS: three
+            # derivative slots + the saved sample (DDIM, LCM and the Euler classes keep none)
+            ts, step, src, mp = sch.timesteps_f32(), sch.step_counter(), lat, sch.m_prev(lat) if sch.state_slots > 0 else None
+        key = (tuple(latents_shape), bool(do_cfg), bool(guess_mode), self._noisy, float(guidance_scale), id(rt.step_plan),
+               tuple(id(r.step_plan) for r in side_rts) if side_rts else None, type(sch), ts.data_ptr(), step.data_ptr(),
+               0 if self.foreign else sch.coef_table().data_ptr(), mp.data_ptr() if mp is not None else 0, src.data_ptr(),
+               _temb_table_enabled(), int(ts.numel()), tuple(getattr(r.net.params, "version", 0) for r in [rt] + side_rts),
+               tuple(b.data_ptr() for b in self._blend) if self._blend is not None else None,
+               sch.renoise_table().data_ptr() if (self._blend is not None and not self.foreign) else 0,
+               in_div.data_ptr() if in_div is not None else 0)
+        if key == self._key and self.program is not None:
+            # The conditioning scale is a by-value argument of the zero-conv launches: `prepare` has patched the launch
+            # records (eager runs see it), but a graph captured with another value still carries the old one.
+            if self.graph is not None and (self._scale_now() != self._graph_scale or
+                                           rt.ip_scales() != getattr(self, "_graph_ip", ())):
+                self.graph = None
+            return self
+        self._key = key
+        heads, skips = self._head_launches(side_rts, rt, ts, step, src, Be, Bs, do_cfg, in_div)
+        tail = self._tail_launches(rt, lat, mp, step, do_cfg, guidance_scale)
+        self.rt, self.side_rt, self.side_rts = rt, side_rt, side_rts
+        self.graph = None
+        self._assemble(multi, heads, skips, tail)
+        self._keep = (ts, step, mp, lat)
+        return self
+
+    # ---- the parts of `bind`, in its order
+    def _blend_buffers(self, blend, latents_shape):
+        """Loop-owned fp32 copies of `blend` at stable addresses (a captured graph reads them); first image / mask only."""
+        if blend is None:
+            return None
+        _, Cl, h, w = latents_shape
+        dev = self.unet.device
+        x0, mk, nz = blend
+        want = ((1, Cl, h, w), (1, 1, h, w), tuple(latents_shape))
+        bufs = getattr(self, "_blend_bufs", None)
+        if bufs is None or tuple(tuple(b.shape) for b in bufs) != want:
+            bufs = self._blend_bufs = tuple(torch.zeros(sh, dtype=torch.float32, device=dev) for sh in want)
+        for b_, v in zip(bufs, (x0[:1], mk[:1], nz)):
+            b_.copy_(v.to(device=dev, dtype=torch.float32).reshape(b_.shape))
+        return bufs
+
+    def _resolve_side(self, controlnet_cond, side_scale, guess_mode):
+        """-> (a MultiControlNetModel's nets or None, the network to `prepare`, control images and scales per net); sets the
+        guess-mode ramp.  Several nets get one runtime each; a wrapper around ONE net is that net (same plans, same launches)."""
         nets = list(self.side.nets) if (self.side is not None and hasattr(self.side, "nets")) else None
         multi = nets is not None and len(nets) > 1
         side = self.side if (nets is None or multi) else nets[0]
@@ -164,12 +189,19 @@ class DenoiseLoop:
         self._guess_ramp = None
         if guess_mode and side is not None and not side0.config.global_pool_conditions:
             self._guess_ramp = [float(v) for v in torch.logspace(-1, 0, len(side0.net._zero_conv_specs()))]
-        Bs = B if half else Be
+        return nets, side, controlnet_cond, side_scale
 
-        # The CFG pair is built here, as `cat([latents] * 2)` (pipeline_PowerPaint.py:990): where every other network input
-        # is CFG-duplicated as well, the two halves of a forward pass are identical until the prompt enters and the
-        # networks run that prefix once (`twin`, SDNet.build_step).  A static input counts as duplicated when it arrives
-        # with the un-duplicated batch (load_input copies it to both halves) or when its halves compare equal.
+    def _prepare_runtimes(self, latents_shape, Be, Bs, do_cfg, half, guess_mode, nets, side, prompt_embeds,
+                          prompt_embeds_side, static_inputs, side_static_inputs, controlnet_cond, side_scale, timestep_cond,
+                          added_cond_kwargs):
+        """-> (rt, side_rt, side_rts): every network prepared, the UNet wired to the side residuals, static channels loaded.
+        The CFG pair is built here, as `cat([latents] * 2)` (pipeline_PowerPaint.py:990): where every other network input
+        is CFG-duplicated as well, the two halves of a forward pass are identical until the prompt enters and the
+        networks run that prefix once (`twin`, SDNet.build_step).  A static input counts as duplicated when it arrives
+        with the un-duplicated batch (load_input copies it to both halves) or when its halves compare equal."""
+        B, Cl, h, w = latents_shape
+        multi = nets is not None and len(nets) > 1
+
         def halves_equal(t):
             if t is None or not torch.is_tensor(t):
                 return False
@@ -186,13 +218,12 @@ class DenoiseLoop:
             # must store activations in the same 16-bit format (the reference raises a dtype error in its first conv)
             raise L.PPError(f"{type(self.side).__name__} computes in {self.side.dtype}, the UNet in {self.unet.dtype}: "
                             f"load both with the same torch_dtype")
-        side_rts = []
+        side_rt, side_rts, wiring_kw = None, [], {}
         if side is not None:
             if half and prompt_embeds_side.shape[0] == Be:
                 prompt_embeds_side = prompt_embeds_side.chunk(2)[1]
             if self.side_kind == "brushnet":
-                side_rt = side.prepare((Bs, Cl, h, w), prompt_embeds_side, side_scale, bool(guess_mode), half,
-                                       twin=twin_s)
+                side_rt = side.prepare((Bs, Cl, h, w), prompt_embeds_side, side_scale, bool(guess_mode), half, twin=twin_s)
                 d, m, u = side.outputs()
                 wiring_kw = dict(down_block_add_samples=d, mid_block_add_sample=m, up_block_add_samples=u)
             elif multi:
@@ -214,141 +245,116 @@ class DenoiseLoop:
             wiring_kw["timestep_cond"] = timestep_cond
         if added_cond_kwargs is not None:
             wiring_kw["added_cond_kwargs"] = added_cond_kwargs
-        rt = self.unet.prepare((Be, cin, h, w), prompt_embeds, twin=twin_u, **wiring_kw)
+        rt = self.unet.prepare((Be, self.unet.config.in_channels, h, w), prompt_embeds, twin=twin_u, **wiring_kw)
         # one-time (per call) static channels of the UNet / side inputs
         rt.load_input(list(static_inputs))
         if side_rt is not None and side_static_inputs:
             side_rt.load_input(list(side_static_inputs))
+        return rt, side_rt, side_rts
 
-        if self.foreign:
-            # network input (scaled by the scheduler per step), timestep table and step counter owned by the loop
-            tsv = torch.as_tensor(sch.timesteps).detach().to(dev, torch.float32).contiguous()
-            if getattr(self, "_f_ts", None) is None or self._f_ts.shape != tsv.shape:
-                self._f_ts = tsv
-                self._f_step = torch.zeros(1, dtype=torch.int32, device=dev)
-                self._f_x = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
-            else:
-                self._f_ts.copy_(tsv)
-            if tuple(self._f_x.shape) != tuple(latents_shape):
-                self._f_x = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
-            ts, step, mp, kind, src = self._f_ts, self._f_step, None, -1, self._f_x
-            self._do_cfg, self._g = bool(do_cfg), float(guidance_scale)
+    def _foreign_state(self, latents_shape, do_cfg, guidance_scale):
+        """-> (ts, step, src, no state) of a duck-typed scheduler: the timestep table, the step counter and the network
+        input (scaled by the scheduler per step), all owned by the loop."""
+        dev = self.unet.device
+        tsv = torch.as_tensor(self.scheduler.timesteps).detach().to(dev, torch.float32).contiguous()
+        if getattr(self, "_f_ts", None) is None or self._f_ts.shape != tsv.shape:
+            self._f_ts = tsv
+            self._f_step = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._f_x = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
         else:
-            ts, step = sch.timesteps_f32(), sch.step_counter()
-            # scheduler state: DPM m_{i-1}; PNDM history + saved sample; UniPC; Heun / DPM2 / DPM2 ancestral / LMS: three
-            # derivative slots + the saved sample (DDIM, LCM and the Euler classes keep none)
-            mp = sch.m_prev(lat) if (1 <= sch.kind <= 3 or ksampler) else None
-            kind, src = sch.kind, lat
-        key = (tuple(latents_shape), bool(do_cfg), bool(guess_mode), self._noisy, float(guidance_scale), id(rt.step_plan),
-               tuple(id(r.step_plan) for r in side_rts) if side_rts else None, kind, ts.data_ptr(), step.data_ptr(),
-               0 if self.foreign else sch.coef_table().data_ptr(), mp.data_ptr() if mp is not None else 0, src.data_ptr(),
-               _temb_table_enabled(), int(ts.numel()), tuple(getattr(r.net.params, "version", 0) for r in [rt] + side_rts),
-               tuple(b.data_ptr() for b in self._blend) if self._blend is not None else None,
-               sch.renoise_table().data_ptr() if (self._blend is not None and not self.foreign) else 0,
-               in_div.data_ptr() if sigma else 0)
-        if key == self._key and self.program is not None:
-            # The conditioning scale is a by-value argument of the zero-conv launches: `prepare` has patched the launch
-            # records (eager runs see it), but a graph captured with another value still carries the old one.
-            if self.graph is not None and (self._scale_now() != self._graph_scale or
-                                           rt.ip_scales() != getattr(self, "_graph_ip", ())):
-                self.graph = None
-            return self
-        self._key = key
+            self._f_ts.copy_(tsv)
+        if tuple(self._f_x.shape) != tuple(latents_shape):
+            self._f_x = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
+        self._do_cfg, self._g = bool(do_cfg), float(guidance_scale)
+        return self._f_ts, self._f_step, self._f_x, None
+
+    def _head_launches(self, side_rts, rt, ts, step, src, Be, Bs, do_cfg, in_div):
+        """-> (heads, skips), per runtime: the launches at the head of the step; the plan indices they replace.
+        in_div: the table a sigma-space scheduler scales the networks' input by, else None."""
+        lib, sch = self.lib, self.scheduler
+        B, Cl, h, w = src.shape
         hw = h * w
         mod = B if do_cfg else 0
         self._temb = {}
-        head_skip = {}
-        heads, skips = {}, {}           # per runtime: the launches at the head of the step; the plan indices they replace
-        tail = prog                     # (the launches behind the networks are collected in `prog`, the networks come in front)
+        heads, skips = {}, {}
         for r in side_rts + [rt]:
             prog = Plan()
             heads[id(r)] = prog.calls
+            skips[id(r)] = set()
             info = self._temb_split(r, ts) if _temb_table_enabled() else None
             x = r.lay["x_in"]
             nb_r = Be if r is rt else Bs                    # (guess mode: the side network takes `latents` as is)
             calls = r.step_plan.calls
             zero = calls[0] if (calls and calls[0][2] == "zero_u64") else None
+            if info is not None:
+                self._temb[id(r)] = info
+                skips[id(r)] |= set(info["idx"])
             if info is not None and zero is not None:
                 # time-embedding row + network input + accumulator zeroing: ONE launch at the head of the step (pp_step_head)
-                self._temb[id(r)] = info
-                head_skip[id(r)] = {0}
+                skips[id(r)].add(0)
                 head = (info["table"].data_ptr(), step.data_ptr(), info["out"], info["total"], src.data_ptr(), nb_r, Cl, hw,
                         mod if nb_r != B else 0, x.ptr, x.C, 0, L.dtype_code(r.net.dtype), zero[1][0], zero[1][1])
-                if sigma:
-                    prog.add("step_head", lib.pp_step_head_scaled, *head, in_div.data_ptr())
-                else:
-                    prog.add("step_head", lib.pp_step_head, *head)
+                fn, div = (lib.pp_step_head, ()) if in_div is None else (lib.pp_step_head_scaled, (in_div.data_ptr(),))
+                prog.add("step_head", fn, *head, *div)
                 continue
-            if sigma:
+            if in_div is not None:
                 raise L.PPError(f"{type(r.net).__name__}: its step plan has no fused head launch, which "
                                 f"{type(sch).__name__} needs to scale the network input")
             if info is not None:
-                self._temb[id(r)] = info
                 prog.add("temb_row", lib.pp_embed_splice, info["table"].data_ptr(), None, step.data_ptr(), info["out"], 1,
                          info["total"] * 4)
             else:
                 prog.add("step_select_t", lib.pp_step_select_t, ts.data_ptr(), step.data_ptr(), r.lay["t_dev"])
             prog.add("nchw_to_nhwc", lib.pp_nchw_to_nhwc, src.data_ptr(), 0, nb_r, Cl, hw, mod if nb_r != B else 0,
                      x.ptr, x.C, 0, L.dtype_code(r.net.dtype))
-        prog = tail
-        for r in side_rts + [rt]:
-            skip = set(self._temb[id(r)]["idx"]) if id(r) in self._temb else set()
-            skips[id(r)] = skip | head_skip.get(id(r), set())
-        # (round 5) where pp_cfg_sched_step is the step's last reader of the counter, its last block moves the counter on:
-        # no pp_step_advance launch behind it
+        return heads, skips
+
+    def _tail_launches(self, rt, lat, mp, step, do_cfg, guidance_scale):
+        """-> the launches behind the networks: the scheduler's step launch (`step_launch` of its family), DDIM's variance
+        noise, the known-region blend, and the counter's advance where the step launch does not do it itself."""
+        prog = Plan()
+        lib, sch = self.lib, self.scheduler
+        # the step launch's last block moves the counter on (the ticket) where nothing behind it reads it: no pp_step_advance
         fold_advance = (not self.foreign) and not (self._eta > 0) and self._blend is None and \
             not (os.environ.get("PP_LAB") == "1" and os.environ.get("PP_FOLD_ADVANCE", "1") == "0")     # (lab: the two launches)
         if not self.foreign:
             if fold_advance and (getattr(self, "_ticket", None) is None or self._ticket.device != lat.device):
                 self._ticket = torch.zeros(1, dtype=torch.int32, device=lat.device)
-            if self._noisy and (getattr(self, "_var_noise", None) is None or
-                                tuple(self._var_noise.shape) != tuple(latents_shape)):
-                self._var_noise = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
-            ticket = self._ticket.data_ptr() if fold_advance else None
-            if ksampler:         # one table row of Heun / DPM2 / DPM2 ancestral / LMS (noise: as for Euler below)
-                noise = self._var_noise if self._noisy else lat
-                prog.add("cfg_ksampler_step", lib.pp_cfg_ksampler_step, rt.outputs["eps"], int(do_cfg),
-                         float(guidance_scale), lat.data_ptr(), mp.data_ptr(), noise.data_ptr(), lat.numel(),
-                         sch.coef_table().data_ptr(), step.data_ptr(), ticket)
-            elif sigma:          # Euler (s_up = 0 in every row: the noise pointer is never read) / Euler ancestral
-                noise = self._var_noise if self._noisy else lat
-                prog.add("cfg_sigma_step", lib.pp_cfg_sigma_step, rt.outputs["eps"], int(do_cfg), float(guidance_scale),
-                         lat.data_ptr(), noise.data_ptr(), lat.numel(), sch.coef_table().data_ptr(), step.data_ptr(), ticket)
-            elif sch.kind == 4:  # LCM: guidance combine, consistency transition, noise term and counter advance in one launch
-                prog.add("cfg_lcm_step", lib.pp_cfg_lcm_step, rt.outputs["eps"], int(do_cfg), float(guidance_scale),
-                         lat.data_ptr(), self._var_noise.data_ptr(), lat.numel(), sch.coef_table().data_ptr(),
-                         step.data_ptr(), ticket)
-            else:
-                prog.add("cfg_sched_step", lib.pp_cfg_sched_step, rt.outputs["eps"], int(do_cfg), float(guidance_scale),
-                         lat.data_ptr(), mp.data_ptr() if mp is not None else None, lat.numel(), sch.kind,
-                         sch.coef_table().data_ptr(), step.data_ptr(), ticket)
+            if self._noisy and (getattr(self, "_var_noise", None) is None or self._var_noise.shape != lat.shape):
+                self._var_noise = torch.zeros_like(lat)
+            noise = self._var_noise if self._noisy else lat      # (a step that reads no noise: any valid address)
+            prog.add(*sch.step_launch(rt.outputs["eps"], int(do_cfg), float(guidance_scale), lat.data_ptr(),
+                                      mp.data_ptr() if mp is not None else None, noise.data_ptr(), lat.numel(),
+                                      step.data_ptr(), self._ticket.data_ptr() if fold_advance else None))
             if self._eta > 0:
-                prog.add("ddim_variance_noise", lib.pp_ddim_variance_noise, lat.data_ptr(), self._var_noise.data_ptr(),
-                         lat.numel(), sch.coef_table().data_ptr(), step.data_ptr())
+                prog.add(*sch.variance_launch(lat.data_ptr(), noise.data_ptr(), lat.numel(), step.data_ptr()))
             if self._blend is not None:
                 x0, mk, nz = self._blend
+                B, Cl, h, w = lat.shape
                 prog.add("latent_blend", lib.pp_latent_blend, lat.data_ptr(), x0.data_ptr(), mk.data_ptr(), nz.data_ptr(),
-                         sch.renoise_table().data_ptr(), step.data_ptr(), B, Cl, hw)
+                         sch.renoise_table().data_ptr(), step.data_ptr(), B, Cl, h * w)
         if not fold_advance:
             prog.add("step_advance", lib.pp_step_advance, step.data_ptr())
-        self.rt, self.side_rt, self.side_rts = rt, side_rt, side_rts
-        self.graph = None
+        return prog
+
+    def _assemble(self, multi, heads, skips, tail):
+        """`self.program`: every head, every network's plan without the launches its head replaces, the tail.  Several
+        ControlNets: the parts are kept, and one program per set of active nets is assembled on demand (`_set_entry`)."""
+        rts = self.side_rts + [self.rt]
         self._multi, self._sets = multi, {}
         if multi:
-            self._parts = dict(heads=heads, skips=skips, tail=prog.calls)
-            self._guess_ramps = [self._guess_ramp] * len(side_rts)      # (same zero convs in every net: one ramp, per net)
-            self.program = self._set_entry(tuple(range(len(side_rts))))["program"]     # (every net active: flop counts, tools)
-        else:
-            full = Plan()
-            for r in side_rts + [rt]:
-                full.calls += heads[id(r)]
-            for r in side_rts + [rt]:
-                full.calls += [c for i, c in enumerate(r.step_plan.calls) if i not in skips[id(r)]]
-                full.flops += r.step_plan.flops_executed      # (a program's `flops`: what its launches execute)
-            full.calls += prog.calls
-            self.program = full
-        self._keep = (ts, step, mp, lat)
-        return self
+            self._parts = dict(heads=heads, skips=skips, tail=tail.calls)
+            self._guess_ramps = [self._guess_ramp] * len(self.side_rts)      # (same zero convs in every net: one ramp, per net)
+            self.program = self._set_entry(tuple(range(len(self.side_rts))))["program"]    # (every net active: flops, tools)
+            return
+        full = Plan()
+        for r in rts:
+            full.calls += heads[id(r)]
+        for r in rts:
+            full.calls += [c for i, c in enumerate(r.step_plan.calls) if i not in skips[id(r)]]
+            full.flops += r.step_plan.flops_executed      # (a program's `flops`: what its launches execute)
+        full.calls += tail.calls
+        self.program = full
 
     # ---- time-embedding table
     def _temb_split(self, r, ts):
@@ -503,6 +509,20 @@ class DenoiseLoop:
         torch.cuda.synchronize()
         return g
 
+    def _schedule(self, scale_schedule, num_steps):
+        """The prologue `run` and `_run_foreign` share -> (ents, scale_schedule, varying).  Several ControlNets: per step
+        the set's entry with this call's scales written, no scalar schedule.  Else the schedule as one scale per step (a
+        wrapper around one net hands rows of one scale) and whether it varies inside the call."""
+        ents = None
+        if self._multi:
+            ents = self._multi_schedule(scale_schedule, num_steps)
+            for ent, row in ents:
+                self._set_scales(ent, row)
+            scale_schedule = None
+        elif scale_schedule is not None:
+            scale_schedule = [s[0] if isinstance(s, (list, tuple)) else s for s in scale_schedule]
+        return ents, scale_schedule, scale_schedule is not None and len(set(scale_schedule)) > 1
+
     def run(self, latents: torch.Tensor, num_steps: int, use_graph: bool = True,
             callback: Optional[Callable] = None, timesteps=None, scale_schedule: Optional[List[float]] = None):
         """Runs `num_steps` steps starting from step counter 0.  Returns the fp32 latents tensor (owned by the loop)."""
@@ -515,17 +535,11 @@ class DenoiseLoop:
             self._keep[2].zero_()
         self._fill_temb_tables()
         self.latents.copy_(latents.to(self.latents.device, torch.float32))
-        ents = None
-        if self._multi:
-            ents = self._multi_schedule(scale_schedule, num_steps)
-            for ent, row in ents:
-                self._set_scales(ent, row)
-                if use_graph and ent["graph"] is None:
+        ents, scale_schedule, varying = self._schedule(scale_schedule, num_steps)
+        if ents is not None and use_graph:        # (every set's graph before the first step)
+            for ent, _ in ents:
+                if ent["graph"] is None:
                     ent["graph"] = self._capture_program(ent["program"])
-            scale_schedule = None
-        elif scale_schedule is not None:          # (a wrapper around one net hands rows of one scale)
-            scale_schedule = [s[0] if isinstance(s, (list, tuple)) else s for s in scale_schedule]
-        varying = scale_schedule is not None and len(set(scale_schedule)) > 1
         if not varying and scale_schedule and self.side_rt is not None and \
                 self._scale_now() != self._side_scale(scale_schedule[0]):
             self.side_rt._patch_scale(self._side_scale(scale_schedule[0]))   # (a previous call may have left a windowed value)
@@ -536,12 +550,11 @@ class DenoiseLoop:
         for i in range(num_steps):
             if varying and self.side_rt is not None:
                 self.side_rt._patch_scale(self._side_scale(scale_schedule[i]))
-            # this step's noise (stream-ordered before the step that consumes it); LCM: none on the schedule's last step
-            if self._noisy and self.scheduler.draws_noise_at(self.scheduler.begin_index + i):
-                self._var_noise.copy_(variance_noise(self._var_noise.shape, self._gen, self._var_noise.device,
-                                                     self._noise_dtype))
-            elif self.scheduler.discards_draw:      # (plain Euler: the library draws and does not use it)
-                self.scheduler.discard_draw(self.latents.shape, self._gen, self._noise_dtype)
+            # this row's noise, by the scheduler's own rule (stream-ordered before the step that consumes it)
+            z = self.scheduler.noise_for(self.scheduler.begin_index + i, self.latents.shape, self._gen, self.latents.device,
+                                         self._noise_dtype)
+            if z is not None:
+                self._var_noise.copy_(z)
             if ents is not None:
                 if use_graph:
                     ents[i][0]["graph"].replay()
@@ -587,15 +600,7 @@ class DenoiseLoop:
         self._fill_temb_tables()
         self._f_step.zero_()
         lat = latents.to(self.latents.device, torch.float32).clone()
-        ents = None
-        if self._multi:
-            ents = self._multi_schedule(scale_schedule, num_steps)
-            for ent, row in ents:
-                self._set_scales(ent, row)
-            scale_schedule = None
-        elif scale_schedule is not None:
-            scale_schedule = [s[0] if isinstance(s, (list, tuple)) else s for s in scale_schedule]
-        varying = scale_schedule is not None and len(set(scale_schedule)) > 1
+        ents, scale_schedule, varying = self._schedule(scale_schedule, num_steps)
         stream = torch.cuda.current_stream().cuda_stream
         for i in range(num_steps):
             t = tl[i]

@@ -3,16 +3,22 @@
  pipeline_PowerPaint_Brushnet_CA.py:87-128,1391,1449,969): `.set_timesteps`, `.timesteps`, `.order`,
 `.init_noise_sigma`, `.scale_model_input`, `.step(..., return_dict=False)[0]`, `.add_noise`, `.config.steps_offset`.
 
-The arithmetic restates diffusers==0.27.0 `DDIMScheduler` / `DPMSolverMultistepScheduler` (pinned at
+The arithmetic restates the diffusers==0.27.0 classes of the same names (pinned at
 /root/reference/requirements/requirements.txt:3, not vendored).  Per-step coefficients are computed on the host in
-fp32 torch exactly in the library's operation order and uploaded as a device table `coef[step][8]`; the tensor math
-(CFG combine + step) runs in the fused HIP kernel `pp_cfg_sched_step` on fp32 latents.  `.step()` itself launches
-that kernel, so a foreign loop calling `scheduler.step` still runs on the HIP path.
+fp32 torch exactly in the library's operation order and uploaded as a device table `coef[row][8 or 16]`; the tensor math
+(CFG combine + step) runs in one fused HIP kernel per family, on fp32 latents:
 
-`EulerDiscreteScheduler` / `EulerAncestralDiscreteScheduler` (and `use_karras_sigmas`) are the sigma-space family: latents
-x0 + sigma eps, `init_noise_sigma` > 1, a real `scale_model_input`, float timesteps; their step is `pp_cfg_sigma_step`.
-`HeunDiscreteScheduler`, `KDPM2DiscreteScheduler`, `KDPM2AncestralDiscreteScheduler` and `LMSDiscreteScheduler` are the
-members of that family that keep state between network evaluations; their step is `pp_cfg_ksampler_step`.
+    family (base class)          classes                                 step kernel             state_slots   scales_input
+    _SchedulerBase               DDIM, DPM-Solver++ 2M, PNDM, UniPC      pp_cfg_sched_step       0, 1, 5, 4    no
+    LCMScheduler                 LCM                                     pp_cfg_lcm_step         0             no
+    _SigmaScheduler              Euler, Euler a                          pp_cfg_sigma_step       0             yes
+    _KSampler                    Heun, DPM2, DPM2 a, LMS                 pp_cfg_ksampler_step    4             yes
+
+Each family spells its kernel's argument list out once, in `step_launch`; `_SchedulerBase.step` and the fused loop
+(pipelines/_loop.py) both launch what it returns, and both take the step's noise from `noise_for`.  So a foreign loop calling
+`scheduler.step` runs the same kernel on the same row as the fused loop.  `kind` is the `kind` argument of
+`pp_cfg_sched_step` (0..3); on the other classes it is a tag no kernel takes.  The sigma-space families (and
+`use_karras_sigmas`) have latents x0 + sigma eps, `init_noise_sigma` > 1, a real `scale_model_input` and float timesteps.
 """
 from types import SimpleNamespace
 
@@ -83,9 +89,14 @@ def sigma_to_t(sigma, log_sigmas):
 class _SchedulerBase:
     order = 1
     init_noise_sigma = 1.0
-    kind = -1
+    kind = -1                # the `kind` argument of pp_cfg_sched_step (0..3); elsewhere a tag no kernel takes
     _ALLOWED = ()            # options of `_ONLY` this class implements at every value
-    discards_draw = False    # the library's step draws noise it does not use (plain Euler): `_SigmaScheduler.discard_draw`
+    state_slots = 0          # fp32 copies of the latents the step kernel keeps between steps (DPM: 1, PNDM: 5): `m_prev`
+    scales_input = False     # the networks' input is scaled per table row, at the head of the step (`in_div_table`)
+    takes_eta = False        # this class's step takes `eta` (DDIM)
+    discards_draw = False    # the library's step draws noise it does not use (plain Euler): `discard_draw`
+    blend_refused = None     # why the known-region blend of a 4-channel UNet is not implemented for this class, if it is not
+    _step_fields = {}        # what `step(return_dict=True)` returns next to `prev_sample`
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, **cfg):
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start,
@@ -185,9 +196,8 @@ class _SchedulerBase:
         a = self.alphas_cumprod[ts[1:]].to(torch.float32)
         return torch.stack([torch.cat([a ** 0.5, torch.ones(1)]), torch.cat([(1 - a) ** 0.5, torch.zeros(1)])], 1)
 
-    state_slots = 1          # fp32 copies of the latents the step kernel keeps between steps (DPM: 1, PNDM: 5)
-
     def m_prev(self, like: torch.Tensor) -> torch.Tensor:
+        """The step kernel's state (`state_slots` > 0): one slot has the latents' shape, several are stacked in front."""
         shape = (self.state_slots,) + tuple(like.shape) if self.state_slots > 1 else tuple(like.shape)
         if self._m_prev is None or tuple(self._m_prev.shape) != shape or self._m_prev.device != like.device:
             self._m_prev = torch.zeros(shape, dtype=torch.float32, device=like.device)
@@ -229,30 +239,57 @@ class _SchedulerBase:
         """Does the step at table row `row` draw noise?  (LCM: every row but the last of the full schedule.)"""
         return self.step_noise
 
+    def noise_for(self, row: int, shape, generator, device, dtype):
+        """THE noise rule, of `step` and of the fused loop alike: the Gaussian noise the step at table row `row` consumes,
+        drawn like diffusers' `randn_tensor(shape, generator=generator, ...)` -- or None where it consumes none, after
+        advancing `generator` by the draw the library makes and does not use (`discards_draw`).  The caller's generator
+        ends where the library leaves it."""
+        if self.step_noise and self.draws_noise_at(row):
+            return variance_noise(shape, generator, device, dtype)
+        if self.discards_draw:
+            self.discard_draw(shape, generator, dtype)
+        return None
+
+    @staticmethod
+    def discard_draw(shape, generator, dtype):
+        """Advance `generator` by one `randn_tensor(shape)` without keeping or uploading the numbers.  (No generator: the
+        library would use the global RNG, which nothing here has to stay in step with.)"""
+        gens = generator if isinstance(generator, (list, tuple)) else [generator]
+        sh = tuple(shape) if len(gens) == 1 else (1,) + tuple(shape[1:])
+        for g in gens:
+            if isinstance(g, torch.Generator):
+                torch.randn(sh, generator=g, device=g.device, dtype=dtype)
+
+    def step_launch(self, eps, cfg, guidance, lat, state, noise, n, step, ticket):
+        """This family's step launch as `Plan.add` takes it, `(name, fn, *args)`: the one place that spells the entry point's
+        argument list out.  Raw pointers and integers: eps (the CFG pair when `cfg`), the fp32 latents updated in place, the
+        state (`m_prev`) or None, the noise (a row that adds none never reads it: any valid address), `n` elements, the device
+        step counter indexing the scheduler's own table, the ticket through which the last block moves it on, or None."""
+        return ("cfg_sched_step", L.lib().pp_cfg_sched_step, eps, cfg, guidance, lat, state, n, self.kind,
+                self._coef_dev.data_ptr(), step, ticket)
+
     def step(self, model_output, timestep, sample, eta: float = 0.0, generator=None, return_dict: bool = True, **kw):
-        """x_t -> x_{t-1} on the HIP kernel (fp32 math).  Returns a NEW tensor in sample's dtype.  `eta` / `generator`:
-        stochastic DDIM (kind 0 only), the variance noise drawn like diffusers' `randn_tensor(model_output.shape, ...)`."""
+        """One table row, x_t -> x_{t-1}, in the family's HIP kernel (fp32 math).  Returns a NEW tensor in sample's dtype;
+        the state between the calls (`state_slots`) lives in the scheduler, zeroed by `set_timesteps` / `set_begin_index`.
+        `generator`: the step's noise (`noise_for`).  `eta`: stochastic DDIM only (`takes_eta`)."""
         if not sample.is_cuda:
             raise L.PPError("scheduler.step needs CUDA tensors: the step runs in the HIP kernel, no CPU fallback")
-        if self.kind == 0 and float(eta) != self.eta:
+        if self.takes_eta and float(eta) != self.eta:
             self.set_eta(eta)
         i = self._index_of(timestep)
         x = sample.detach().to(torch.float32).contiguous().clone()
         e = model_output.detach().to(torch.float32).contiguous()
         step = torch.full((1,), i, dtype=torch.int32, device=x.device)
-        mp = self.m_prev(x) if self.kind >= 1 else None
-        L.check(L.lib().pp_cfg_sched_step(e.data_ptr(), 0, 0.0, x.data_ptr(), mp.data_ptr() if mp is not None else None,
-                                           x.numel(), self.kind, self._coef_dev.data_ptr(), step.data_ptr(), None,
-                                           torch.cuda.current_stream().cuda_stream), "pp_cfg_sched_step")
-        if self.kind == 0 and self.eta > 0:
-            z = variance_noise(model_output.shape, generator, x.device, model_output.dtype)
-            L.check(L.lib().pp_ddim_variance_noise(x.data_ptr(), z.data_ptr(), x.numel(), self._coef_dev.data_ptr(),
-                                                    step.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                    "pp_ddim_variance_noise")
+        z = self.noise_for(i, model_output.shape, generator, x.device, model_output.dtype)
+        noise = (x if z is None else z).data_ptr()
+        launches = [self.step_launch(e.data_ptr(), 0, 0.0, x.data_ptr(), self.m_prev(x).data_ptr() if self.state_slots else None,
+                                     noise, x.numel(), step.data_ptr(), None)]
+        if self.takes_eta and self.eta > 0:
+            launches.append(self.variance_launch(x.data_ptr(), noise, x.numel(), step.data_ptr()))
+        for name, fn, *args in launches:
+            L.check(fn(*args, torch.cuda.current_stream().cuda_stream), "pp_" + name)
         out = x.to(sample.dtype)
-        if not return_dict:
-            return (out,)
-        return SimpleNamespace(prev_sample=out)
+        return SimpleNamespace(prev_sample=out, **self._step_fields) if return_dict else (out,)
 
     def add_noise(self, original_samples, noise, timesteps):
         a = self.alphas_cumprod.to(original_samples.device)[timesteps.to(original_samples.device).long()]
@@ -266,6 +303,7 @@ class _SchedulerBase:
 class DDIMScheduler(_SchedulerBase):
     """epsilon prediction, `leading` spacing, steps_offset = 1, set_alpha_to_one = False, no clipping; eta in [0, 1]."""
     kind = 0
+    takes_eta = True
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
                  set_alpha_to_one=False, timestep_spacing="leading", **kw):
@@ -296,6 +334,10 @@ class DDIMScheduler(_SchedulerBase):
     @property
     def step_noise(self) -> bool:
         return self.eta > 0
+
+    def variance_launch(self, lat, noise, n, step):
+        """eta > 0: `latents += std_dev_t * z`, the launch behind the step launch (same form as `step_launch`)."""
+        return ("ddim_variance_noise", L.lib().pp_ddim_variance_noise, lat, noise, n, self._coef_dev.data_ptr(), step)
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         T = self.config.num_train_timesteps
@@ -347,6 +389,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
     training table and the timesteps are their rounded `sigma_to_t` (the spacing options then have no effect, as in the
     library); only the host table changes."""
     kind = 1
+    state_slots = 1
     _ALLOWED = ("use_karras_sigmas",)
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, solver_order=2,
@@ -636,6 +679,7 @@ class LCMScheduler(_SchedulerBase):
     x' = den and nothing is drawn.  Table row = (sqrt(1-a_t), sqrt(a_t), c_out, c_skip, sqrt(a_prev), sqrt(1-a_prev), 0, 0),
     the last row with (1, 0) in columns 4 and 5; the tensor math runs in `pp_cfg_lcm_step`."""
     kind = 4
+    _step_fields = {"denoised": None}
 
     # arithmetic options of diffusers-0.27 `LCMScheduler.__init__` that the fused step does not implement
     _CHECKED = ("prediction_type", "beta_schedule", "clip_sample", "thresholding", "rescale_betas_zero_snr", "trained_betas")
@@ -660,9 +704,7 @@ class LCMScheduler(_SchedulerBase):
         names = set(inspect.signature(cls.__init__).parameters) - {"self", "kw"}
         return cls(**{k: v for k, v in src.items() if k in names or k in cls._CHECKED})
 
-    @property
-    def step_noise(self) -> bool:
-        return True
+    step_noise = True        # (a constant in place of the base's property)
 
     def draws_noise_at(self, row: int) -> bool:
         return int(row) != len(self._ts_host) - 1
@@ -736,24 +778,14 @@ class LCMScheduler(_SchedulerBase):
                 coef[i, 4], coef[i, 5] = 1.0, 0.0                        # prev_sample = denoised, no noise drawn
         self._coef = coef
 
+    def step_launch(self, eps, cfg, guidance, lat, state, noise, n, step, ticket):
+        """Guidance combine, consistency transition, noise term and counter advance in one launch (no state)."""
+        return ("cfg_lcm_step", L.lib().pp_cfg_lcm_step, eps, cfg, guidance, lat, noise, n, self._coef_dev.data_ptr(), step,
+                ticket)
+
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, **kw):
-        """x_t -> x_{t-1} in `pp_cfg_lcm_step` (fp32 math).  Returns a NEW tensor in sample's dtype.  The noise is drawn like
-        diffusers' `randn_tensor(model_output.shape, generator=generator, ...)`, and not on the schedule's last step."""
-        if not sample.is_cuda:
-            raise L.PPError("scheduler.step needs CUDA tensors: the step runs in the HIP kernel, no CPU fallback")
-        i = self._index_of(timestep)
-        x = sample.detach().to(torch.float32).contiguous().clone()
-        e = model_output.detach().to(torch.float32).contiguous()
-        step = torch.full((1,), i, dtype=torch.int32, device=x.device)
-        # (the last row never reads the noise: any valid address does)
-        z = variance_noise(model_output.shape, generator, x.device, model_output.dtype) if self.draws_noise_at(i) else x
-        L.check(L.lib().pp_cfg_lcm_step(e.data_ptr(), 0, 0.0, x.data_ptr(), z.data_ptr(), x.numel(),
-                                         self._coef_dev.data_ptr(), step.data_ptr(), None,
-                                         torch.cuda.current_stream().cuda_stream), "pp_cfg_lcm_step")
-        out = x.to(sample.dtype)
-        if not return_dict:
-            return (out,)
-        return SimpleNamespace(prev_sample=out, denoised=None)
+        """`_SchedulerBase.step` without `eta` in its signature, which `prepare_extra_step_kwargs` reads."""
+        return super().step(model_output, timestep, sample, generator=generator, return_dict=return_dict)
 
 
 class _SigmaScheduler(_SchedulerBase):
@@ -766,6 +798,8 @@ class _SigmaScheduler(_SchedulerBase):
     use_karras_sigmas: the rho = 7 ramp between the ends of that inference grid, timesteps = the fractional `sigma_to_t`.
     Table row = (sigma_i, dt, s_up, 0 ...), evaluated in fp32 torch in the library's operation order; the tensor math
     x' = x + dt e + s_up z runs in `pp_cfg_sigma_step`.  No state between steps."""
+    scales_input = True
+    _step_fields = {"pred_original_sample": None}
     _ALLOWED = ("use_karras_sigmas",)
     # arithmetic options of the library's constructors that the fused step does not implement at another value
     _CHECKED = ("prediction_type", "beta_schedule", "trained_betas", "rescale_betas_zero_snr", "interpolation_type",
@@ -890,38 +924,15 @@ class _SigmaScheduler(_SchedulerBase):
     def draws_noise_at(self, row: int) -> bool:
         return True          # the library's step calls randn_tensor on every step, the last one included
 
-    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, **kw):
-        """x_i -> x_{i+1} in `pp_cfg_sigma_step` (fp32 math).  Returns a NEW tensor in sample's dtype.  The noise is drawn
-        like the library's `randn_tensor(model_output.shape, generator=generator, ...)`: on every step, also where it is
-        not used (plain Euler; the last ancestral step) -- the caller's generator ends where the library leaves it."""
-        if not sample.is_cuda:
-            raise L.PPError("scheduler.step needs CUDA tensors: the step runs in the HIP kernel, no CPU fallback")
-        i = self._index_of(timestep)
-        x = sample.detach().to(torch.float32).contiguous().clone()
-        e = model_output.detach().to(torch.float32).contiguous()
-        step = torch.full((1,), i, dtype=torch.int32, device=x.device)
-        if self.step_noise:
-            z = variance_noise(model_output.shape, generator, x.device, model_output.dtype)
-        else:
-            self.discard_draw(model_output.shape, generator, model_output.dtype)
-            z = x                                       # (s_up = 0: never read, any valid address does)
-        L.check(L.lib().pp_cfg_sigma_step(e.data_ptr(), 0, 0.0, x.data_ptr(), z.data_ptr(), x.numel(),
-                                           self._coef_dev.data_ptr(), step.data_ptr(), None,
-                                           torch.cuda.current_stream().cuda_stream), "pp_cfg_sigma_step")
-        out = x.to(sample.dtype)
-        if not return_dict:
-            return (out,)
-        return SimpleNamespace(prev_sample=out, pred_original_sample=None)
+    def step_launch(self, eps, cfg, guidance, lat, state, noise, n, step, ticket):
+        """x' = x + dt e + s_up z (no state; plain Euler has s_up = 0 in every row and never reads the noise)."""
+        return ("cfg_sigma_step", L.lib().pp_cfg_sigma_step, eps, cfg, guidance, lat, noise, n, self._coef_dev.data_ptr(), step,
+                ticket)
 
-    @staticmethod
-    def discard_draw(shape, generator, dtype):
-        """Advance `generator` by one `randn_tensor(shape)` without keeping or uploading the numbers.  (No generator: the
-        library would use the global RNG, which nothing here has to stay in step with.)"""
-        gens = generator if isinstance(generator, (list, tuple)) else [generator]
-        sh = tuple(shape) if len(gens) == 1 else (1,) + tuple(shape[1:])
-        for g in gens:
-            if isinstance(g, torch.Generator):
-                torch.randn(sh, generator=g, device=g.device, dtype=dtype)
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, **kw):
+        """`_SchedulerBase.step` without `eta` in its signature.  The Euler classes draw on every step, also where the noise is
+        not used (plain Euler: `discards_draw`; the last ancestral step); DPM2 ancestral on every call, both stages."""
+        return super().step(model_output, timestep, sample, generator=generator, return_dict=return_dict)
 
 
 class EulerDiscreteScheduler(_SigmaScheduler):
@@ -944,9 +955,7 @@ class EulerAncestralDiscreteScheduler(_SigmaScheduler):
     one s_up = 0 and the drawn z is not read)."""
     kind = 6
 
-    @property
-    def step_noise(self) -> bool:
-        return True
+    step_noise = True        # (a constant in place of the base's property)
 
     def _sigma_up(self, s_from, s_to):
         return (s_to ** 2 * (s_from ** 2 - s_to ** 2) / s_from ** 2) ** 0.5
@@ -1008,25 +1017,10 @@ class _KSampler(_SigmaScheduler):
         self._coef = torch.stack(rows)
         self._set_row_sigmas(self._coef[:, 5])
 
-    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, **kw):
-        """One table row in `pp_cfg_ksampler_step` (fp32 math).  Returns a NEW tensor in sample's dtype; the state between
-        the calls lives in the scheduler, zeroed by `set_timesteps` / `set_begin_index`.  DPM2 ancestral draws its noise
-        like the library's `randn_tensor(model_output.shape, generator=generator, ...)`: on every call, both stages."""
-        if not sample.is_cuda:
-            raise L.PPError("scheduler.step needs CUDA tensors: the step runs in the HIP kernel, no CPU fallback")
-        i = self._index_of(timestep)
-        x = sample.detach().to(torch.float32).contiguous().clone()
-        e = model_output.detach().to(torch.float32).contiguous()
-        step = torch.full((1,), i, dtype=torch.int32, device=x.device)
-        # (s_up = 0 in every row of the other three: never read, any valid address does)
-        z = variance_noise(model_output.shape, generator, x.device, model_output.dtype) if self.step_noise else x
-        L.check(L.lib().pp_cfg_ksampler_step(e.data_ptr(), 0, 0.0, x.data_ptr(), self.m_prev(x).data_ptr(), z.data_ptr(),
-                                              x.numel(), self._coef_dev.data_ptr(), step.data_ptr(), None,
-                                              torch.cuda.current_stream().cuda_stream), "pp_cfg_ksampler_step")
-        out = x.to(sample.dtype)
-        if not return_dict:
-            return (out,)
-        return SimpleNamespace(prev_sample=out, pred_original_sample=None)
+    def step_launch(self, eps, cfg, guidance, lat, state, noise, n, step, ticket):
+        """One table row on the state [4][n] (s_up = 0 in every row of Heun, DPM2 and LMS: the noise is never read)."""
+        return ("cfg_ksampler_step", L.lib().pp_cfg_ksampler_step, eps, cfg, guidance, lat, state, noise, n,
+                self._coef_dev.data_ptr(), step, ticket)
 
 
 class HeunDiscreteScheduler(_KSampler):
@@ -1082,9 +1076,7 @@ class KDPM2AncestralDiscreteScheduler(KDPM2DiscreteScheduler):
     generator ends where the library leaves it.  The last step has s_down = 0: Euler, no noise added."""
     kind = 9
 
-    @property
-    def step_noise(self) -> bool:
-        return True
+    step_noise = True        # (a constant in place of the base's property)
 
     _sigma_up = EulerAncestralDiscreteScheduler._sigma_up
 
