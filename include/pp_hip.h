@@ -884,6 +884,25 @@ int pp_freeu(const void* hidden, void* hidden_out, int ch, const void* skip, voi
 int pp_ip_attn_add(const void* q, int ldq, const void* k_ip, const void* v_ip, void* o, int ldo, int batch, int heads, int nq,
                    int nk, int d, float qk_scale, float ip_scale, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * IP-Adapter Plus (added under ABI 29: purely additive).  The attention of the adapter's Resampler -- a few latent queries
+ * over the image rows AND the latent rows, which the two to_kv GEMMs of a layer leave in two buffers:
+ *     o[b,i,h*d:(h+1)*d] = sum_t softmax_t(scale * q[b,i,h] . K[b,t,h]) V[b,t,h],   t over nx + nl keys
+ *   q, o  : 16-bit, element (b, i, h, j) at [(b*nq + i)*ld + h*d + j]; ldq, ldo >= heads*d; q is only read, q != o
+ *   kv_x  : 16-bit rows of [K | V]: key t < nx of item b is row b*nx + t (row stride ldkx >= 2*heads*d), K at column
+ *           h*d + j, V at column heads*d + h*d + j -- what a to_kv GEMM writes
+ *   kv_l  : likewise with nl rows per item: keys nx .. nx + nl - 1.  nl = 0 with kv_l = NULL is plain cross-attention
+ *           (nl > 0 without kv_l, or the reverse, is PP_ERR_BAD_ARG)
+ *   d     : 64 (else PP_ERR_UNSUPPORTED); nq >= 1, nx >= 1, nl >= 0, any number of keys (they are walked in tiles with a
+ *           running maximum and sum); every leading dimension a multiple of 8, every pointer 16-byte aligned
+ *           (PP_ERR_BAD_ARG otherwise); batch, heads <= 65535
+ * Scores, softmax (maximum subtracted; the denominator sums the unrounded probabilities) and accumulation are fp32; the
+ * probabilities are rounded once to `dtype` for the P V matrix product; one rounding to `dtype` (bf16 / fp16) at the store.
+ * Nothing outside rows [0, batch*nq) x columns [0, heads*64) of o is written; nothing behind the last key row of either
+ * segment, and no column behind 2*heads*64, reaches the result (they may hold anything finite or not). */
+int pp_perceiver_attn(const void* q, int ldq, const void* kv_x, int ldkx, int nx, const void* kv_l, int ldkl, int nl, void* o,
+                      int ldo, int batch, int heads, int nq, int d, float scale, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -554,8 +554,8 @@ class Builder:
         filled = (acc, groups) if acc else None
         return (Act(h.ptr, h.B, h.H, h.W, h.C, gn_filled=filled), Act(sk.ptr, sk.B, sk.H, sk.W, sk.C, gn_filled=filled))
 
-    def layernorm(self, x: int, rows: int, Cc: int, gamma: int, beta: int, eps: float = 1e-5) -> int:
-        out = self.alloc(rows * Cc * 2)
+    def layernorm(self, x: int, rows: int, Cc: int, gamma: int, beta: int, eps: float = 1e-5, out: int = 0) -> int:
+        out = out or self.alloc(rows * Cc * 2)
         self.plan.add("layernorm", self.lib.pp_layernorm, x, rows, Cc, gamma, beta, eps, out, self.dt)
         return out
 
@@ -582,6 +582,17 @@ class Builder:
         self.plan.add("ip_attn_add", self.lib.pp_ip_attn_add, q, ldq, k_ip, v_ip, o, ldo, B, heads, nq, nk, d,
                       float(d) ** -0.5, scale, self.dt)
         self.plan.count("ip_attn_add", 4.0 * B * nq * nk * heads * d)
+
+    def perceiver_attn(self, q: int, ldq: int, kv_x: int, ldkx: int, nx: int, kv_l: int, ldkl: int, nl: int, B: int, heads: int,
+                       nq: int, out: int = 0) -> int:
+        """The Resampler's attention (csrc/perceiver_attn.hip): nq queries per item over the nx + nl keys of the two [K | V]
+        segments the to_kv GEMMs wrote; head dimension 64.  Returns o [B * nq][heads * 64]."""
+        d = 64
+        out = out or self.alloc(B * nq * heads * d * 2)
+        self.plan.add("perceiver_attn", self.lib.pp_perceiver_attn, q, ldq, kv_x, ldkx, nx, kv_l or None, ldkl, nl, out,
+                      heads * d, B, heads, nq, d, float(d) ** -0.5, self.dt)
+        self.plan.count("perceiver_attn", 4.0 * B * heads * nq * (nx + nl) * d)
+        return out
 
     def ff_fused(self, hs: int, rows: int, Cc: int, hw: int, w1: int, b1: int, cs1: int, ln_stats: int, ln_tiles: int,
                  w2: int, bias2: int, out: int, res1: int = 0, res1_wrap: int = 0, res2: int = 0, w2_kperm: bool = False):
@@ -941,14 +952,16 @@ class SDNet:
         self.P: Dict[str, int] = {}
         self.temb_off: Dict[str, int] = {}
         self.temb_total = 0
-        # IP-Adapters (set_ip_adapters): per adapter (tokens per image, image-embed dimension); empty = a network without any
-        self.ip: List[Tuple[int, int]] = []
+        # IP-Adapters (set_ip_adapters): per adapter (tokens per image, image-embed dimension) -- the plain pair for a base
+        # adapter, an ip_adapter.IPPlus (the pair, then the Resampler's sizes) for a Plus one; empty = a network without any
+        self.ip: List[Tuple[int, ...]] = []
         # what build_setup leaves for build_step (per plan: every build_setup starts them afresh)
         self._nctx = 0                                          # context tokens
         self.kv: Dict[str, Tuple[int, int, int, int]] = {}      # transformer -> hoisted cross-attention (K, ldk, V^T, ldvt)
         self.xa: Dict[str, XAttnFold] = {}                      # ... -> folded cross-attention operands (none: the chain)
         self.ip_kv: Dict[str, List[Tuple[int, int, int]]] = {}  # ... -> per IP-Adapter (K_i, V_i, tokens)
         self.ip_scale_cells: list = []                          # per IP-Adapter: its ctypes.c_float scale cell
+        self.ip_tok: List[Tuple[int, int]] = []                 # per IP-Adapter: (image tokens e_i, tokens per batch item)
         self.upfold: Dict[str, int] = {}                        # upsampler conv -> its sub-pixel folded weights
         self.cond_emb: Optional[Act] = None                     # (controlnet) the conditioning embedding
         for c in self.boc:
@@ -1424,6 +1437,14 @@ class SDNet:
           ip_adapter.<i>.proj.weight   16-bit [T * ctx][D rounded up to 64] (zero columns: the GEMM contracts 64 at a time)
           ip_adapter.<i>.proj.bias, .norm.weight, .norm.bias   fp32
           ip_adapter.<i>.<transformer>.kv.weight   16-bit [2 C][ctx] = [to_k_ip; to_v_ip], as attn2.kv.weight
+        A Plus adapter (ad["kind"] == "plus", ad["plus"] its ip_adapter.IPPlus) brings the Resampler's file keys instead of
+        proj / norm and is packed as
+          ip_adapter.<i>.resampler.latents   16-bit [Q][dim]
+          ip_adapter.<i>.resampler.{proj_in,proj_out}.weight   16-bit (proj_in [dim][E rounded up to 64], zero columns), .bias
+                                                               fp32;  .norm_out.{weight,bias}   fp32
+          ip_adapter.<i>.resampler.layers.<l>.{to_q,to_kv,to_out,ff1,ff2}.weight   16-bit (to_kv = [K rows; V rows], as filed)
+          ip_adapter.<i>.resampler.layers.<l>.{norm1,norm2,ff_norm}.{weight,bias}   fp32
+        with the same kv.weight pairs.  Base and Plus adapters mix freely.
         They are no source of any PackRecipe: `repack` (LoRA) never touches them.  Every packed pointer moves."""
         if self.kind != "unet":
             raise L.PPError("IP-Adapters attach to the UNet's cross-attentions only")
@@ -1435,18 +1456,37 @@ class SDNet:
         pk.forget("ip_adapter.", self._own_bytes)
         ip = []
         for i, ad in enumerate(adapters):
-            w = ad["proj.weight"].float()
-            D = w.shape[1]
-            T = w.shape[0] // self.ctx_dim
-            wp = torch.zeros(w.shape[0], _align(D, 64))
-            wp[:, :D] = w
-            pk.add(f"ip_adapter.{i}.proj.weight", wp, self.dtype)
-            for n in ("proj.bias", "norm.weight", "norm.bias"):
-                pk.add(f"ip_adapter.{i}.{n}", ad[n].float(), torch.float32)
+            if ad.get("kind") == "plus":
+                sp = ad["plus"]
+                R = f"ip_adapter.{i}.resampler"
+                pk.add(f"{R}.latents", ad["latents"].float()[0], self.dtype)
+                w_in = torch.zeros(sp.dim, _align(sp.D, 64))          # (zero columns up to the GEMM's 64, as a base proj.weight)
+                w_in[:, :sp.D] = ad["proj_in.weight"].float()
+                for n, w in (("proj_in", w_in), ("proj_out", ad["proj_out.weight"].float())):
+                    pk.add(f"{R}.{n}.weight", w, self.dtype)
+                    pk.add(f"{R}.{n}.bias", ad[f"{n}.bias"].float(), torch.float32)
+                for wb in ("weight", "bias"):
+                    pk.add(f"{R}.norm_out.{wb}", ad[f"norm_out.{wb}"].float(), torch.float32)
+                for l in range(sp.depth):
+                    for dst, src in (("to_q", "0.to_q"), ("to_kv", "0.to_kv"), ("to_out", "0.to_out"), ("ff1", "1.1"), ("ff2", "1.3")):
+                        pk.add(f"{R}.layers.{l}.{dst}.weight", ad[f"layers.{l}.{src}.weight"].float(), self.dtype)
+                    for dst, src in (("norm1", "0.norm1"), ("norm2", "0.norm2"), ("ff_norm", "1.0")):
+                        for wb in ("weight", "bias"):
+                            pk.add(f"{R}.layers.{l}.{dst}.{wb}", ad[f"layers.{l}.{src}.{wb}"].float(), torch.float32)
+                ip.append(sp)
+            else:
+                w = ad["proj.weight"].float()
+                D = w.shape[1]
+                T = w.shape[0] // self.ctx_dim
+                wp = torch.zeros(w.shape[0], _align(D, 64))
+                wp[:, :D] = w
+                pk.add(f"ip_adapter.{i}.proj.weight", wp, self.dtype)
+                for n in ("proj.bias", "norm.weight", "norm.bias"):
+                    pk.add(f"ip_adapter.{i}.{n}", ad[n].float(), torch.float32)
+                ip.append((T, D))
             for pre, _ in self._attn_specs():
                 wk, wv = ad["kv"][pre]
                 pk.add(f"ip_adapter.{i}.{pre}.kv.weight", torch.cat([wk.float(), wv.float()], 0), self.dtype)
-            ip.append((T, D))
         pk.regrow(self._own_bytes)
         self.P = pk.ptr
         self.ip = ip
@@ -1522,6 +1562,42 @@ class SDNet:
         pb.release(m)
         return out
 
+    def _resampler(self, pb: Builder, R: str, sp, x_in: int, N: int, S: int, lat0: int) -> int:
+        """IP-Adapter Plus's image projection over N = B n images (DESIGN.md "IP-Adapter"): x_in = hidden states [N S][E rounded up to
+        64] (zero pad columns), lat0 = the latents repeated N times [N Q][dim] (only read) -> the tokens [N Q][ctx].  proj_in; per layer LayerNorm1(x),
+        LayerNorm2(l), to_q, to_kv over the image rows and over the latent rows (two buffers: the two segments
+        pp_perceiver_attn reads), the attention, to_out + l, LayerNorm, W1 with GELU, W2 + l; proj_out, norm_out."""
+        P = self.P
+        Q, E, dim, inner, ff = sp.T, sp.D, sp.dim, sp.heads * 64, sp.ff
+        # Every buffer is allocated once and reused by all layers; none is ever released: what the runtimes allocate behind the
+        # setup plan lives for the whole call (tables made once per plan among it), and this plan runs again at every call.
+        la, lb = pb.alloc(N * Q * dim * 2), pb.alloc(N * Q * dim * 2)      # the residual stream, ping-pong
+        x, xn = pb.alloc(N * S * dim * 2), pb.alloc(N * S * dim * 2)
+        ln, h, q, a = (pb.alloc(N * Q * c * 2) for c in (dim, dim, inner, inner))
+        kvx, kvl, g = pb.alloc(N * S * 2 * inner * 2), pb.alloc(N * Q * 2 * inner * 2), pb.alloc(N * Q * ff * 2)
+        pb.linear(x_in, N * S, _align(E, 64), P[f"{R}.proj_in.weight"], dim, P[f"{R}.proj_in.bias"], out=x, name="linear")
+        l = lat0
+        for j in range(sp.depth):
+            Lp = f"{R}.layers.{j}"
+            pb.layernorm(x, N * S, dim, P[f"{Lp}.norm1.weight"], P[f"{Lp}.norm1.bias"], out=xn)
+            pb.layernorm(l, N * Q, dim, P[f"{Lp}.norm2.weight"], P[f"{Lp}.norm2.bias"], out=ln)
+            pb.linear(ln, N * Q, dim, P[f"{Lp}.to_q.weight"], inner, out=q, name="linear")
+            pb.linear(xn, N * S, dim, P[f"{Lp}.to_kv.weight"], 2 * inner, out=kvx, name="linear")
+            pb.linear(ln, N * Q, dim, P[f"{Lp}.to_kv.weight"], 2 * inner, out=kvl, name="linear")
+            pb.perceiver_attn(q, inner, kvx, 2 * inner, S, kvl, 2 * inner, Q, N, sp.heads, Q, out=a)
+            pb.linear(a, N * Q, inner, P[f"{Lp}.to_out.weight"], dim, res1=l, out=lb, name="linear")
+            pb.layernorm(lb, N * Q, dim, P[f"{Lp}.ff_norm.weight"], P[f"{Lp}.ff_norm.bias"], out=h)
+            pb.linear(h, N * Q, dim, P[f"{Lp}.ff1.weight"], ff, act=L.PP_ACT_GELU, out=g, name="linear")
+            pb.linear(g, N * Q, ff, P[f"{Lp}.ff2.weight"], dim, res1=lb, out=la, name="linear")
+            l = la
+        y = pb.linear(l, N * Q, dim, P[f"{R}.proj_out.weight"], self.ctx_dim, P[f"{R}.proj_out.bias"], name="linear")
+        e = pb.layernorm(y, N * Q, self.ctx_dim, P[f"{R}.norm_out.weight"], P[f"{R}.norm_out.bias"])
+        # The split-K workspaces of the GEMMs above (W2 contracts ff = 3072) sat on top of the arena and are dirty from the
+        # first run on.  What build_setup allocates next counts on the arena's zeros where no launch ever writes -- the pad
+        # columns of V^T, which the attention multiplies by a zero probability -- so it starts above everything used here.
+        pb.arena.off = max(pb.arena.off, pb.arena.peak)
+        return e
+
     # ---------------------------------------------------------------- setup plan: step-invariant work
     def build_setup(self, pb: Builder, B: int, nctx: int, ehs: int, cond: Optional[Act] = None, *,
                     hw0: Tuple[int, int], ip_in: Sequence[Tuple[int, int]] = (), ip_scales=()):
@@ -1531,21 +1607,29 @@ class SDNet:
         ip_in (a UNet with IP-Adapters, one entry per adapter): (pointer, n) of the call's image embeds, 16-bit [B][n][D rounded
         up to 64] with zero pad columns; ip_scales: the adapters' ctypes.c_float scale cells.  The image tokens
         e_i = LayerNorm(reshape(proj(embeds))) [B][n T][ctx] and, per transformer, K_i = to_k_ip(e_i) and V_i = to_v_ip(e_i),
-        row-major [B][n T][C] each, are step-invariant: computed here, read by the step plan's pp_ip_attn_add launches.  While
+        row-major [B][n T][C] each, are step-invariant: computed here, read by the step plan's pp_ip_attn_add launches.  For a
+        Plus adapter the entry is (pointer, n, S, latents pointer): the 16-bit hidden states [B n S][E rounded up to 64] and the adapter's latents
+        repeated B n times [B n Q][dim] (NetRuntime.set_ip_embeds fills both), and e_i comes out of the Resampler
+        (_resampler: 10 depth + 3 launches).  While
         adapters are loaded every cross-attention is XAttnForm.CHAIN (self.xa stays empty): to_q -> attention -> to_out."""
         self._nctx = nctx
         if len(ip_in) != len(self.ip) or len(ip_scales) != len(self.ip):
             raise L.PPError(f"{len(self.ip)} IP-Adapters are loaded, the setup plan was given {len(ip_in)} image-embed buffers")
         self.ip_kv, self.ip_scale_cells = {}, list(ip_scales)
         ip_tok = []
-        for i, ((T, D), (src, n)) in enumerate(zip(self.ip, ip_in)):
+        for i, (spec, entry) in enumerate(zip(self.ip, ip_in)):
+            (T, D), (src, n) = spec[:2], entry[:2]
             if n < 1 or n * T > L.PP_IP_MAX_TOKENS:
                 raise L.PPError(f"IP-Adapter {i}: {n} images of {T} tokens, pp_ip_attn_add takes 1..{L.PP_IP_MAX_TOKENS} tokens")
             Pn = f"ip_adapter.{i}"
+            if len(spec) > 2:
+                ip_tok.append((self._resampler(pb, f"{Pn}.resampler", spec, src, B * n, entry[2], entry[3]), n * T))
+                continue
             y = pb.linear(src, B * n, _align(D, 64), self.P[f"{Pn}.proj.weight"], T * self.ctx_dim, self.P[f"{Pn}.proj.bias"],
                           name="linear")
             e = pb.layernorm(y, B * n * T, self.ctx_dim, self.P[f"{Pn}.norm.weight"], self.P[f"{Pn}.norm.bias"])
             ip_tok.append((e, n * T))
+        self.ip_tok = ip_tok               # per adapter (e_i [B][n T][ctx], n T): what the K_i / V_i GEMMs below read
         ldvt = _align(nctx, 8)
         forms = self.xattn_forms(pb.lib, B, hw0[0], hw0[1], nctx)
         self.kv, self.xa = {}, {}

@@ -175,7 +175,8 @@ class UNet2DConditionModel(_HipModel):
         adapters were loaded.  Everything is validated before anything changes: a refused file leaves the model as it was.
         The weights go into the packed parameter buffer (SDNet.set_ip_adapters); the plans are rebuilt on the next call,
         without the fused cross-attention forms and the CFG twin prefix (every attn2 runs to_q -> attention ->
-        pp_ip_attn_add per adapter -> to_out).  Scales start at 1.0, as in diffusers."""
+        pp_ip_attn_add per adapter -> to_out).  Base and Plus (Resampler) files load, mixed freely; `encoder_hid_proj` shows an
+        ImageProjection or an IPAdapterPlusImageProjection per adapter.  Scales start at 1.0, as in diffusers."""
         if isinstance(state_dicts, dict):
             state_dicts = [state_dicts]
         if not state_dicts:
@@ -207,7 +208,8 @@ class UNet2DConditionModel(_HipModel):
 
     def _ip_image_embeds(self, added_cond_kwargs, B: int):
         """`added_cond_kwargs["image_embeds"]` of a UNet with IP-Adapters (unet_2d_condition.py:1030-1037 of the reference):
-        a list of [B, n, D] tensors, one per adapter.  Without adapters the key is refused, never ignored."""
+        a list with one tensor per adapter, [B, n, D] for a base adapter and [B, n, S, E] for a Plus adapter (each refuses the
+        other's rank by name).  Without adapters the key is refused, never ignored."""
         if not self.net.ip:
             if added_cond_kwargs and "image_embeds" in added_cond_kwargs:
                 raise L.PPError("added_cond_kwargs['image_embeds'] given but no IP-Adapter is loaded (load_ip_adapter first)")
@@ -216,9 +218,10 @@ class UNet2DConditionModel(_HipModel):
             raise ValueError(f"{self.__class__} has the config param `encoder_hid_dim_type` set to 'ip_image_proj' which requires "
                              f"the keyword argument `image_embeds` to be passed in  `added_conditions`")
         embeds = added_cond_kwargs["image_embeds"]
-        IPA.check_image_embeds(embeds, len(self.net.ip))
-        for i, (e, (T, D)) in enumerate(zip(embeds, self.net.ip)):
-            if e.shape[0] != B or e.shape[2] != D:
+        IPA.check_image_embeds(embeds, len(self.net.ip), [len(spec) > 2 for spec in self.net.ip])
+        for i, (e, spec) in enumerate(zip(embeds, self.net.ip)):
+            T, D = spec[:2]
+            if e.shape[0] != B or e.shape[-1] != D or (e.dim() == 4 and e.shape[2] < 1):
                 raise ValueError(f"image_embeds[{i}] has shape {tuple(e.shape)}, the UNet runs batch {B} and adapter {i} takes "
                                  f"embeds of dimension {D}")
             if e.shape[1] * T > L.PP_IP_MAX_TOKENS:
@@ -276,7 +279,7 @@ class UNet2DConditionModel(_HipModel):
                               down_block_additional_residuals, mid_block_additional_residual)
         ip_embeds = self._ip_image_embeds(added_cond_kwargs, B)
         self.rt.ensure(B, H, W, self._nctx(encoder_hidden_states), Cin, wiring, twin=twin, freeu=self._freeu_values(),
-                       ip_n=[e.shape[1] for e in ip_embeds] if ip_embeds else ())
+                       ip_n=[e.shape[1] if e.dim() == 3 else (e.shape[1], e.shape[2]) for e in ip_embeds] if ip_embeds else ())
         if ip_embeds:
             self.rt.set_ip_embeds(ip_embeds)
         if wiring[0] != "plain":

@@ -439,6 +439,21 @@ def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: in
     return o
 
 
+def perceiver_attention(q: torch.Tensor, kv_x: torch.Tensor, kv_l: Optional[torch.Tensor], batch: int, heads: int, nq: int,
+                        scale: Optional[float] = None, out: Optional[torch.Tensor] = None, ldo: Optional[int] = None):
+    """The Resampler's attention (pp_perceiver_attn): q [batch*nq, >=heads*64]; kv_x [batch*nx, >=2*heads*64] and kv_l
+    [batch*nl, ...] (or None) rows of [K | V], row strides from the tensors -> o [batch*nq, heads*64] over the nx + nl keys
+    (out / ldo: see _attn_out)."""
+    d = 64
+    o = _attn_out(out, ldo, batch * nq, heads * d, q)
+    nx, nl = kv_x.shape[0] // batch, (kv_l.shape[0] // batch if kv_l is not None else 0)
+    L.check(L.lib().pp_perceiver_attn(_p(q), q.stride(0), _p(kv_x), kv_x.stride(0), nx, _p(kv_l),
+                                      kv_l.stride(0) if kv_l is not None else 0, nl, _p(o), o.stride(0), batch, heads, nq, d,
+                                      scale if scale is not None else d ** -0.5, L.dtype_code(q.dtype), _s()),
+            "pp_perceiver_attn")
+    return o
+
+
 def softmax_rows(s: torch.Tensor, scale: float = 1.0, dtype=torch.bfloat16):
     """fp32 logits [rows, n] (row stride s.stride(0)) -> 16-bit softmax(scale * s) [rows, n]."""
     rows, n = s.shape

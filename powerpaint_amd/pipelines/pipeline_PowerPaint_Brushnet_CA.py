@@ -116,7 +116,9 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
         """diffusers' `IPAdapterMixin.load_ip_adapter` for local files and state dicts (nothing is downloaded): a dict
         {"image_proj": {...}, "ip_adapter": {...}}, a .bin holding one, a .safetensors with `image_proj.` / `ip_adapter.` key
         prefixes, a folder plus `weight_name` (and `subfolder`) -- or a list of those for several adapters (`subfolder` /
-        `weight_name` then a value or one per adapter).  Base adapters only; Plus / FaceID files are refused by name
+        `weight_name` then a value or one per adapter).  Base adapters (Linear + LayerNorm projection of the pooled image
+        embeds, [B, n, D] per call) and Plus adapters (the Resampler over the tower's `hidden_states[-2]`, [B, n, S, E] per
+        call, 16 tokens per image) load, alone or mixed in one list; FaceID and full-face files are refused by name
         (powerpaint_amd.ip_adapter.check_ip_adapter, which also states the index order of the cross-attentions).
         `image_encoder_folder` (default None: no image encoder is loaded) names the CLIP vision tower's folder as diffusers
         resolves it -- a name without "/" lies under `subfolder` of the model path, anything else is relative to the model
@@ -173,26 +175,39 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
 
     def encode_image(self, image, device, num_images_per_prompt, output_hidden_states=None):
         """pipeline_PowerPaint_Brushnet_CA.py:632-654 through the registered (duck-typed) `image_encoder` /
-        `feature_extractor`; the unconditional embeds of a base adapter are zeros."""
+        `feature_extractor`; the unconditional embeds of a base adapter are zeros.  output_hidden_states (IP-Adapter Plus,
+        :639-648): the encoder's `hidden_states[-2]` [B, S, E] of the image and of the ZERO image (its hidden states, not
+        zeros); each is copied by `repeat_interleave` before the next encoder call (the HIP tower's hidden states live in
+        buffers it writes again).  Hidden states serve a Plus adapter only: while none is loaded the request is refused, as an
+        image prompt without an adapter is -- never a tensor that nothing on the HIP path would take."""
         if self.image_encoder is None:
             raise ValueError("`ip_adapter_image` needs an `image_encoder` registered on the pipeline (none is): load one with "
                              "load_ip_adapter(<folder>, image_encoder_folder=...), register a "
                              "powerpaint_amd.models.CLIPVisionModelWithProjection, or pass `ip_adapter_image_embeds`")
         if output_hidden_states:
-            raise L.PPError("encode_image(output_hidden_states=True) serves IP-Adapter Plus, which is not implemented")
+            layers = getattr(getattr(self.unet, "encoder_hid_proj", None), "image_projection_layers", None) or ()
+            if not any(isinstance(m, IPA.IPAdapterPlusImageProjection) for m in layers):
+                raise L.PPError("encode_image(output_hidden_states=True) serves IP-Adapter Plus, and no Plus adapter is loaded "
+                                "(load_ip_adapter with a Plus file first; a base adapter takes the pooled image_embeds)")
         dtype = next(self.image_encoder.parameters()).dtype
         if not isinstance(image, torch.Tensor):
             if self.feature_extractor is None:
                 raise ValueError("`ip_adapter_image` that is not a tensor needs a `feature_extractor` registered on the pipeline")
             image = self.feature_extractor(image, return_tensors="pt").pixel_values
         image = image.to(device=device, dtype=dtype)
+        if output_hidden_states:
+            hs = self.image_encoder(image, output_hidden_states=True).hidden_states[-2]
+            hs = hs.repeat_interleave(num_images_per_prompt, dim=0)
+            uncond = self.image_encoder(torch.zeros_like(image), output_hidden_states=True).hidden_states[-2]
+            uncond = uncond.repeat_interleave(num_images_per_prompt, dim=0)
+            return hs, uncond
         image_embeds = self.image_encoder(image).image_embeds
         image_embeds = image_embeds.repeat_interleave(num_images_per_prompt, dim=0)
         return image_embeds, torch.zeros_like(image_embeds)
 
     def prepare_ip_adapter_image_embeds(self, ip_adapter_image, ip_adapter_image_embeds, device, num_images_per_prompt,
                                         do_classifier_free_guidance):
-        """pipeline_PowerPaint_Brushnet_CA.py:657-706: one [B, n, D] tensor per adapter, under CFG the negative embeds in the
+        """pipeline_PowerPaint_Brushnet_CA.py:657-706: one [B, n, D] (base) or [B, n, S, E] (Plus) tensor per adapter, under CFG the negative embeds in the
         first half of the batch (precomputed embeds carry them there already and are `chunk(2)`ed for the repeat)."""
         layers = getattr(getattr(self.unet, "encoder_hid_proj", None), "image_projection_layers", None)
         if layers is None:

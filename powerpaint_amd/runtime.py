@@ -58,11 +58,22 @@ class NetRuntime:
         return tuple(c.value for c in self.__dict__.get("_ip_scale_cells", [])[:len(getattr(self.net, "ip", []))])
 
     def set_ip_embeds(self, embeds: Optional[Sequence[torch.Tensor]]):
-        """The call's image embeds, one [B, n, D] tensor per loaded adapter, copied into the setup plan's inputs; the setup plan
+        """The call's image embeds, one [B, n, D] (base) or [B, n, S, E] (Plus) tensor per loaded adapter, copied into the setup plan's inputs; the setup plan
         runs again at the next set_context (the embeds change per call: they are never assumed unchanged)."""
         if "ip_in" not in self.lay:
             return
-        for (ptr, n), (T, D), e in zip(self.lay["ip_in"], self.net.ip, embeds):
+        for i, (entry, spec, e) in enumerate(zip(self.lay["ip_in"], self.net.ip, embeds)):
+            (ptr, n), (T, D) = entry[:2], spec[:2]
+            if len(spec) > 2:
+                # Plus: the hidden states [B n S][E rounded up to 64] (the pad columns stay the arena's zeros), and the adapter's
+                # latents repeated over the B n images -- the residual stream the Resampler's first layer reads
+                # (device-to-device from the packed buffer; no launch of the plan)
+                S, lat = entry[2], entry[3]
+                dst = self.arena.view(ptr, (self.B * n * S, D), self.net.dtype, strides=(_align(D, 64), 1))
+                dst.copy_(e.reshape(self.B * n * S, D).to(self.device))
+                src = self.net.params.tensor(f"ip_adapter.{i}.resampler.latents")
+                self.arena.view(lat, (self.B * n, T, spec.dim), self.net.dtype).copy_(src.unsqueeze(0).expand(self.B * n, -1, -1))
+                continue
             dst = self.arena.view(ptr, (self.B * n, D), self.net.dtype, strides=(_align(D, 64), 1))
             dst.copy_(e.reshape(self.B * n, D).to(self.device))
         self._ctx_id = None
@@ -104,7 +115,15 @@ class NetRuntime:
             # stay the arena's zeros), and one by-value scale cell per adapter shared by all its launches (set_ip_scales)
             if len(ip_n) != len(net.ip):
                 raise L.PPError(f"{len(net.ip)} IP-Adapters are loaded: the plan needs the image count of each")
-            lay["ip_in"] = [(arena.alloc(B * n * _align(D, 64) * 2), n) for (T, D), n in zip(net.ip, ip_n)]
+            # (a Plus adapter's ip_n entry is (n, S): S hidden states of width D per image, and its latents repeated B n times)
+            lay["ip_in"] = []
+            for spec, n in zip(net.ip, ip_n):
+                T, D = spec[:2]
+                if len(spec) > 2:
+                    n, S = n
+                    lay["ip_in"].append((arena.alloc(B * n * S * _align(D, 64) * 2), n, S, arena.alloc(B * n * T * spec.dim * 2)))
+                else:
+                    lay["ip_in"].append((arena.alloc(B * n * _align(D, 64) * 2), n))
             ip_kw = dict(ip_in=lay["ip_in"], ip_scales=self._ip_cells(len(net.ip)))
         net.build_setup(pb_setup, B, nctx, lay["ehs"], cond, hw0=(H, W), **ip_kw)
         pb = Builder(arena, dtype=net.dtype)
@@ -172,7 +191,8 @@ class NetRuntime:
                scale: float = 1.0, pad_uncond: bool = False, twin: bool = False, freeu=None, ip_n=()):
         """freeu: None, or (s1, s2, b1, b2) of UNet2DConditionModel.enable_freeu -- on / off is part of the plan key (the
         plan gains one pp_freeu launch per resnet of up blocks 0 and 1), the values live in device memory the launches read.
-        ip_n: images per loaded IP-Adapter in this call's embeds (part of the key only while adapters are loaded).
+        ip_n: images per loaded IP-Adapter in this call's embeds, (images, hidden states per image) for a Plus adapter (part of
+        the key only while adapters are loaded).
         twin: the caller vouches that the second half of every network input (x_in, ControlNet conditioning) equals the
         first -- a CFG pair built from one tensor; the step plan then runs the prompt-independent prefix on one half
         (SDNet.build_step)."""
@@ -185,7 +205,7 @@ class NetRuntime:
                bool(twin)) + (("freeu",) if freeu is not None else ())      # (without FreeU: the key of a plan that never had it)
         ip = getattr(getattr(self, "net", None), "ip", None)
         if ip:
-            key += (("ip", tuple(ip), tuple(int(n) for n in ip_n)),)
+            key += (("ip", tuple(ip), tuple(tuple(int(v) for v in n) if isinstance(n, (tuple, list)) else int(n) for n in ip_n)),)
         if isinstance(scale, (list, tuple)):
             scale = tuple(float(v) for v in scale)       # (one representation: a list never equals the stored tuple)
         if key == self.key:
