@@ -884,6 +884,20 @@ int pp_freeu(const void* hidden, void* hidden_out, int ch, const void* skip, voi
 int pp_ip_attn_add(const void* q, int ldq, const void* k_ip, const void* v_ip, void* o, int ldo, int batch, int heads, int nq,
                    int nk, int d, float qk_scale, float ip_scale, int dtype, void* stream);
 
+/* (added under ABI 29; purely additive) pp_ip_attn_add under diffusers-0.27 `ip_adapter_masks`: the term of query row r is
+ * multiplied by row_w[r] (IPAdapterMaskProcessor.downsample of the adapter's mask: one value per query row, in flat row
+ * order, the same for every batch item and channel):
+ *     o[b][r][:] += ip_scale * row_w[r] * sum_j softmax_j(qk_scale * q[b][r][h] . k_ip[b][j][h]) * v_ip[b][j][h]
+ *   row_w      : DEVICE pointer to fp32 [nq], 4-byte aligned -- read by the kernel, so a captured graph follows new values.
+ *                NULL or unaligned is PP_ERR_BAD_ARG.  Any finite value: a bicubic resize of a binary mask rings below 0
+ *                and above 1.
+ *   everything else as pp_ip_attn_add: the same limits and return codes, ip_scale == 0 launches nothing
+ * Arithmetic as pp_ip_attn_add, ip_scale * row_w[r] formed in fp32, still ONE rounding to `dtype` at the store.  With
+ * row_w[r] == 1.0f the row is pp_ip_attn_add's bit for bit.  A row with row_w[r] == 0.0f keeps its bits in o (signed zeros
+ * included): it is neither read (q, o) nor written, and a group of rows that are all 0 costs no arithmetic either. */
+int pp_ip_attn_add_masked(const void* q, int ldq, const void* k_ip, const void* v_ip, void* o, int ldo, int batch, int heads,
+                          int nq, int nk, int d, float qk_scale, float ip_scale, const float* row_w, int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * IP-Adapter Plus (added under ABI 29: purely additive).  The attention of the adapter's Resampler -- a few latent queries
  * over the image rows AND the latent rows, which the two to_kv GEMMs of a layer leave in two buffers:

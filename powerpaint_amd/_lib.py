@@ -187,6 +187,8 @@ SIGNATURES = {
     "pp_mask_prep": (C.c_int, [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "pp_ip_attn_add": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, f32,
                                  C.c_int, vp]),
+    "pp_ip_attn_add_masked": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, f32,
+                                        vp, C.c_int, vp]),
     "pp_perceiver_attn": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, f32, C.c_int, vp]),
 }

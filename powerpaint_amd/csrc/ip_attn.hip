@@ -15,6 +15,15 @@
 // first lane: 4 to 6 lane exchanges per score, a fixed fp32 summation order.
 // Scores, softmax (maximum subtracted), the weighted sum and the add are fp32; ONE rounding to the 16-bit format at the store.
 // Every element of o is read once and written once by the same lane; lanes outside [rows) x [columns) neither load nor store.
+//
+// pp_ip_attn_add_masked (diffusers' ip_adapter_masks) is the same body with MASK = true: the term of row r is multiplied by
+// row_w[r], one fp32 weight per query row shared by the batch items, READ from device memory (a captured graph follows new
+// values).  The weights of a pass are fetched ahead of its q / o loads -- one dependent load per pass, IP_ROWS values in
+// flight together -- because a row whose weight is exactly 0 keeps its bits: its lanes load neither q nor o and do not
+// store.  A row group without a live lane is skipped by a wave-uniform branch; in a group that runs, every lane executes
+// every lane exchange of head_sum (a dead lane computes on zeros and stores nothing).  The weight multiplies ip_scale in
+// fp32 in front of the division by the softmax denominator: with a weight of 1.0 that product is ip_scale itself and the
+// result is pp_ip_attn_add's bit for bit.  The MASK = false instantiations are the code they were.
 #include "pp_common.h"
 
 namespace {
@@ -31,6 +40,7 @@ struct IpArgs {
   long long ldq, ldo;
   int nq, nk, C, L, span, R;     // span = G * L lanes per row of the slab; R rows per wave pass
   float qk_scale, ip_scale;
+  const float* row_w;            // MASK only: fp32 [nq], one weight per query row (behind the unmasked form's fields)
 };
 
 template <int DT>
@@ -73,7 +83,7 @@ PP_DEVINL float head_sum(float x, int L, int leader) {
   return __shfl(t, leader, 64);
 }
 
-template <int DT, bool REG>
+template <int DT, bool REG, bool MASK>
 __global__ __launch_bounds__(IP_T) void ip_attn_add_kernel(const IpArgs a) {
   typedef E16<DT> E;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -102,10 +112,18 @@ __global__ __launch_bounds__(IP_T) void ip_attn_add_kernel(const IpArgs a) {
   const int wg = blockIdx.x * (IP_T / 64) + wave, nwaves = gridDim.x * (IP_T / 64);
   for (int r0 = wg * a.R * IP_ROWS; r0 < a.nq; r0 += nwaves * a.R * IP_ROWS) {        // (wave-uniform trip count)
     u32x4_t qu[IP_ROWS], ou[IP_ROWS];
+    float rw[IP_ROWS];
+    if (MASK) {
+#pragma unroll
+      for (int t = 0; t < IP_ROWS; ++t) {
+        const int r = r0 + t * a.R + rsub;
+        rw[t] = (lane_on && r < a.nq) ? a.row_w[r] : 0.f;
+      }
+    }
 #pragma unroll
     for (int t = 0; t < IP_ROWS; ++t) {
       const int r = r0 + t * a.R + rsub;
-      const bool ok = lane_on && r < a.nq;
+      const bool ok = lane_on && r < a.nq && (!MASK || rw[t] != 0.f);
       const size_t row = (size_t)b * a.nq + (size_t)(ok ? r : 0);
       qu[t] = ok ? *reinterpret_cast<const u32x4_t*>(a.q + row * a.ldq + col) : zero4;
       ou[t] = ok ? *reinterpret_cast<const u32x4_t*>(a.o + row * a.ldo + col) : zero4;
@@ -114,7 +132,8 @@ __global__ __launch_bounds__(IP_T) void ip_attn_add_kernel(const IpArgs a) {
     for (int t = 0; t < IP_ROWS; ++t) {
       if (r0 + t * a.R >= a.nq) break;                               // (wave-uniform: no row of this group exists)
       const int r = r0 + t * a.R + rsub;
-      const bool ok = lane_on && r < a.nq;
+      const bool ok = lane_on && r < a.nq && (!MASK || rw[t] != 0.f);
+      if (MASK && !__any(ok)) continue;                              // (wave-uniform: every row of this group has weight 0)
       float qf[8], acc[8];
       unpack8<DT>(qu[t], qf);
 #pragma unroll
@@ -154,7 +173,7 @@ __global__ __launch_bounds__(IP_T) void ip_attn_add_kernel(const IpArgs a) {
         }
       }
       if (ok) {
-        const float w = a.ip_scale / l;                              // (l >= 1: the maximum's own term)
+        const float w = (MASK ? a.ip_scale * rw[t] : a.ip_scale) / l;   // (l >= 1: the maximum's own term)
         float of[8];
         unpack8<DT>(ou[t], of);
         u32x4_t out;
@@ -169,8 +188,12 @@ __global__ __launch_bounds__(IP_T) void ip_attn_add_kernel(const IpArgs a) {
 
 }  // namespace
 
-extern "C" int pp_ip_attn_add(const void* q, int ldq, const void* k_ip, const void* v_ip, void* o, int ldo, int batch, int heads,
-                              int nq, int nk, int d, float qk_scale, float ip_scale, int dtype, void* stream) {
+namespace {
+
+template <bool MASK>
+int ip_attn_add_launch(const void* q, int ldq, const void* k_ip, const void* v_ip, void* o, int ldo, int batch, int heads, int nq,
+                       int nk, int d, float qk_scale, float ip_scale, const float* row_w, int dtype, void* stream) {
+  if (MASK && (!row_w || ((uintptr_t)row_w & 3))) return PP_ERR_BAD_ARG;
   if (!q || !k_ip || !v_ip || !o || !pp_dt_ok(dtype)) return PP_ERR_BAD_ARG;
   if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0 || d <= 0 || d % 8) return PP_ERR_BAD_ARG;
   if (d != 40 && d != 80 && d != 160) return PP_ERR_UNSUPPORTED;
@@ -194,13 +217,27 @@ extern "C" int pp_ip_attn_add(const void* q, int ldq, const void* k_ip, const vo
   a.span = G * a.L;
   a.R = 64 / a.span;
   a.qk_scale = qk_scale; a.ip_scale = ip_scale;
+  a.row_w = row_w;
   const int rows_per_wg = (IP_T / 64) * a.R * IP_ROWS;
   const dim3 grid((unsigned)((nq + rows_per_wg - 1) / rows_per_wg), (unsigned)(heads / G), (unsigned)batch);
   if (nk <= IP_NKR) {
-    PP_DT_SWITCH(dtype, hipLaunchKernelGGL((ip_attn_add_kernel<EDT, true>), grid, dim3(IP_T), 0, (hipStream_t)stream, a));
+    PP_DT_SWITCH(dtype, hipLaunchKernelGGL((ip_attn_add_kernel<EDT, true, MASK>), grid, dim3(IP_T), 0, (hipStream_t)stream, a));
   } else {
-    PP_DT_SWITCH(dtype, hipLaunchKernelGGL((ip_attn_add_kernel<EDT, false>), grid, dim3(IP_T), 0, (hipStream_t)stream, a));
+    PP_DT_SWITCH(dtype, hipLaunchKernelGGL((ip_attn_add_kernel<EDT, false, MASK>), grid, dim3(IP_T), 0, (hipStream_t)stream, a));
   }
   PP_CHECK_LAUNCH("ip_attn_add_kernel");
   return PP_OK;
+}
+
+}  // namespace
+
+extern "C" int pp_ip_attn_add(const void* q, int ldq, const void* k_ip, const void* v_ip, void* o, int ldo, int batch, int heads,
+                              int nq, int nk, int d, float qk_scale, float ip_scale, int dtype, void* stream) {
+  return ip_attn_add_launch<false>(q, ldq, k_ip, v_ip, o, ldo, batch, heads, nq, nk, d, qk_scale, ip_scale, nullptr, dtype, stream);
+}
+
+extern "C" int pp_ip_attn_add_masked(const void* q, int ldq, const void* k_ip, const void* v_ip, void* o, int ldo, int batch,
+                                     int heads, int nq, int nk, int d, float qk_scale, float ip_scale, const float* row_w,
+                                     int dtype, void* stream) {
+  return ip_attn_add_launch<true>(q, ldq, k_ip, v_ip, o, ldo, batch, heads, nq, nk, d, qk_scale, ip_scale, row_w, dtype, stream);
 }

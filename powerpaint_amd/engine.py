@@ -575,12 +575,18 @@ class Builder:
         return out
 
     def ip_attn_add(self, q: int, ldq: int, k_ip: int, v_ip: int, o: int, ldo: int, B: int, heads: int, nq: int, nk: int,
-                    d: int, scale):
+                    d: int, scale, row_w: int = 0):
         """IP-Adapter's image-prompt term added in place to a cross-attention output (csrc/ip_attn.hip): `scale` is a
         ctypes.c_float CELL handed over by value at every launch -- whoever owns it (NetRuntime.set_ip_scales) changes the
-        value of eager runs in place; a captured graph carries the value it was captured with."""
-        self.plan.add("ip_attn_add", self.lib.pp_ip_attn_add, q, ldq, k_ip, v_ip, o, ldo, B, heads, nq, nk, d,
-                      float(d) ** -0.5, scale, self.dt)
+        value of eager runs in place; a captured graph carries the value it was captured with.  row_w (ip_adapter_masks):
+        device pointer to the fp32 [nq] weights of the adapter's mask at this level -- the record is then the masked entry,
+        which READS them (NetRuntime.set_ip_masks rewrites them under a captured graph)."""
+        if row_w:
+            self.plan.add("ip_attn_add", self.lib.pp_ip_attn_add_masked, q, ldq, k_ip, v_ip, o, ldo, B, heads, nq, nk, d,
+                          float(d) ** -0.5, scale, row_w, self.dt)
+        else:
+            self.plan.add("ip_attn_add", self.lib.pp_ip_attn_add, q, ldq, k_ip, v_ip, o, ldo, B, heads, nq, nk, d,
+                          float(d) ** -0.5, scale, self.dt)
         self.plan.count("ip_attn_add", 4.0 * B * nq * nk * heads * d)
 
     def perceiver_attn(self, q: int, ldq: int, kv_x: int, ldkx: int, nx: int, kv_l: int, ldkl: int, nl: int, B: int, heads: int,
@@ -841,8 +847,10 @@ class _TransformerBlock:
             q = pb.linear(ln, rows, Cc, P[f"{tb}.attn2.to_q.weight"], Cc, name="linear", **kw)
             a = pb.attention(q, Cc, kv[0], kv[1], kv[2], kv[3], x.B, net.heads, hw, net._nctx, Cc // net.heads)
             # IP-Adapter: a += scale_i * softmax(q K_i^T / sqrt(d)) V_i per adapter, in place, in front of to_out
-            for (k_ip, v_ip, nk_ip), cell in zip(net.ip_kv.get(self.pre, ()), net.ip_scale_cells):
-                pb.ip_attn_add(q, Cc, k_ip, v_ip, a, Cc, x.B, net.heads, hw, nk_ip, Cc // net.heads, cell)
+            # (with ip_adapter_masks: times the adapter's per-row weights of this level, build_setup's ip_row_w)
+            row_w = net.ip_row_w[hw] if net.ip_row_w else [0] * len(net.ip_scale_cells)
+            for (k_ip, v_ip, nk_ip), cell, w in zip(net.ip_kv.get(self.pre, ()), net.ip_scale_cells, row_w):
+                pb.ip_attn_add(q, Cc, k_ip, v_ip, a, Cc, x.B, net.heads, hw, nk_ip, Cc // net.heads, cell, w)
             st = self.producer(rows)
             hs = pb.linear(a, rows, Cc, P[f"{tb}.attn2.to_out.weight"], Cc, P[f"{tb}.attn2.to_out.bias"], res1=hs,
                            row_stats_out=st, name="linear")
@@ -961,6 +969,7 @@ class SDNet:
         self.xa: Dict[str, XAttnFold] = {}                      # ... -> folded cross-attention operands (none: the chain)
         self.ip_kv: Dict[str, List[Tuple[int, int, int]]] = {}  # ... -> per IP-Adapter (K_i, V_i, tokens)
         self.ip_scale_cells: list = []                          # per IP-Adapter: its ctypes.c_float scale cell
+        self.ip_row_w: Dict[int, List[int]] = {}                # ip_adapter_masks: {queries of a level: weight buffer per adapter}
         self.ip_tok: List[Tuple[int, int]] = []                 # per IP-Adapter: (image tokens e_i, tokens per batch item)
         self.upfold: Dict[str, int] = {}                        # upsampler conv -> its sub-pixel folded weights
         self.cond_emb: Optional[Act] = None                     # (controlnet) the conditioning embedding
@@ -1600,7 +1609,7 @@ class SDNet:
 
     # ---------------------------------------------------------------- setup plan: step-invariant work
     def build_setup(self, pb: Builder, B: int, nctx: int, ehs: int, cond: Optional[Act] = None, *,
-                    hw0: Tuple[int, int], ip_in: Sequence[Tuple[int, int]] = (), ip_scales=()):
+                    hw0: Tuple[int, int], ip_in: Sequence[Tuple[int, int]] = (), ip_scales=(), ip_row_w=None):
         """Cross-attention K and V^T for every transformer from encoder_hidden_states (bf16 [B*nctx][ctx_dim] at
         `ehs`); for ControlNet also the conditioning embedding of `cond` (NHWC bf16 image).  hw0 = (H, W) of the latents the
         step plan will be built for (xattn_forms: which cross-attention operands are folded, and in which layout).
@@ -1611,8 +1620,11 @@ class SDNet:
         Plus adapter the entry is (pointer, n, S, latents pointer): the 16-bit hidden states [B n S][E rounded up to 64] and the adapter's latents
         repeated B n times [B n Q][dim] (NetRuntime.set_ip_embeds fills both), and e_i comes out of the Resampler
         (_resampler: 10 depth + 3 launches).  While
-        adapters are loaded every cross-attention is XAttnForm.CHAIN (self.xa stays empty): to_q -> attention -> to_out."""
+        adapters are loaded every cross-attention is XAttnForm.CHAIN (self.xa stays empty): to_q -> attention -> to_out.
+        ip_row_w (ip_adapter_masks bound): {queries per item of a cross-attention level: one fp32 [queries] buffer per adapter},
+        the per-row weights the step plan's masked pp_ip_attn_add launches read (NetRuntime.set_ip_masks fills them)."""
         self._nctx = nctx
+        self.ip_row_w = dict(ip_row_w or {})
         if len(ip_in) != len(self.ip) or len(ip_scales) != len(self.ip):
             raise L.PPError(f"{len(self.ip)} IP-Adapters are loaded, the setup plan was given {len(ip_in)} image-embed buffers")
         self.ip_kv, self.ip_scale_cells = {}, list(ip_scales)

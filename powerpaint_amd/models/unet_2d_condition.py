@@ -229,6 +229,27 @@ class UNet2DConditionModel(_HipModel):
                                 f"per adapter")
         return list(embeds)
 
+    def _check_ip_masks(self, masks):
+        """`cross_attention_kwargs["ip_adapter_masks"]` of diffusers 0.27: ONE float tensor [adapters, 1, H, W] (what
+        `IPAdapterMaskProcessor.preprocess` returns), shared by the batch and both CFG halves.  None passes; without a loaded
+        adapter the masks are refused, as an image prompt is -- never ignored."""
+        if masks is None:
+            return None
+        if not self.net.ip:
+            raise ValueError("`ip_adapter_masks` were given but no IP-Adapter is loaded: call `load_ip_adapter` first (the masks "
+                             "are never silently dropped)")
+        if not isinstance(masks, torch.Tensor) or masks.ndim != 4 or not masks.is_floating_point():
+            raise ValueError(" ip_adapter_mask should be a tensor with shape [num_ip_adapter, 1, height, width]."
+                             " Please use `IPAdapterMaskProcessor` to preprocess your mask")
+        if masks.shape[1] != 1:
+            raise ValueError(f"ip_adapter_masks should be a tensor with shape [num_ip_adapter, 1, height, width], got "
+                             f"{tuple(masks.shape)} (one mask per adapter: per-image masks are not implemented)")
+        if len(masks) != len(self.net.ip):
+            raise ValueError(f"Number of ip_adapter_masks ({len(masks)}) must match number of IP-Adapters ({len(self.net.ip)})")
+        if not bool(torch.isfinite(masks).all()):
+            raise ValueError("ip_adapter_masks hold non-finite values")
+        return masks
+
     # ------------------------------------------------------------------ FreeU (DESIGN.md "FreeU")
     def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
         """FreeU (https://arxiv.org/abs/2309.11497), the reference's `UNet2DConditionModel.enable_freeu`
@@ -263,9 +284,12 @@ class UNet2DConditionModel(_HipModel):
 
     def prepare(self, sample_shape, encoder_hidden_states, down_block_add_samples=None, mid_block_add_sample=None,
                 up_block_add_samples=None, down_block_additional_residuals=None, mid_block_additional_residual=None,
-                twin: bool = False, timestep_cond: Optional[torch.Tensor] = None, added_cond_kwargs=None):
+                twin: bool = False, timestep_cond: Optional[torch.Tensor] = None, added_cond_kwargs=None,
+                ip_adapter_masks: Optional[torch.Tensor] = None):
         """Compile (or reuse) the launch plan for this shape / residual wiring and bind the inputs.  added_cond_kwargs:
-        {"image_embeds": [...]} while IP-Adapters are loaded (_ip_image_embeds), copied in on every call.  timestep_cond: the
+        {"image_embeds": [...]} while IP-Adapters are loaded (_ip_image_embeds), copied in on every call.  ip_adapter_masks:
+        `cross_attention_kwargs["ip_adapter_masks"]` (_check_ip_masks) -- masked or not is part of the plan key, the values
+        are per-row weights in device memory, rewritten on every call (NetRuntime.set_ip_masks).  timestep_cond: the
         guidance embedding of a UNet with `time_cond_proj_dim` ([B or 1, d], one value over the batch; None = no term, as
         in diffusers) -- constant over a denoising call, folded into the time embedding's first bias once
         (NetRuntime.set_timestep_cond).  twin: the caller (the
@@ -277,11 +301,15 @@ class UNet2DConditionModel(_HipModel):
             raise ValueError(f"sample has {Cin} channels, unet.config.in_channels = {self.config.in_channels}")
         wiring = self._wiring(down_block_add_samples, mid_block_add_sample, up_block_add_samples,
                               down_block_additional_residuals, mid_block_additional_residual)
+        ip_masks = self._check_ip_masks(ip_adapter_masks)
         ip_embeds = self._ip_image_embeds(added_cond_kwargs, B)
         self.rt.ensure(B, H, W, self._nctx(encoder_hidden_states), Cin, wiring, twin=twin, freeu=self._freeu_values(),
-                       ip_n=[e.shape[1] if e.dim() == 3 else (e.shape[1], e.shape[2]) for e in ip_embeds] if ip_embeds else ())
+                       ip_n=[e.shape[1] if e.dim() == 3 else (e.shape[1], e.shape[2]) for e in ip_embeds] if ip_embeds else (),
+                       ip_masked=ip_masks is not None)
         if ip_embeds:
             self.rt.set_ip_embeds(ip_embeds)
+        if ip_masks is not None:
+            self.rt.set_ip_masks(ip_masks)
         if wiring[0] != "plain":
             groups = {"down": down_block_add_samples if wiring[0] == "brushnet" else down_block_additional_residuals,
                       "mid": [mid_block_add_sample if wiring[0] == "brushnet" else mid_block_additional_residual]}
@@ -331,7 +359,8 @@ class UNet2DConditionModel(_HipModel):
         self.merge_adapters((cross_attention_kwargs or {}).get("scale", 1.0))
         rt = self.prepare(tuple(sample.shape), encoder_hidden_states, down_block_add_samples, mid_block_add_sample,
                           up_block_add_samples, down_block_additional_residuals, mid_block_additional_residual,
-                          timestep_cond=timestep_cond, added_cond_kwargs=added_cond_kwargs)
+                          timestep_cond=timestep_cond, added_cond_kwargs=added_cond_kwargs,
+                          ip_adapter_masks=(cross_attention_kwargs or {}).get("ip_adapter_masks"))
         # the reference consumes the BrushNet lists destructively (.pop(0), unet_2d_condition.py:1223,1234,1318)
         for lst in (down_block_add_samples, up_block_add_samples):
             if isinstance(lst, list):

@@ -286,6 +286,13 @@ class PipelineBase(PipelinePretrainedMixin):
                 self.__dict__.pop("_prompt_memo", None)        # embeddings of the previous weights
         return s
 
+    def _refuse_ip_adapter_masks(self, cross_attention_kwargs):
+        """A pipeline without an IP-Adapter path: `cross_attention_kwargs["ip_adapter_masks"]` is refused, never dropped."""
+        if (cross_attention_kwargs or {}).get("ip_adapter_masks") is not None:
+            raise ValueError(f"{type(self).__name__} has no IP-Adapter path: `ip_adapter_masks` would confine an image prompt "
+                             f"that this pipeline never applies (StableDiffusionPowerPaintBrushNetPipeline takes them, after "
+                             f"`load_ip_adapter`)")
+
     def prepare_extra_step_kwargs(self, generator, eta):
         """pipeline_PowerPaint.py:536-551."""
         kw = {}

@@ -72,8 +72,11 @@ class DenoiseLoop:
     def bind(self, latents_shape, do_cfg: bool, guidance_scale: float, prompt_embeds, prompt_embeds_side=None,
              static_inputs=(), side_static_inputs=(), controlnet_cond=None, side_scale: float = 1.0,
              guess_mode: bool = False, eta: float = 0.0, generator=None, noise_dtype=torch.float32, blend=None,
-             timestep_cond=None, added_cond_kwargs=None):
+             timestep_cond=None, added_cond_kwargs=None, ip_adapter_masks=None):
         """Compile the per-step program.  latents_shape = (B, 4, h, w) of the *un-duplicated* latents.
+        ip_adapter_masks: `cross_attention_kwargs["ip_adapter_masks"]` of the call, [adapters, 1, H, W]; the UNet only, as the
+        image embeds.  Their values are device memory the UNet's launches read (NetRuntime.set_ip_masks): new masks of the
+        same count reach a captured graph without a re-capture.
         added_cond_kwargs: {"image_embeds": [...]} of a UNet with IP-Adapters (pipeline_PowerPaint_Brushnet_CA.py:1363-1366,
         1430-1441: the UNet only, never the side network); copied in and projected once per call (NetRuntime.set_ip_embeds).
         blend = (image_latents [1,4,h,w], mask [1,1,h,w], noise [B,4,h,w]): the `num_channels_unet == 4` branch of the
@@ -122,7 +125,7 @@ class DenoiseLoop:
         multi = nets is not None and len(nets) > 1
         rt, side_rt, side_rts = self._prepare_runtimes(
             latents_shape, Be, Bs, do_cfg, half, guess_mode, nets, side, prompt_embeds, prompt_embeds_side, static_inputs,
-            side_static_inputs, controlnet_cond, side_scale, timestep_cond, added_cond_kwargs)
+            side_static_inputs, controlnet_cond, side_scale, timestep_cond, added_cond_kwargs, ip_adapter_masks)
         if self.foreign:
             ts, step, src, mp = self._foreign_state(latents_shape, do_cfg, guidance_scale)
         else:
@@ -193,7 +196,7 @@ class DenoiseLoop:
 
     def _prepare_runtimes(self, latents_shape, Be, Bs, do_cfg, half, guess_mode, nets, side, prompt_embeds,
                           prompt_embeds_side, static_inputs, side_static_inputs, controlnet_cond, side_scale, timestep_cond,
-                          added_cond_kwargs):
+                          added_cond_kwargs, ip_adapter_masks=None):
         """-> (rt, side_rt, side_rts): every network prepared, the UNet wired to the side residuals, static channels loaded.
         The CFG pair is built here, as `cat([latents] * 2)` (pipeline_PowerPaint.py:990): where every other network input
         is CFG-duplicated as well, the two halves of a forward pass are identical until the prompt enters and the
@@ -245,6 +248,8 @@ class DenoiseLoop:
             wiring_kw["timestep_cond"] = timestep_cond
         if added_cond_kwargs is not None:
             wiring_kw["added_cond_kwargs"] = added_cond_kwargs
+        if ip_adapter_masks is not None:
+            wiring_kw["ip_adapter_masks"] = ip_adapter_masks
         rt = self.unet.prepare((Be, self.unet.config.in_channels, h, w), prompt_embeds, twin=twin_u, **wiring_kw)
         # one-time (per call) static channels of the UNet / side inputs
         rt.load_input(list(static_inputs))

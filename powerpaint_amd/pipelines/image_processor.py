@@ -218,3 +218,46 @@ class VaeImageProcessor:
             return image
         arr = self.pt_to_numpy(image)
         return arr if output_type == "np" else self.numpy_to_pil(arr)
+
+
+class IPAdapterMaskProcessor(VaeImageProcessor):
+    """diffusers-0.27 `IPAdapterMaskProcessor`: `preprocess(masks, height=, width=)` turns PIL images / arrays / tensors into
+    the binary [n, 1, H, W] tensor that `cross_attention_kwargs={"ip_adapter_masks": ...}` takes (grey, Lanczos resize,
+    >= 0.5 -> 1), and the static `downsample` is the rule by which one adapter's mask becomes one weight per query row of a
+    cross-attention level -- the ONE implementation of it: NetRuntime.set_ip_masks fills the kernels' weight buffers with it."""
+
+    def __init__(self, do_resize: bool = True, vae_scale_factor: int = 8, resample: str = "lanczos",
+                 do_normalize: bool = False, do_binarize: bool = True, do_convert_grayscale: bool = True):
+        super().__init__(do_resize=do_resize, vae_scale_factor=vae_scale_factor, resample=resample,
+                         do_normalize=do_normalize, do_binarize=do_binarize, do_convert_grayscale=do_convert_grayscale)
+
+    @staticmethod
+    def downsample(mask: torch.Tensor, batch_size: int, num_queries: int, value_embed_dim: int) -> torch.Tensor:
+        """mask [1, H, W] -> [batch_size, num_queries, value_embed_dim]: a bicubic resize (unclamped: a binary mask rings to
+        about -0.094 and 1.094) to the grid of the mask's OWN aspect ratio that holds num_queries positions, flattened in row
+        order; a grid with fewer positions is padded with zeros at the end, one with more is cut (a warning each)."""
+        import math
+        import warnings
+        o_h, o_w = mask.shape[1], mask.shape[2]
+        ratio = o_w / o_h
+        mask_h = int(math.sqrt(num_queries / ratio))
+        if mask_h < 1:
+            raise ValueError(f"a {o_h}x{o_w} mask has no grid of {num_queries} positions (its aspect ratio leaves no row)")
+        mask_h = int(mask_h) + int((num_queries % int(mask_h)) != 0)
+        mask_w = num_queries // mask_h
+        m = torch.nn.functional.interpolate(mask.unsqueeze(0), size=(mask_h, mask_w), mode="bicubic").squeeze(0)
+        if batch_size < m.shape[0]:
+            m = m[:batch_size]
+        elif batch_size > m.shape[0]:
+            m = m.repeat(batch_size, 1, 1)
+        m = m.view(m.shape[0], -1)
+        area = mask_h * mask_w
+        if area < num_queries:
+            warnings.warn("The aspect ratio of the mask does not match the aspect ratio of the output image. "
+                          "Please update your masks or adjust the output size for optimal performance.", UserWarning)
+            m = torch.nn.functional.pad(m, (0, num_queries - m.shape[1]), value=0.0)
+        if area > num_queries:
+            warnings.warn("The aspect ratio of the mask does not match the aspect ratio of the output image. "
+                          "Please update your masks or adjust the output size for optimal performance.", UserWarning)
+            m = m[:, :num_queries]
+        return m.reshape(m.shape[0], m.shape[1], 1).repeat(1, 1, value_embed_dim)

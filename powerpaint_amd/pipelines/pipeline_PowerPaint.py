@@ -76,6 +76,7 @@ class StableDiffusionInpaintPipeline(PipelineBase):
                  callback_steps: int = 1, cross_attention_kwargs: Optional[Dict[str, Any]] = None, task_class=None,
                  masked_image_latents: Optional[torch.FloatTensor] = None,
                  mask_latents: Optional[torch.FloatTensor] = None):
+        self._refuse_ip_adapter_masks(cross_attention_kwargs)
         if task_class is not None:
             raise NotImplementedError("task_class is not used by the released checkpoints")
         height = height or self.unet.config.sample_size * self.vae_scale_factor

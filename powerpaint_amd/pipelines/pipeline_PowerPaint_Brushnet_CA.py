@@ -128,7 +128,8 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
         raises there too).  Without it, register a duck-typed `image_encoder` and `feature_extractor` yourself, or pass
         `ip_adapter_image_embeds`."""
         if kwargs.get("ip_adapter_masks") is not None:
-            raise L.PPError("load_ip_adapter: ip_adapter_masks are not implemented on the HIP path")
+            raise L.PPError("load_ip_adapter takes no ip_adapter_masks (diffusers' does not either): hand them to the call, "
+                            "pipe(..., cross_attention_kwargs={\"ip_adapter_masks\": IPAdapterMaskProcessor().preprocess(...)})")
         srcs = pretrained_model_name_or_path_or_dict
         srcs = list(srcs) if isinstance(srcs, (list, tuple)) else [srcs]
         if image_encoder_folder is not None:
@@ -271,6 +272,14 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
         callback = kwargs.pop("callback", None)
         callback_steps = kwargs.pop("callback_steps", 1)
         self._check_ip_inputs(ip_adapter_image, ip_adapter_image_embeds)
+        # `cross_attention_kwargs` reaches the UNet only (:1430-1441): its `ip_adapter_masks` confine each adapter's image
+        # prompt to a region (checked here, before anything runs; never dropped)
+        ip_adapter_masks = (cross_attention_kwargs or {}).get("ip_adapter_masks")
+        if ip_adapter_masks is not None:
+            self.unet._check_ip_masks(ip_adapter_masks)
+            if ip_adapter_image is None and ip_adapter_image_embeds is None:
+                raise ValueError("`ip_adapter_masks` confine an image prompt: pass `ip_adapter_image` or "
+                                 "`ip_adapter_image_embeds` with them")
         if isinstance(control_guidance_start, list):
             control_guidance_start = control_guidance_start[0]
         if isinstance(control_guidance_end, list):
@@ -359,7 +368,7 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
                         side_static_inputs=[(conditioning_latents, self.unet.config.in_channels)],
                         side_scale=scales[0], guess_mode=guess_mode, eta=eta, generator=generator,
                         noise_dtype=self._noise_dtype(prompt_embeds), timestep_cond=timestep_cond,
-                        added_cond_kwargs=added_cond_kwargs)
+                        added_cond_kwargs=added_cond_kwargs, ip_adapter_masks=ip_adapter_masks)
         cb = None
         bad = [k for k in callback_on_step_end_tensor_inputs if k not in self._callback_tensor_inputs]
         if bad:                                                                              # check_inputs, :775-780

@@ -115,6 +115,7 @@ class StableDiffusionControlNetInpaintPipeline(StableDiffusionInpaintPipeline):
                  control_guidance_end: Union[float, List[float]] = 1.0,
                  masked_image_latents: Optional[torch.FloatTensor] = None,
                  mask_latents: Optional[torch.FloatTensor] = None):
+        self._refuse_ip_adapter_masks(cross_attention_kwargs)
         multi = isinstance(self.controlnet, MultiControlNetModel)
         if multi:
             n_nets = len(self.controlnet.nets)

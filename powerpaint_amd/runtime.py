@@ -78,8 +78,36 @@ class NetRuntime:
             dst.copy_(e.reshape(self.B * n, D).to(self.device))
         self._ctx_id = None
 
+    def _xattn_queries(self, H: int, W: int) -> List[int]:
+        """The distinct query counts per batch item (h * w) of the levels that hold a cross-attention, largest first."""
+        n = len(self.net.boc)
+        sizes = level_sizes(H, W, n)
+        out = set()
+        for pre, _ in self.net._attn_specs():
+            part = pre.split(".")
+            lvl = n - 1 if part[0] == "mid_block" else (int(part[1]) if part[0] == "down_blocks" else n - 1 - int(part[1]))
+            out.add(sizes[lvl][0] * sizes[lvl][1])
+        return sorted(out, reverse=True)
+
+    def set_ip_masks(self, masks: torch.Tensor):
+        """`ip_adapter_masks` [adapters, 1, H, W] -> the per-row weights the masked pp_ip_attn_add launches read: per adapter
+        and distinct query count, IPAdapterMaskProcessor.downsample(mask_i, 1, nq, 1) (host torch: a few small bicubic
+        resizes per call) written into the plan's fp32 buffers.  Stream-ordered writes to memory the kernels READ: eager runs
+        and replays of a captured graph queued after this call see the new values, nothing is re-captured."""
+        from .pipelines.image_processor import IPAdapterMaskProcessor
+        bufs = self.lay.get("ip_row_w")
+        if not bufs:
+            raise L.PPError("set_ip_masks: the plan was built without ip_adapter_masks (NetRuntime.ensure(ip_masked=True))")
+        if len(masks) != len(self.net.ip):
+            raise ValueError(f"Number of ip_adapter_masks ({len(masks)}) must match number of IP-Adapters ({len(self.net.ip)})")
+        m = masks.detach().to(device="cpu", dtype=torch.float32)
+        for nq, ptrs in bufs.items():
+            for i, ptr in enumerate(ptrs):
+                w = IPAdapterMaskProcessor.downsample(m[i], 1, nq, 1).reshape(nq)
+                self.arena.view(ptr, (nq,), torch.float32).copy_(w)
+
     def _build(self, arena: Arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond=False, twin=False,
-               freeu=False, ip_n=()):
+               freeu=False, ip_n=(), ip_masked=False):
         net = self.net
         pb_setup = Builder(arena, dtype=net.dtype)
         pb_setup.gemm_tile, pb_setup.gemm_splitk = self.gemm_tile, self.gemm_splitk
@@ -125,6 +153,10 @@ class NetRuntime:
                 else:
                     lay["ip_in"].append((arena.alloc(B * n * _align(D, 64) * 2), n))
             ip_kw = dict(ip_in=lay["ip_in"], ip_scales=self._ip_cells(len(net.ip)))
+            if ip_masked:
+                # ip_adapter_masks: fp32 [nq] per adapter and distinct query count; the transformers of a level share it
+                lay["ip_row_w"] = {nq: [arena.alloc(nq * 4) for _ in net.ip] for nq in self._xattn_queries(H, W)}
+                ip_kw["ip_row_w"] = lay["ip_row_w"]
         net.build_setup(pb_setup, B, nctx, lay["ehs"], cond, hw0=(H, W), **ip_kw)
         pb = Builder(arena, dtype=net.dtype)
         pb.gemm_tile, pb.gemm_splitk = self.gemm_tile, self.gemm_splitk
@@ -188,11 +220,14 @@ class NetRuntime:
         return out
 
     def ensure(self, B: int, H: int, W: int, nctx: int, cin_total: int, wiring=("plain",), cond_hw=None,
-               scale: float = 1.0, pad_uncond: bool = False, twin: bool = False, freeu=None, ip_n=()):
+               scale: float = 1.0, pad_uncond: bool = False, twin: bool = False, freeu=None, ip_n=(),
+               ip_masked: bool = False):
         """freeu: None, or (s1, s2, b1, b2) of UNet2DConditionModel.enable_freeu -- on / off is part of the plan key (the
         plan gains one pp_freeu launch per resnet of up blocks 0 and 1), the values live in device memory the launches read.
         ip_n: images per loaded IP-Adapter in this call's embeds, (images, hidden states per image) for a Plus adapter (part of
         the key only while adapters are loaded).
+        ip_masked: `ip_adapter_masks` are bound (all adapters or none, as in diffusers 0.27) -- every pp_ip_attn_add launch is
+        then the masked entry, reading per-row weights that set_ip_masks fills; part of the key, the values are not.
         twin: the caller vouches that the second half of every network input (x_in, ControlNet conditioning) equals the
         first -- a CFG pair built from one tensor; the step plan then runs the prompt-independent prefix on one half
         (SDNet.build_step)."""
@@ -205,7 +240,10 @@ class NetRuntime:
                bool(twin)) + (("freeu",) if freeu is not None else ())      # (without FreeU: the key of a plan that never had it)
         ip = getattr(getattr(self, "net", None), "ip", None)
         if ip:
-            key += (("ip", tuple(ip), tuple(tuple(int(v) for v in n) if isinstance(n, (tuple, list)) else int(n) for n in ip_n)),)
+            key += (("ip", tuple(ip), tuple(tuple(int(v) for v in n) if isinstance(n, (tuple, list)) else int(n) for n in ip_n),
+                     bool(ip_masked)),)
+        elif ip_masked:
+            raise L.PPError("ip_adapter_masks need a loaded IP-Adapter")
         if isinstance(scale, (list, tuple)):
             scale = tuple(float(v) for v in scale)       # (one representation: a list never equals the stored tuple)
         if key == self.key:
@@ -217,10 +255,12 @@ class NetRuntime:
         #  workgroups placed on the XCDs round-robin by linear id?  Plans combine split-K in-kernel only if so.)
         self.xcd_placement_ok = bool(self.lib.pp_xcd_placement_ok())
         dry = Arena()
-        self._build(dry, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None, ip_n)
+        self._build(dry, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None, ip_n,
+                    bool(ip_masked))
         self.arena = Arena(_align(dry.peak, 4096), self.device)
         self.lay, self.setup_plan, self.step_plan, self.outputs = self._build(
-            self.arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None, ip_n)
+            self.arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None, ip_n,
+            bool(ip_masked))
         self.twin = bool(twin)
         self.pad_uncond = bool(pad_uncond)
         self.key = key
