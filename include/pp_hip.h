@@ -917,6 +917,53 @@ int pp_ip_attn_add_masked(const void* q, int ldq, const void* k_ip, const void* 
 int pp_perceiver_attn(const void* q, int ldq, const void* kv_x, int ldkx, int nx, const void* kv_l, int ldkl, int nl, void* o,
                       int ldo, int batch, int heads, int nq, int d, float scale, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Token merging (added under ABI 29: purely additive).  ToMe for Stable Diffusion (Bolya & Hoffman 2023; tomesd's
+ * bipartite_soft_matching_random2d) in front of a self-attention: the r most redundant tokens of an h x w grid are averaged
+ * into their most similar DESTINATION token, attention runs on n - r rows, and its output is copied back out to all n.
+ *   geometry   : n = h*w tokens per batch item in row-major order; one token of every sy x sx window (hsy = h / sy rows of
+ *                wsx = w / sx windows, integer division) is a destination, nd = hsy*wsx of them; every other token -- the
+ *                leftover rows and columns of sizes that are no multiple of the window included -- is a source.
+ *   table      : uint8 rows of >= nd entries (row stride table_row_stride bytes, table_rows rows): entry i*wsx + j of a row is
+ *                the in-window index k of the destination of window (i, j), token (i*sy + k / sx, j*sx + k % sx).  A value
+ *                >= sx*sy is read as sx*sy - 1.
+ *   row_idx    : DEVICE pointer to one int32, the table row to use, clamped to [0, table_rows) -- read by the kernel, so a
+ *                captured graph follows a device-side step counter with no re-capture.  NULL: row 0.
+ *   merged sequence (n - r rows): the kept sources in ascending token order, then the destinations in ascending token order.
+ * pp_tome_supported: 1 where the four entries run the geometry (h, w >= 2, at least one window, sx*sy <= 256,
+ * n <= PP_TOME_MAX_TOKENS, C a positive multiple of 8), else 0; they return PP_ERR_UNSUPPORTED there and launch nothing.
+ *
+ * pp_tome_match: x 16-bit [batch*n][C] (row stride ldx >= C, a multiple of 8; 16-byte aligned), the hidden state the matching
+ *   is computed from.  best_dst int32 [batch][n], score fp32 [batch][n]: per SOURCE token the destination token with the
+ *   highest cosine and that cosine; an equal maximum goes to the lower destination token.  Destination tokens get
+ *   best_dst = -1 and score = -2.  The dot products are accumulated in fp32 on the matrix cores from the 16-bit values; the
+ *   inverse norms are fp32 (1 / sqrt of the fp32 sum of squares of the same values; a zero row has inverse norm 0, cosine 0).
+ * pp_tome_select: the r sources with the highest score are merged (an equal score goes to the lower token), 0 <= r <= n - nd.
+ *   pos    int32 [batch][n]      merged-sequence row of every token (a merged source: the row of its destination)
+ *   rowtok int32 [batch][n - r]  the token a merged-sequence row starts from (the kept source, or the destination)
+ *   seg    int32 [batch][nd + 1] list bounds: the sources merged into the destination of rank d are lst[seg[d] .. seg[d+1])
+ *   lst    int32 [batch][r]      merged source tokens, grouped by destination rank, ascending token order inside a group
+ * pp_tome_merge: qk 16-bit rows [batch*n][2C] (row stride ldqk) and vt 16-bit [batch][C][ldvt] (V transposed, ldvt >= n) ->
+ *   qk_out [batch*(n - r)][2C] (row stride ldqk_out) and vt_out [batch][C][ldvt_out], ldvt_out >= round8(n - r) a multiple of 8, the
+ *   columns [n - r, round8(n - r)) written as zeros (what pp_attention_fwd may read), none behind them.  A destination row is the mean of itself and its list (fp32 sum in list order,
+ *   one division, ONE rounding to `dtype`); every other row is copied.  Outputs must not alias inputs.
+ * pp_tome_unmerge: out[b][t][0:C] = a[b][pos[b][t]][0:C], 16-bit rows (a: nm = n - r rows per item, row stride lda; out: n rows,
+ *   row stride ldo); a pos outside [0, nm) is clamped.
+ * Leading dimensions of row buffers are multiples of 8 and their pointers 16-byte aligned; int32 / fp32 buffers 4-byte
+ * aligned (PP_ERR_BAD_ARG otherwise).  Nothing outside the stated outputs is written (the gaps of a padded leading dimension
+ * included).  No floating-point atomics: the same inputs give the same bits on every run. */
+#define PP_TOME_MAX_TOKENS 16384
+int pp_tome_supported(int h, int w, int C, int sx, int sy);
+int pp_tome_match(const void* x, int ldx, int batch, int h, int w, int C, int sx, int sy, const void* table,
+                  int table_row_stride, int table_rows, const void* row_idx, void* best_dst, void* score, int dtype,
+                  void* stream);
+int pp_tome_select(const void* best_dst, const void* score, int batch, int n, int nd, int r, void* pos, void* rowtok, void* seg,
+                   void* lst, void* stream);
+int pp_tome_merge(const void* qk, int ldqk, const void* vt, int ldvt, int batch, int n, int C, int nd, int r, const void* rowtok,
+                  const void* seg, const void* lst, void* qk_out, int ldqk_out, void* vt_out, int ldvt_out, int dtype,
+                  void* stream);
+int pp_tome_unmerge(const void* a, int lda, const void* pos, int batch, int n, int nm, int C, void* out, int ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,7 @@ def conv3x3_args(dtype: int, B: int, H: int, W: int, c1: int, cout: int, x, x2=N
 
 PP_LORA_MAX_ADAPTERS, PP_LORA_MAX_RANK = 8, 128
 PP_LORA_ROWS_PLAIN, PP_LORA_ROWS_GEGLU = 0, 1
+PP_TOME_MAX_TOKENS = 16384            # tokens per batch item the pp_tome_* entries take (include/pp_hip.h)
 PP_IP_MAX_TOKENS = 64                 # image tokens per adapter pp_ip_attn_add takes (include/pp_hip.h)
 PP_LORA_COLS_PLAIN, PP_LORA_COLS_IGEMM, PP_LORA_COLS_KPERM, PP_LORA_COLS_KPERM_GEGLU = 0, 1, 2, 3
 
@@ -191,6 +192,13 @@ SIGNATURES = {
                                         vp, C.c_int, vp]),
     "pp_perceiver_attn": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, f32, C.c_int, vp]),
+    "pp_tome_supported": (C.c_int, [C.c_int] * 5),
+    "pp_tome_match": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp,
+                                vp, C.c_int, vp]),
+    "pp_tome_select": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "pp_tome_merge": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int,
+                                vp, C.c_int, C.c_int, vp]),
+    "pp_tome_unmerge": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
 }
 
 _lib = None

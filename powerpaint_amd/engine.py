@@ -13,6 +13,7 @@ Design (MI355X-first):
 """
 import ctypes as C
 import enum
+import math
 import os
 from dataclasses import dataclass
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
@@ -712,6 +713,29 @@ class PackVec:
     keys: Tuple[str, ...]
 
 
+class ToMe(NamedTuple):
+    """Token merging in front of the self-attentions (powerpaint_amd/tome.py, DESIGN.md "Token merging"): tomesd's arguments.
+    Part of a plan's key; the window draws are data."""
+    ratio: float
+    max_downsample: int
+    sx: int
+    sy: int
+    use_rand: bool
+
+
+class ToMeBlock(NamedTuple):
+    """One transformer whose self-attention runs on merged tokens: its grid, the destinations nd, the merged sources r and
+    the offset of its windows inside a row of the window table."""
+    h: int
+    w: int
+    nd: int
+    r: int
+    offset: int
+
+
+TOME_TABLE_ROWS = 1000       # network evaluations of one pipeline call the window table holds
+
+
 class XAttnForm(enum.Enum):
     """How the cross-attention sub-block of a transformer (norm2 -> to_q -> attention over the prompt -> to_out + residual)
     runs.  SDNet.xattn_form decides; the value is the `kperm` pp_xattn_fold lays the folded operands out with."""
@@ -775,13 +799,14 @@ class _TransformerBlock:
                 qk = pb.alloc(rows * 2 * Cc * 2)
                 # (round 5) Q leaves the front end as Q * d^-0.5 * log2(e) where the pipelined attention kernel covers the
                 # shape: its scores then come out of the MFMA as exp2 arguments (PP_ATTN_PIPE_LOG2)
-                log2q = bool(net.attn_log2 and pb.lib.pp_attention_log2_ok(hw, hw, d))
+                n_att = hw - self.tome_r()                       # (token merging: attention runs on the merged rows)
+                log2q = bool(net.attn_log2 and pb.lib.pp_attention_log2_ok(n_att, n_att, d))
                 pb.plan.add("tfront", pb.lib.pp_tfront, x.ptr, Cc, acc, P[f"{pre}.norm.weight"], P[f"{pre}.norm.bias"], 1e-6,
                             net.groups, P[f"{pre}.proj_in.weight"], P[f"{pre}.proj_in.bias"],
                             P[f"{tb}.attn1.qkv.weight_kp"], P[f"{tb}.attn1.qkv.colsum"], P[f"{tb}.attn1.qkv.bias"], 1e-5, hs, Cc,
                             qk, 2 * Cc, vt, hw, rows, Cc, hw, (float(d) ** -0.5) * 1.4426950408889634 if log2q else 1.0, pb.dt)
                 pb.plan.count("tfront", 2.0 * rows * Cc * Cc + 2.0 * rows * 3 * Cc * Cc)     # (proj_in + QKV)
-                return hs, pb.attention(qk, 2 * Cc, qk + 2 * Cc, 2 * Cc, vt, hw, x.B, net.heads, hw, hw, d, log2q=log2q)
+                return hs, self.attend(hs, qk, 2 * Cc, vt, hw, log2q=log2q)
         st = self.producer(rows)
         n = pb.groupnorm(x, P[f"{pre}.norm.weight"], P[f"{pre}.norm.bias"], 1e-6, False, groups=net.groups)
         hs = pb.linear(n.ptr, rows, Cc, P[f"{pre}.proj_in.weight"], Cc, P[f"{pre}.proj_in.bias"], row_stats_out=st,
@@ -791,13 +816,45 @@ class _TransformerBlock:
             vt = pb.alloc(x.B * Cc * hw * 2)
             qk = pb.linear(ln, rows, Cc, P[f"{tb}.attn1.qkv.weight"], 3 * Cc, out_vt=vt, vt_col0=2 * Cc, vt_ld=hw,
                            rows_per_batch=hw, name="linear", **kw)
-            return hs, pb.attention(qk, 2 * Cc, qk + 2 * Cc, 2 * Cc, vt, hw, x.B, net.heads, hw, hw, d)
+            return hs, self.attend(hs, qk, 2 * Cc, vt, hw)
         # tiny latents (hw < 8, e.g. 2x2): V^T rows must be 16-byte aligned and zero padded -> unfused transpose
         ldvt = _align(hw, 8)
         vt = pb.alloc(x.B * Cc * ldvt * 2)
         qkv = pb.linear(ln, rows, Cc, P[f"{tb}.attn1.qkv.weight"], 3 * Cc, name="linear", **kw)
         pb.plan.add("transpose_v", pb.lib.pp_transpose_v, qkv + 4 * Cc, 3 * Cc, x.B, hw, Cc, vt, ldvt)
-        return hs, pb.attention(qkv, 3 * Cc, qkv + 2 * Cc, 3 * Cc, vt, ldvt, x.B, net.heads, hw, hw, d)
+        return hs, self.attend(hs, qkv, 3 * Cc, vt, ldvt)
+
+    def tome_r(self) -> int:
+        """Sources this block merges in front of its self-attention (0: none -- SDNet.tome_layout decides)."""
+        tm = self.net._tome_step
+        return tm["layout"][self.pre].r if tm and self.pre in tm["layout"] else 0
+
+    def attend(self, hs: int, qk: int, ldqk: int, vt: int, ldvt: int, log2q: bool = False) -> int:
+        """attn1 over Q | K rows (row stride ldqk elements, K behind Q) and V^T.  With token merging on this block: match on
+        hs, select, merge Q | K and V^T, attention on n - r rows, unmerge -- merging is a mean and the projections are affine,
+        so the merged rows of Q, K, V are the projections of the merged tokens, and what reads the output stays as it is."""
+        net, pb, x = self.net, self.pb, self.x
+        Cc, hw, B, d = x.C, self.hw, x.B, x.C // net.heads
+        r = self.tome_r()
+        if not r:
+            return pb.attention(qk, ldqk, qk + 2 * Cc, ldqk, vt, ldvt, B, net.heads, hw, hw, d, log2q=log2q)
+        tm, lib = net._tome_step, pb.lib
+        blk, t = tm["layout"][self.pre], net.tome
+        nm, ldvt2 = hw - r, _align(hw - r, 8)
+        best, score, pos = tm["bufs"][self.pre]
+        tm.setdefault("batch", {})[self.pre] = B          # (NetRuntime.tome_decisions: one CFG half under the twin prefix)
+        rowtok, seg, lst = pb.alloc(B * nm * 4), pb.alloc(B * (blk.nd + 1) * 4), pb.alloc(B * r * 4)
+        qk2, vt2 = pb.alloc(B * nm * 2 * Cc * 2), pb.alloc(B * Cc * ldvt2 * 2)
+        a2, a = pb.alloc(B * nm * Cc * 2), pb.alloc(B * hw * Cc * 2)
+        pb.plan.add("tome_match", lib.pp_tome_match, hs, Cc, B, x.H, x.W, Cc, t.sx, t.sy, tm["table"] + blk.offset, tm["stride"],
+                    tm["rows"], tm["row"], best, score, pb.dt)
+        pb.plan.count("tome_match", 2.0 * B * hw * blk.nd * Cc)
+        pb.plan.add("tome_select", lib.pp_tome_select, best, score, B, hw, blk.nd, r, pos, rowtok, seg, lst)
+        pb.plan.add("tome_merge", lib.pp_tome_merge, qk, ldqk, vt, ldvt, B, hw, Cc, blk.nd, r, rowtok, seg, lst, qk2, 2 * Cc, vt2,
+                    ldvt2, pb.dt)
+        pb.attention(qk2, 2 * Cc, qk2 + 2 * Cc, 2 * Cc, vt2, ldvt2, B, net.heads, nm, nm, d, out=a2, ldo=Cc, log2q=log2q)
+        pb.plan.add("tome_unmerge", lib.pp_tome_unmerge, a2, Cc, pos, B, hw, nm, Cc, a, Cc)
+        return a
 
     def cross_attention(self, hs: int, a: int, xa: Optional[XAttnFold], kv: Tuple[int, int, int, int]) -> Tuple[int, int]:
         """attn1.to_out + residual, then the cross-attention sub-block in the form build_setup resolved (xa: its folded
@@ -1013,6 +1070,36 @@ class SDNet:
                 if t == "CrossAttnUpBlock2D":
                     out += [(f"up_blocks.{i}.attentions.{j}", rev[i]) for j in range(self.L + 1)]
         return out
+
+    _tome_step: Optional[Dict[str, object]] = None
+    tome: Optional[ToMe] = None      # token merging (powerpaint_amd/tome.py: apply_patch / remove_patch)
+
+    def tome_layout(self, H: int, W: int) -> Tuple[Dict[str, ToMeBlock], int]:
+        """THE place that decides which transformers merge tokens, and how many: -> ({prefix: ToMeBlock} in execution order,
+        bytes of one row of the window table).  tomesd's rules: a block takes part when ceil(sqrt(orig_tokens // tokens)) <=
+        max_downsample; r = int(tokens * ratio), capped at the number of source tokens; r == 0 leaves the block untouched."""
+        t = self.tome
+        if t is None:
+            return {}, 0
+        n = len(self.boc)
+        sizes = level_sizes(H, W, n)
+        out, off = {}, 0
+        for pre, c in self._attn_specs():
+            part = pre.split(".")
+            lvl = n - 1 if part[0] == "mid_block" else (int(part[1]) if part[0] == "down_blocks" else n - 1 - int(part[1]))
+            h, w = sizes[lvl]
+            if math.ceil(math.sqrt((H * W) // (h * w))) > t.max_downsample:
+                continue
+            nd = (h // t.sy) * (w // t.sx)
+            r = min(int(h * w * t.ratio), h * w - nd)
+            if r <= 0:
+                continue
+            if nd < 1 or not L.lib().pp_tome_supported(h, w, c, t.sx, t.sy):
+                raise L.PPError(f"token merging: {pre} ({h}x{w} tokens of {c} channels, {t.sy}x{t.sx} windows) is outside what the "
+                                f"pp_tome kernels take (include/pp_hip.h, pp_tome_supported)")
+            out[pre] = ToMeBlock(h, w, nd, r, off)
+            off += nd
+        return out, _align(off, 16)
 
     def _zero_conv_specs(self) -> List[Tuple[str, int]]:
         """(state-dict prefix, channels) of the 1x1 output convs (BrushNet 12+1+15, ControlNet 12+1)."""
@@ -1718,7 +1805,7 @@ class SDNet:
     def build_step(self, pb: Builder, x_in: Act, t_dev: int, add_down: Optional[List[int]] = None,
                    add_mid: int = 0, add_up: Optional[List[int]] = None, ctrl_down: Optional[List[int]] = None,
                    ctrl_mid: int = 0, scale: float = 1.0, pad_uncond: bool = False, twin: bool = False,
-                   freeu: int = 0, b1_eff: int = 0) -> Dict[str, object]:
+                   freeu: int = 0, b1_eff: int = 0, tome: Optional[Dict[str, object]] = None) -> Dict[str, object]:
         """Append one forward pass.  x_in: NHWC bf16 input (already channel-concatenated).  Returns outputs:
         unet -> {"eps": ptr fp32 NCHW}; brushnet -> {"down": [Act], "mid": Act, "up": [Act]}; controlnet likewise.
         pad_uncond (side networks): the pipelines' guess mode runs the side branch on the conditional half of a CFG pair
@@ -1743,6 +1830,10 @@ class SDNet:
         P, lib = self.P, pb.lib
         B, H, W = x_in.B, x_in.H, x_in.W
         boc = self.boc
+        # token merging (NetRuntime._build): layout (tome_layout), the window table (pointer, row stride, rows), the cell that
+        # holds the pointer to the device word naming the row, per block the persistent (best_dst, score, pos) buffers, and
+        # (filled in here) the batch each block runs on
+        self._tome_step = tome
         brush = add_down is not None
         add_down = list(add_down) if brush else None
         add_up = list(add_up) if brush else None

@@ -719,3 +719,54 @@ def tfront(x: torch.Tensor, acc: torch.Tensor, gamma, beta, w1: torch.Tensor, b1
                               vt.stride(1), M, c, rows_per_batch,
                               float(q_scale), L.dtype_code(x.dtype), _s()), "pp_tfront")
     return hs, qk, vt
+
+
+# ---- token merging (csrc/tome.hip; include/pp_hip.h, "Token merging") --------------------------------------------------------
+def tome_supported(h: int, w: int, C: int, sx: int = 2, sy: int = 2) -> bool:
+    return bool(L.lib().pp_tome_supported(h, w, C, sx, sy))
+
+
+def tome_match(x: torch.Tensor, batch: int, h: int, w: int, table: torch.Tensor, sx: int = 2, sy: int = 2, row_idx=None,
+               best=None, score=None):
+    """pp_tome_match: x 16-bit [batch*h*w, C] (row stride free); table uint8 [rows, >= hsy*wsx] on the device; row_idx: int32
+    device tensor with the table row to use, or None (row 0).  -> (best_dst int32 [batch, h*w], score fp32 [batch, h*w])."""
+    n, Cc = h * w, x.shape[1]
+    best = torch.empty(batch, n, dtype=torch.int32, device=x.device) if best is None else best
+    score = torch.empty(batch, n, dtype=torch.float32, device=x.device) if score is None else score
+    L.check(L.lib().pp_tome_match(_p(x), x.stride(0), batch, h, w, Cc, sx, sy, _p(table), table.stride(0), table.shape[0],
+                                  _p(row_idx), _p(best), _p(score), L.dtype_code(x.dtype), _s()), "pp_tome_match")
+    return best, score
+
+
+def tome_select(best: torch.Tensor, score: torch.Tensor, nd: int, r: int, out=None):
+    """pp_tome_select -> (pos [batch, n], rowtok [batch, n - r], seg [batch, nd + 1], lst [batch, r]), int32."""
+    batch, n = best.shape
+    if out is None:
+        out = tuple(torch.empty(batch, max(m, 1), dtype=torch.int32, device=best.device) for m in (n, n - r, nd + 1, r))
+    pos, rowtok, seg, lst = out
+    L.check(L.lib().pp_tome_select(_p(best), _p(score), batch, n, nd, r, _p(pos), _p(rowtok), _p(seg), _p(lst), _s()),
+            "pp_tome_select")
+    return pos, rowtok, seg, lst
+
+
+def tome_merge(qk: torch.Tensor, vt: torch.Tensor, batch: int, n: int, nd: int, r: int, rowtok, seg, lst, qk_out=None,
+               vt_out=None):
+    """pp_tome_merge: qk 16-bit [batch*n, 2C] (row stride free), vt 16-bit [batch, C, ldvt] -> (qk_out [batch*(n - r), 2C],
+    vt_out [batch, C, round8(n - r)]), or into the given views."""
+    Cc, nm = qk.shape[1] // 2, n - r
+    qk_out = torch.empty(batch * nm, 2 * Cc, dtype=qk.dtype, device=qk.device) if qk_out is None else qk_out
+    vt_out = torch.empty(batch, Cc, (nm + 7) // 8 * 8, dtype=qk.dtype, device=qk.device) if vt_out is None else vt_out
+    L.check(L.lib().pp_tome_merge(_p(qk), qk.stride(0), _p(vt), vt.stride(1), batch, n, Cc, nd, r, _p(rowtok), _p(seg), _p(lst),
+                                  _p(qk_out), qk_out.stride(0), _p(vt_out), vt_out.stride(1), L.dtype_code(qk.dtype), _s()),
+            "pp_tome_merge")
+    return qk_out, vt_out
+
+
+def tome_unmerge(a: torch.Tensor, pos: torch.Tensor, out=None):
+    """pp_tome_unmerge: a 16-bit [batch*nm, C] (row stride free), pos int32 [batch, n] -> out [batch*n, C]."""
+    batch, n = pos.shape
+    nm, Cc = a.shape[0] // batch, a.shape[1]
+    out = torch.empty(batch * n, Cc, dtype=a.dtype, device=a.device) if out is None else out
+    L.check(L.lib().pp_tome_unmerge(_p(a), a.stride(0), _p(pos), batch, n, nm, Cc, _p(out), out.stride(0), _s()),
+            "pp_tome_unmerge")
+    return out

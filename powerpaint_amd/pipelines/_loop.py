@@ -132,6 +132,12 @@ class DenoiseLoop:
             # scheduler state: DPM m_{i-1}; PNDM history + saved sample; UniPC; Heun / DPM2 / DPM2 ancestral / LMS: three
             # derivative slots + the saved sample (DDIM, LCM and the Euler classes keep none)
             ts, step, src, mp = sch.timesteps_f32(), sch.step_counter(), lat, sch.m_prev(lat) if sch.state_slots > 0 else None
+        # token merging: one row of destination windows per network evaluation, drawn once per call; the match launches pick
+        # their row by the step counter, so a replayed graph merges around fresh windows at every step (no re-capture)
+        for r in side_rts + [rt]:
+            if r.tome_blocks():
+                r.tome_bind(step.data_ptr())
+                r.tome_fill(int(ts.numel()), r.net.tome_state)
         key = (tuple(latents_shape), bool(do_cfg), bool(guess_mode), self._noisy, float(guidance_scale), id(rt.step_plan),
                tuple(id(r.step_plan) for r in side_rts) if side_rts else None, type(sch), ts.data_ptr(), step.data_ptr(),
                0 if self.foreign else sch.coef_table().data_ptr(), mp.data_ptr() if mp is not None else 0, src.data_ptr(),

@@ -6,7 +6,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import Act, Arena, Builder, Plan, SDNet, _align, level_sizes
+from .engine import Act, Arena, Builder, Plan, SDNet, TOME_TABLE_ROWS, _align, level_sizes
 
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
@@ -185,6 +185,15 @@ class NetRuntime:
             lay["tcond_mid"] = arena.alloc(net.boc[0] * 4)
             lay["b1_eff"] = arena.alloc(net.boc[0] * 4 * 4)
             kw["b1_eff"] = lay["b1_eff"]
+        layout, stride = net.tome_layout(H, W)
+        if layout:
+            # token merging: the window table uint8 [evaluations][stride] (one segment per merging block), the device word that
+            # names the row (the launches read it through `_tome_row`, a cell holding the POINTER: a denoising loop points it
+            # at its own step counter), and per block the decisions of the last evaluation (tome_decisions)
+            lay["tome"] = dict(layout=layout, stride=stride, rows=TOME_TABLE_ROWS, table=arena.alloc(TOME_TABLE_ROWS * stride),
+                               word=arena.alloc(256), row=self._tome_row,
+                               bufs={pre: tuple(arena.alloc(B * b.h * b.w * 4) for _ in range(3)) for pre, b in layout.items()})
+            kw["tome"] = lay["tome"]
         if pad_uncond:
             if net.kind == "unet":
                 raise L.PPError("pad_uncond is an output layout of the side networks (BrushNet / ControlNet)")
@@ -244,6 +253,9 @@ class NetRuntime:
                      bool(ip_masked)),)
         elif ip_masked:
             raise L.PPError("ip_adapter_masks need a loaded IP-Adapter")
+        tm = getattr(getattr(self, "net", None), "tome", None)
+        if tm is not None:                                       # (without token merging: the key of a plan that never had it)
+            key += (("tome", tuple(tm)),)
         if isinstance(scale, (list, tuple)):
             scale = tuple(float(v) for v in scale)       # (one representation: a list never equals the stored tuple)
         if key == self.key:
@@ -254,6 +266,7 @@ class NetRuntime:
         # (the one synchronising probe of the library runs here, at plan-build time and never under a stream capture: are
         #  workgroups placed on the XCDs round-robin by linear id?  Plans combine split-K in-kernel only if so.)
         self.xcd_placement_ok = bool(self.lib.pp_xcd_placement_ok())
+        self._tome_row = C.c_void_p(0)
         dry = Arena()
         self._build(dry, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None, ip_n,
                     bool(ip_masked))
@@ -275,6 +288,65 @@ class NetRuntime:
         self._freeu = None
         self.set_freeu(freeu)
         self._tcond_key = self._tcond_keep = None      # (a fresh arena: the effective bias is recomputed by the next set_timestep_cond)
+        self.tome_bind(None)
+
+    # ------------------------------------------------------------------ token merging (DESIGN.md "Token merging")
+    def tome_blocks(self):
+        """{prefix: ToMeBlock} of the transformers whose self-attention runs on merged tokens in this plan (may be empty)."""
+        return dict(getattr(self, "lay", {}).get("tome", {}).get("layout", {}))
+
+    def tome_bind(self, row_ptr: Optional[int]):
+        """Which device int32 names the window-table row the pp_tome_match launches use: a denoising loop's step counter, or
+        None for the runtime's own word (always 0: `tome_fill(1, ...)` in front of a bare forward).  The pointer is a by-value
+        argument: a graph captured before keeps the one it was captured with, so this runtime's own graph is dropped."""
+        tm = getattr(self, "lay", {}).get("tome")
+        if tm is None:
+            return
+        ptr = int(row_ptr) if row_ptr else tm["word"]
+        if self._tome_row.value != ptr:
+            self._tome_row.value = ptr
+            self.graph = None
+
+    def tome_fill(self, evaluations: int, state) -> int:
+        """Draw the destination windows of `evaluations` network evaluations into the table: per evaluation one
+        torch.randint(sy*sx, (hsy, wsx, 1)) per merging block in execution order, from `state`'s CPU generator -- tomesd's
+        draws.  No draw (index 0 everywhere) with use_rand off or an odd logical batch (the batch of the forward, both CFG
+        halves).  One host-to-device copy; stream-ordered, so replays of a captured graph queued behind it read the new rows."""
+        tm = getattr(self, "lay", {}).get("tome")
+        if tm is None:
+            return 0
+        if evaluations > tm["rows"]:
+            raise L.PPError(f"token merging: {evaluations} network evaluations in one call, the window table holds {tm['rows']}")
+        t = self.net.tome
+        host = torch.zeros(evaluations, tm["stride"], dtype=torch.uint8)
+        draws = 0
+        if t.use_rand and self.B % 2 == 0:
+            g = state.generator()
+            for e in range(evaluations):
+                for b in tm["layout"].values():
+                    host[e, b.offset:b.offset + b.nd] = torch.randint(t.sy * t.sx, (b.h // t.sy, b.w // t.sx, 1),
+                                                                    generator=g).reshape(-1).to(torch.uint8)
+                    draws += 1
+        self.arena.view(tm["table"], (evaluations, tm["stride"]), torch.uint8).copy_(host)
+        self._tome_rows_filled = evaluations
+        return draws
+
+    def tome_table(self) -> torch.Tensor:
+        """The filled rows of the window table, uint8 [evaluations][row bytes] (a copy)."""
+        tm = self.lay["tome"]
+        return self.arena.view(tm["table"], (getattr(self, "_tome_rows_filled", 1), tm["stride"]), torch.uint8).clone()
+
+    def tome_decisions(self):
+        """{prefix: (best_dst int32 [b, n], score fp32 [b, n], pos int32 [b, n])} of the LAST evaluation, copies; b is the
+        batch the block ran on (one CFG half under the twin prefix)."""
+        tm = self.lay["tome"]
+        out = {}
+        for pre, blk in tm["layout"].items():
+            n, b = blk.h * blk.w, tm["batch"][pre]
+            best, score, pos = tm["bufs"][pre]
+            out[pre] = (self.arena.view(best, (b, n), torch.int32).clone(), self.arena.view(score, (b, n), torch.float32).clone(),
+                        self.arena.view(pos, (b, n), torch.int32).clone())
+        return out
 
     def set_freeu(self, values):
         """Write FreeU's (s1, s2, b1, b2) where the plan's pp_freeu launches read them, if they changed (stream-ordered:
@@ -453,6 +525,10 @@ class NetRuntime:
 
     # ------------------------------------------------------------------ run
     def run_step(self, use_graph: bool = False):
+        """One forward pass on its own (a model's `forward`): with token merging, fresh windows first -- a one-row table."""
+        if "tome" in self.lay:
+            self.tome_bind(None)
+            self.tome_fill(1, self.net.tome_state)
         if use_graph:
             if self.graph is None:
                 self.capture()
