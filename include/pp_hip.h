@@ -964,6 +964,28 @@ int pp_tome_merge(const void* qk, int ldqk, const void* vt, int ldvt, int batch,
                   void* stream);
 int pp_tome_unmerge(const void* a, int lda, const void* pos, int batch, int n, int nm, int C, void* out, int ldo, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Perturbed-attention guidance (added under ABI 29: purely additive).  PAG (diffusers' PAGMixin) runs one more segment of
+ * the batch whose selected self-attentions are replaced by the identity -- their output is V -- and guides away from it.
+ *
+ * pp_attn_identity_v: out[b][p][c] = vt[b][c][p] for b in [batch0, batch0 + batch), p < n, c < C: the attention output of
+ *   the perturbed batch items, copied out of V^T (16-bit [all items][C][ldvt], what pp_transpose_v, the QKV GEMM's out_vt
+ *   epilogue and pp_tfront leave) into the attention output rows (16-bit, item b's rows are b*n .. b*n + n - 1, row stride
+ *   ldo).  A bit copy: bf16 and fp16 alike.  The inverse of pp_transpose_v.
+ *   C % 8 == 0, ldvt >= n, ldvt % 8 == 0, ldo >= C, ldo % 8 == 0, any n >= 1; batch0 >= 0, 1 <= batch <= 65535; pointers
+ *   2-byte aligned (16-byte aligned pointers get 16-byte accesses on both sides).  PP_ERR_BAD_ARG otherwise, without a launch.
+ *   Columns [n, ldvt) of V^T may hold anything: they may be read and never reach `out`.  Rows of `out` of other batch items
+ *   and the bytes behind column C of a row are never written.  out must not alias vt.
+ *
+ * pp_pag_combine: eps fp32 [3][n] (cfg = 1: e_u, e_c, e_p) or [2][n] (cfg = 0: e_c, e_p), the last segment the perturbed one.
+ *   With s = pag_table[step_dev[0]] (fp32 table on the device, one scale per schedule row; step_dev the loop's int32 step
+ *   counter, read and NOT moved) segment 0 becomes, in place,
+ *       cfg = 1:  e_u + guidance * (e_c - e_u) + s * (e_c - e_p)          cfg = 0:  e_c + s * (e_c - e_p)
+ *   every element from its own index only; the other segments are not written.  The scheduler's step launch behind it runs
+ *   with cfg = 0 on segment 0.  n >= 1 need not be a multiple of 4; eps 4-byte aligned; cfg is 0 or 1 (PP_ERR_BAD_ARG). */
+int pp_attn_identity_v(const void* vt, int ldvt, int batch0, int batch, int n, int C, void* out, int ldo, void* stream);
+int pp_pag_combine(float* eps, int cfg, float guidance, const float* pag_table, const int32_t* step_dev, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -736,6 +736,14 @@ class ToMeBlock(NamedTuple):
 TOME_TABLE_ROWS = 1000       # network evaluations of one pipeline call the window table holds
 
 
+class PAG(NamedTuple):
+    """Perturbed-attention guidance on a UNet (powerpaint_amd/pag.py, DESIGN.md "Perturbed-attention guidance"): the
+    transformers whose self-attention is the identity for the LAST `n` batch items.  Part of a plan's key; the scales are not
+    the network's business (the loop's pp_pag_combine reads them)."""
+    layers: Tuple[str, ...]
+    n: int
+
+
 class XAttnForm(enum.Enum):
     """How the cross-attention sub-block of a transformer (norm2 -> to_q -> attention over the prompt -> to_out + residual)
     runs.  SDNet.xattn_form decides; the value is the `kperm` pp_xattn_fold lays the folded operands out with."""
@@ -836,6 +844,16 @@ class _TransformerBlock:
         net, pb, x = self.net, self.pb, self.x
         Cc, hw, B, d = x.C, self.hw, x.B, x.C // net.heads
         r = self.tome_r()
+        pg = net._pag_step
+        if pg is not None and self.pre in pg.layers:
+            # perturbed-attention guidance: softmax attention on the leading batch items (same pointers, smaller batch); for the
+            # trailing pg.n items attn1's output is V itself, copied out of V^T into the same buffer
+            if r:
+                raise L.PPError(f"{self.pre}: token merging (ToMe) together with perturbed-attention guidance (PAG) is not implemented")
+            a = pb.alloc(B * hw * Cc * 2)
+            pb.attention(qk, ldqk, qk + 2 * Cc, ldqk, vt, ldvt, B - pg.n, net.heads, hw, hw, d, out=a, ldo=Cc, log2q=log2q)
+            pb.plan.add("attn_identity_v", pb.lib.pp_attn_identity_v, vt, ldvt, B - pg.n, pg.n, hw, Cc, a, Cc)
+            return a
         if not r:
             return pb.attention(qk, ldqk, qk + 2 * Cc, ldqk, vt, ldvt, B, net.heads, hw, hw, d, log2q=log2q)
         tm, lib = net._tome_step, pb.lib
@@ -1072,6 +1090,7 @@ class SDNet:
         return out
 
     _tome_step: Optional[Dict[str, object]] = None
+    _pag_step: Optional[PAG] = None  # perturbed-attention guidance of the step plan being built (build_step(pag=...))
     tome: Optional[ToMe] = None      # token merging (powerpaint_amd/tome.py: apply_patch / remove_patch)
 
     def tome_layout(self, H: int, W: int) -> Tuple[Dict[str, ToMeBlock], int]:
@@ -1805,7 +1824,8 @@ class SDNet:
     def build_step(self, pb: Builder, x_in: Act, t_dev: int, add_down: Optional[List[int]] = None,
                    add_mid: int = 0, add_up: Optional[List[int]] = None, ctrl_down: Optional[List[int]] = None,
                    ctrl_mid: int = 0, scale: float = 1.0, pad_uncond: bool = False, twin: bool = False,
-                   freeu: int = 0, b1_eff: int = 0, tome: Optional[Dict[str, object]] = None) -> Dict[str, object]:
+                   freeu: int = 0, b1_eff: int = 0, tome: Optional[Dict[str, object]] = None,
+                   pag: Optional[PAG] = None) -> Dict[str, object]:
         """Append one forward pass.  x_in: NHWC bf16 input (already channel-concatenated).  Returns outputs:
         unet -> {"eps": ptr fp32 NCHW}; brushnet -> {"down": [Act], "mid": Act, "up": [Act]}; controlnet likewise.
         pad_uncond (side networks): the pipelines' guess mode runs the side branch on the conditional half of a CFG pair
@@ -1826,9 +1846,22 @@ class SDNet:
         b1_eff (a UNet with time_cond_proj_dim): device pointer to the fp32 effective bias of time_embedding.linear_1,
         b1 + W1 (Wc c) for the call's guidance embedding c -- `linear_1(t_emb + cond_proj(c))` of diffusers' TimestepEmbedding
         (unet_2d_condition.py:1156) with the c-dependent term, constant over a call, taken out of the step
-        (NetRuntime.set_timestep_cond fills it).  0: the parameter's own bias."""
+        (NetRuntime.set_timestep_cond fills it).  0: the parameter's own bias.
+        pag (unet): perturbed-attention guidance -- in the transformers pag.layers the self-attention of the LAST pag.n batch
+        items is the identity (`_TransformerBlock.attend`: the attention launch on the leading items, one pp_attn_identity_v
+        launch for the rest); the CFG twin prefix is not taken.  None: the plan of a UNet without it."""
         P, lib = self.P, pb.lib
         B, H, W = x_in.B, x_in.H, x_in.W
+        if pag is not None:
+            known = [p for p, _ in self._attn_specs()]
+            if self.kind != "unet":
+                raise L.PPError("perturbed-attention guidance perturbs the UNet only, never BrushNet or ControlNet")
+            if not 0 < pag.n < B or not pag.layers or any(p not in known for p in pag.layers):
+                raise L.PPError(f"perturbed-attention guidance: {pag.n} perturbed items of a batch of {B} in {list(pag.layers)} "
+                                f"is no setting of this network")
+            if tome and tome.get("layout"):
+                raise L.PPError("token merging (ToMe) together with perturbed-attention guidance (PAG) is not implemented")
+        self._pag_step = pag
         boc = self.boc
         # token merging (NetRuntime._build): layout (tome_layout), the window table (pointer, row stride, rows), the cell that
         # holds the pointer to the device word naming the row, per block the persistent (best_dst, score, pos) buffers, and
@@ -1840,7 +1873,8 @@ class SDNet:
         # (a forced tile / split-K factor -- NetRuntime.gemm_tile / gemm_splitk, a measurement knob -- may send conv_in off
         #  the single-pass staged epilogue that stores the twin copy: the flag then changes nothing, as everywhere it cannot run)
         # (IP-Adapters: the prefix ends in the fused cross-attention block, which is not taken while one is loaded)
-        twin = bool(twin) and not pad_uncond and not self.ip and not (pb.gemm_tile or pb.gemm_splitk) and \
+        # (perturbed-attention guidance: the batch is no pair of identical halves)
+        twin = bool(twin) and not pad_uncond and not self.ip and pag is None and not (pb.gemm_tile or pb.gemm_splitk) and \
             self.twin_prefix_ok(lib, B, H, W, self._nctx, brush)
 
         def pop(lst):

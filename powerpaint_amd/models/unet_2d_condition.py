@@ -12,6 +12,7 @@ import torch
 
 from .. import _lib as L
 from .. import ip_adapter as IPA
+from .. import pag as PAGM
 from ..lora import AdapterSet, LoraAdapter, unet_targets
 from ._base import SD15_DOWN, SD15_UP, Output, _HipModel
 
@@ -268,6 +269,24 @@ class UNet2DConditionModel(_HipModel):
         v = self.__dict__.get("_freeu")
         return tuple(float(x) for x in v) if v is not None and all(v) else None
 
+    # ------------------------------------------------------------------ perturbed-attention guidance
+    def pag_attn1_names(self):
+        """The self-attention modules of this UNet by their diffusers names, in execution order."""
+        return PAGM.attn1_names([p for p, _ in self.net._attn_specs()])
+
+    def set_pag_applied_layers(self, layers="mid"):
+        """diffusers' `pag_applied_layers` (a string or a list of strings, each a regular expression searched in the names of
+        the self-attention modules; PAGMixin's rules, pag.resolve_layers).  Invalid entries raise at once.  What is stored is
+        the resolved set of transformers; it takes effect in calls with `pag_scale > 0` (prepare(pag_batch=...))."""
+        self._pag_layers = PAGM.resolve_prefixes(layers, [p for p, _ in self.net._attn_specs()])
+        return self
+
+    def pag_layers(self):
+        """The transformers `set_pag_applied_layers` selected (default: "mid")."""
+        if self.__dict__.get("_pag_layers") is None:
+            self.set_pag_applied_layers("mid")
+        return self._pag_layers
+
     # ------------------------------------------------------------------
     def _wiring(self, down_add, mid_add, up_add, ctrl_down, ctrl_mid):
         def ptrs(lst):
@@ -285,8 +304,11 @@ class UNet2DConditionModel(_HipModel):
     def prepare(self, sample_shape, encoder_hidden_states, down_block_add_samples=None, mid_block_add_sample=None,
                 up_block_add_samples=None, down_block_additional_residuals=None, mid_block_additional_residual=None,
                 twin: bool = False, timestep_cond: Optional[torch.Tensor] = None, added_cond_kwargs=None,
-                ip_adapter_masks: Optional[torch.Tensor] = None):
-        """Compile (or reuse) the launch plan for this shape / residual wiring and bind the inputs.  added_cond_kwargs:
+                ip_adapter_masks: Optional[torch.Tensor] = None, pag_batch: int = 0):
+        """Compile (or reuse) the launch plan for this shape / residual wiring and bind the inputs.  pag_batch > 0:
+        perturbed-attention guidance -- the LAST pag_batch items of the batch are the perturbed segment: in the transformers
+        `pag_layers()` their self-attention is the identity (one re-plan when it is switched on or off; 0: the plan of a UNet
+        that never had it).  added_cond_kwargs:
         {"image_embeds": [...]} while IP-Adapters are loaded (_ip_image_embeds), copied in on every call.  ip_adapter_masks:
         `cross_attention_kwargs["ip_adapter_masks"]` (_check_ip_masks) -- masked or not is part of the plan key, the values
         are per-row weights in device memory, rewritten on every call (NetRuntime.set_ip_masks).  timestep_cond: the
@@ -305,7 +327,7 @@ class UNet2DConditionModel(_HipModel):
         ip_embeds = self._ip_image_embeds(added_cond_kwargs, B)
         self.rt.ensure(B, H, W, self._nctx(encoder_hidden_states), Cin, wiring, twin=twin, freeu=self._freeu_values(),
                        ip_n=[e.shape[1] if e.dim() == 3 else (e.shape[1], e.shape[2]) for e in ip_embeds] if ip_embeds else (),
-                       ip_masked=ip_masks is not None)
+                       ip_masked=ip_masks is not None, pag=PAGM.setting(self.pag_layers(), pag_batch) if pag_batch else None)
         if ip_embeds:
             self.rt.set_ip_embeds(ip_embeds)
         if ip_masks is not None:

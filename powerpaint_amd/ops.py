@@ -770,3 +770,27 @@ def tome_unmerge(a: torch.Tensor, pos: torch.Tensor, out=None):
     L.check(L.lib().pp_tome_unmerge(_p(a), a.stride(0), _p(pos), batch, n, nm, Cc, _p(out), out.stride(0), _s()),
             "pp_tome_unmerge")
     return out
+
+
+def attn_identity_v(vt: torch.Tensor, n: int, out: torch.Tensor, batch0: int = 0, batch: Optional[int] = None):
+    """pp_attn_identity_v: vt 16-bit [items, C, ldvt] (V transposed) -> rows [b*n, b*n + n) x columns [0, C) of `out` ([items*n,
+    >= C], row stride free) for b in [batch0, batch0 + batch): the attention output of PAG's perturbed batch items, V itself."""
+    items, Cc, ldvt = vt.shape
+    batch = items - batch0 if batch is None else batch
+    if vt.stride(2) != 1 or vt.stride(1) != ldvt or vt.stride(0) != Cc * ldvt or out.stride(1) != 1 or out.dtype != vt.dtype:
+        raise L.PPError("attn_identity_v: vt must be dense [items, C, ldvt], out row-major of the same 16-bit format")
+    if batch0 < 0 or batch < 1 or batch0 + batch > items or out.shape[0] < items * n or out.shape[1] < Cc:
+        raise L.PPError(f"attn_identity_v: items [{batch0}, {batch0 + batch}) of {items}, n = {n}: out {tuple(out.shape)} is too small")
+    L.check(L.lib().pp_attn_identity_v(_p(vt), ldvt, batch0, batch, n, Cc, _p(out), out.stride(0), _s()), "pp_attn_identity_v")
+    return out
+
+
+def pag_combine(eps: torch.Tensor, cfg: bool, guidance: float, pag_table: torch.Tensor, step: torch.Tensor):
+    """pp_pag_combine, in place: eps fp32 [3 or 2 segments, ...] contiguous; pag_table fp32 [rows]; step int32 [1] on the device."""
+    segs = 3 if cfg else 2
+    if eps.dtype != torch.float32 or not eps.is_contiguous() or eps.shape[0] != segs or pag_table.dtype != torch.float32 or \
+            step.dtype != torch.int32:
+        raise L.PPError(f"pag_combine: eps must be contiguous fp32 [{segs}, ...], pag_table fp32, step int32")
+    L.check(L.lib().pp_pag_combine(_p(eps), int(bool(cfg)), float(guidance), _p(pag_table), _p(step), eps[0].numel(), _s()),
+            "pp_pag_combine")
+    return eps

@@ -286,6 +286,13 @@ class PipelineBase(PipelinePretrainedMixin):
                 self.__dict__.pop("_prompt_memo", None)        # embeddings of the previous weights
         return s
 
+    def set_pag_applied_layers(self, layers="mid"):
+        """diffusers' `pag_applied_layers` (PAGMixin): a string or a list of strings, each searched as a regular expression
+        in the names of the UNet's self-attention modules (`mid_block.attentions.0.transformer_blocks.0.attn1`, ...).  The
+        selection takes effect in calls with `pag_scale > 0`.  An entry that selects nothing raises ValueError at once."""
+        self.unet.set_pag_applied_layers(layers)
+        return self
+
     def _refuse_ip_adapter_masks(self, cross_attention_kwargs):
         """A pipeline without an IP-Adapter path: `cross_attention_kwargs["ip_adapter_masks"]` is refused, never dropped."""
         if (cross_attention_kwargs or {}).get("ip_adapter_masks") is not None:

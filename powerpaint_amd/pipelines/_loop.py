@@ -17,6 +17,12 @@ Behind it pp_ddim_variance_noise (DDIM, eta > 0) and pp_latent_blend (ppt-v1 wit
 to the next timestep).  The step launch's last block moves the step counter on where nothing behind it reads the counter;
 else pp_step_advance does.  No host->device traffic and no host synchronisation inside the loop.
 
+Perturbed-attention guidance (`pag_scale > 0`, powerpaint_amd/pag.py): every network runs (2 + do_cfg) B items, `[uncond, cond,
+cond]` or `[cond, cond]`, the last segment perturbed inside the UNet; the head launch replicates the latents over all of them.
+In front of the step launch pp_pag_combine writes  e_u + g (e_c - e_u) + s_i (e_c - e_p)  into segment 0 of eps, s_i read from
+a device table with one scale per schedule row, and the step launch runs with cfg = 0 on that segment.  The scales are data:
+a new scale pair reaches a captured graph without a re-capture.
+
 Several ControlNets (`side` = a MultiControlNetModel, pipeline_PowerPaint_ControlNet.py:306,1678-1694): one runtime per
 net (own arena, time-embedding table, hoisted control-image embedding, twin-prefix decision); the step is
     head(net 0) .. head(net N-1), head(UNet), plan(net 0) .. plan(net N-1), plan(UNet), scheduler step
@@ -38,6 +44,7 @@ from typing import Callable, List, Optional
 import torch
 
 from .. import _lib as L
+from .. import pag as PAGM
 from ..engine import Plan
 from ..schedulers import _SchedulerBase
 
@@ -72,7 +79,8 @@ class DenoiseLoop:
     def bind(self, latents_shape, do_cfg: bool, guidance_scale: float, prompt_embeds, prompt_embeds_side=None,
              static_inputs=(), side_static_inputs=(), controlnet_cond=None, side_scale: float = 1.0,
              guess_mode: bool = False, eta: float = 0.0, generator=None, noise_dtype=torch.float32, blend=None,
-             timestep_cond=None, added_cond_kwargs=None, ip_adapter_masks=None):
+             timestep_cond=None, added_cond_kwargs=None, ip_adapter_masks=None, pag_scale: float = 0.0,
+             pag_adaptive_scale: float = 0.0):
         """Compile the per-step program.  latents_shape = (B, 4, h, w) of the *un-duplicated* latents.
         ip_adapter_masks: `cross_attention_kwargs["ip_adapter_masks"]` of the call, [adapters, 1, H, W]; the UNet only, as the
         image embeds.  Their values are device memory the UNet's launches read (NetRuntime.set_ip_masks): new masks of the
@@ -93,8 +101,15 @@ class DenoiseLoop:
         guess_mode (pipeline_PowerPaint_Brushnet_CA.py:1394-1425, pipeline_PowerPaint_ControlNet.py:1669-1702): the
         side network sees only the conditional half of a CFG pair (its inputs -- `prompt_embeds_side`, conditioning
         latents / control image -- arrive un-duplicated) with its residual scales log-spaced from 0.1 to 1; the
-        unconditional half of the UNet batch gets zeros."""
+        unconditional half of the UNet batch gets zeros.
+        pag_scale > 0 (diffusers' PAGMixin): perturbed-attention guidance in the transformers `unet.pag_layers()`; per-call
+        inputs arrive as without it (un-duplicated or as the CFG pair) and are laid out `[.., cond, cond]` here.  The scale
+        pair is no part of the plan key: `_fill_pag_table` writes one scale per schedule row into device memory."""
         B, sch = latents_shape[0], self.scheduler
+        pag = float(pag_scale) > 0.0
+        if pag:
+            PAGM.check_supported(tome=getattr(self.unet.net, "tome", None) is not None and self.unet.net.tome.ratio > 0,
+                                 guess_mode=bool(guess_mode))
         if self.latents is None or tuple(self.latents.shape) != tuple(latents_shape):
             self.latents = torch.zeros(latents_shape, dtype=torch.float32, device=self.unet.device)
         lat = self.latents
@@ -119,13 +134,13 @@ class DenoiseLoop:
                             f"no head launch to scale the network input in")
         self._blend = self._blend_buffers(blend, latents_shape)
         half = bool(guess_mode and do_cfg)                   # side network on the conditional half only
-        Be = 2 * B if do_cfg else B
+        Be = PAGM.segments(do_cfg) * B if pag else (2 * B if do_cfg else B)
         Bs = B if half else Be
         nets, side, controlnet_cond, side_scale = self._resolve_side(controlnet_cond, side_scale, guess_mode)
         multi = nets is not None and len(nets) > 1
         rt, side_rt, side_rts = self._prepare_runtimes(
             latents_shape, Be, Bs, do_cfg, half, guess_mode, nets, side, prompt_embeds, prompt_embeds_side, static_inputs,
-            side_static_inputs, controlnet_cond, side_scale, timestep_cond, added_cond_kwargs, ip_adapter_masks)
+            side_static_inputs, controlnet_cond, side_scale, timestep_cond, added_cond_kwargs, ip_adapter_masks, pag=pag)
         if self.foreign:
             ts, step, src, mp = self._foreign_state(latents_shape, do_cfg, guidance_scale)
         else:
@@ -145,6 +160,9 @@ class DenoiseLoop:
                tuple(b.data_ptr() for b in self._blend) if self._blend is not None else None,
                sch.renoise_table().data_ptr() if (self._blend is not None and not self.foreign) else 0,
                in_div.data_ptr() if in_div is not None else 0)
+        self._pag = (float(pag_scale), float(pag_adaptive_scale)) if pag else None
+        if pag:                                  # (the table's address is part of the key, the scales in it are not: `run` fills it)
+            key += (("pag", 0 if self.foreign else self._pag_table_for(int(ts.numel()), ts.device).data_ptr()),)
         if key == self._key and self.program is not None:
             # The conditioning scale is a by-value argument of the zero-conv launches: `prepare` has patched the launch
             # records (eager runs see it), but a graph captured with another value still carries the old one.
@@ -153,7 +171,7 @@ class DenoiseLoop:
                 self.graph = None
             return self
         self._key = key
-        heads, skips = self._head_launches(side_rts, rt, ts, step, src, Be, Bs, do_cfg, in_div)
+        heads, skips = self._head_launches(side_rts, rt, ts, step, src, Be, Bs, do_cfg or pag, in_div)
         tail = self._tail_launches(rt, lat, mp, step, do_cfg, guidance_scale)
         self.rt, self.side_rt, self.side_rts = rt, side_rt, side_rts
         self.graph = None
@@ -202,14 +220,27 @@ class DenoiseLoop:
 
     def _prepare_runtimes(self, latents_shape, Be, Bs, do_cfg, half, guess_mode, nets, side, prompt_embeds,
                           prompt_embeds_side, static_inputs, side_static_inputs, controlnet_cond, side_scale, timestep_cond,
-                          added_cond_kwargs, ip_adapter_masks=None):
+                          added_cond_kwargs, ip_adapter_masks=None, pag: bool = False):
         """-> (rt, side_rt, side_rts): every network prepared, the UNet wired to the side residuals, static channels loaded.
         The CFG pair is built here, as `cat([latents] * 2)` (pipeline_PowerPaint.py:990): where every other network input
         is CFG-duplicated as well, the two halves of a forward pass are identical until the prompt enters and the
         networks run that prefix once (`twin`, SDNet.build_step).  A static input counts as duplicated when it arrives
-        with the un-duplicated batch (load_input copies it to both halves) or when its halves compare equal."""
+        with the un-duplicated batch (load_input copies it to both halves) or when its halves compare equal.
+        pag: every per-call input goes into the PAG layout first (pag.layout: the third segment gets the second's inputs, the
+        side networks' included, as diffusers' PAG pipelines feed theirs); no twin prefix."""
         B, Cl, h, w = latents_shape
         multi = nets is not None and len(nets) > 1
+        if pag:
+            lay3 = lambda t: PAGM.layout(t, B, bool(do_cfg))      # noqa: E731
+            prompt_embeds, prompt_embeds_side = lay3(prompt_embeds), lay3(prompt_embeds_side)
+            static_inputs = [(lay3(t), c) for t, c in static_inputs]
+            side_static_inputs = [(lay3(t), c) for t, c in side_static_inputs]
+            controlnet_cond = [lay3(c) for c in controlnet_cond] if isinstance(controlnet_cond, (list, tuple)) \
+                else lay3(controlnet_cond)
+            if timestep_cond is not None:
+                timestep_cond = timestep_cond[:1]              # (one value over the batch: _check_timestep_cond)
+            if added_cond_kwargs and "image_embeds" in added_cond_kwargs:      # [neg, pos] -> [neg, pos, pos]
+                added_cond_kwargs = dict(added_cond_kwargs, image_embeds=[lay3(e) for e in added_cond_kwargs["image_embeds"]])
 
         def halves_equal(t):
             if t is None or not torch.is_tensor(t):
@@ -218,9 +249,9 @@ class DenoiseLoop:
                 return True
             return t.shape[0] == 2 * B and bool(torch.equal(t[:B], t[B:]))
 
-        twin_u = bool(do_cfg) and all(halves_equal(t) for t, _ in static_inputs)
+        twin_u = bool(do_cfg) and not pag and all(halves_equal(t) for t, _ in static_inputs)
         # (the control image goes through set_cond, which accepts the un-duplicated batch as well and copies it to both halves)
-        twin_s = bool(do_cfg) and not half and all(halves_equal(t) for t, _ in side_static_inputs) and \
+        twin_s = bool(do_cfg) and not pag and not half and all(halves_equal(t) for t, _ in side_static_inputs) and \
             (self.side_kind == "brushnet" or multi or halves_equal(controlnet_cond))
         if self.side is not None and self.side.dtype != self.unet.dtype:
             # the fused loop hands the side network's residuals to the UNet as raw NHWC arena pointers, every step: both
@@ -256,6 +287,8 @@ class DenoiseLoop:
             wiring_kw["added_cond_kwargs"] = added_cond_kwargs
         if ip_adapter_masks is not None:
             wiring_kw["ip_adapter_masks"] = ip_adapter_masks
+        if pag:
+            wiring_kw["pag_batch"] = B
         rt = self.unet.prepare((Be, self.unet.config.in_channels, h, w), prompt_embeds, twin=twin_u, **wiring_kw)
         # one-time (per call) static channels of the UNet / side inputs
         rt.load_input(list(static_inputs))
@@ -334,6 +367,12 @@ class DenoiseLoop:
             if self._noisy and (getattr(self, "_var_noise", None) is None or self._var_noise.shape != lat.shape):
                 self._var_noise = torch.zeros_like(lat)
             noise = self._var_noise if self._noisy else lat      # (a step that reads no noise: any valid address)
+            if self._pag is not None:
+                # perturbed-attention guidance: the three-way (two-way) combine into segment 0 of eps, its scale read from this
+                # row of the table; the step launch behind it takes segment 0 as it is (cfg = 0)
+                prog.add("pag_combine", lib.pp_pag_combine, rt.outputs["eps"], int(do_cfg), float(guidance_scale),
+                         self._pag_table.data_ptr(), step.data_ptr(), lat.numel())
+                do_cfg = False
             prog.add(*sch.step_launch(rt.outputs["eps"], int(do_cfg), float(guidance_scale), lat.data_ptr(),
                                       mp.data_ptr() if mp is not None else None, noise.data_ptr(), lat.numel(),
                                       step.data_ptr(), self._ticket.data_ptr() if fold_advance else None))
@@ -347,6 +386,24 @@ class DenoiseLoop:
         if not fold_advance:
             prog.add("step_advance", lib.pp_step_advance, step.data_ptr())
         return prog
+
+    # ---- perturbed-attention guidance: the per-row scale table
+    def _pag_table_for(self, rows: int, device) -> torch.Tensor:
+        """fp32 [rows of the schedule] at a stable address (a captured graph reads it)."""
+        t = getattr(self, "_pag_table", None)
+        if t is None or t.numel() != rows or t.device != device:
+            self._pag_table, self._pag_filled = torch.zeros(rows, dtype=torch.float32, device=device), None
+        return self._pag_table
+
+    def _fill_pag_table(self, ts):
+        """s_i of every schedule row (pag.scale_rows) -> the device table, when the scale pair or the timesteps changed."""
+        host = getattr(self.scheduler, "_ts_host", None) if not self.foreign else None
+        tsl = [float(v) for v in (host if host is not None else ts).tolist()]
+        want = (self._pag, tuple(tsl))
+        if want != self._pag_filled:
+            self._pag_rows = PAGM.scale_rows(self._pag[0], self._pag[1], tsl)
+            self._pag_table.copy_(torch.tensor(self._pag_rows, dtype=torch.float32))
+            self._pag_filled = want
 
     def _assemble(self, multi, heads, skips, tail):
         """`self.program`: every head, every network's plan without the launches its head replaces, the tail.  Several
@@ -545,6 +602,8 @@ class DenoiseLoop:
         if self._keep[2] is not None:
             self._keep[2].zero_()
         self._fill_temb_tables()
+        if self._pag is not None:
+            self._fill_pag_table(self._keep[0])
         self.latents.copy_(latents.to(self.latents.device, torch.float32))
         ents, scale_schedule, varying = self._schedule(scale_schedule, num_steps)
         if ents is not None and use_graph:        # (every set's graph before the first step)
@@ -637,7 +696,9 @@ class DenoiseLoop:
             else:
                 self.program.run(stream)
             eps = self.rt.eps_tensor()
-            if self._do_cfg:
+            if self._pag is not None:
+                eps = PAGM.combine(eps, self._do_cfg, self._g, PAGM.scale_rows(self._pag[0], self._pag[1], [float(t)])[0])
+            elif self._do_cfg:
                 eu, ec = eps.chunk(2)
                 eps = eu + self._g * (ec - eu)
             lat = sch.step(eps, t, lat, **self._extra_step_kwargs, return_dict=False)[0].to(torch.float32)

@@ -15,13 +15,15 @@ from .image_processor import VaeImageProcessor
 
 class StableDiffusionInpaintPipeline(PipelineBase):
     def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, scheduler=None, safety_checker=None,
-                 feature_extractor=None, requires_safety_checker: bool = False):
+                 feature_extractor=None, requires_safety_checker: bool = False, pag_applied_layers=None):
         self.register_modules(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet, scheduler=scheduler,
                               safety_checker=safety_checker, feature_extractor=feature_extractor)
         self.vae_scale_factor = 2 ** (len(vae.config.block_out_channels) - 1) if vae is not None else 8
         self.image_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor) if vae is not None else None
         self._loop = None
         self.use_graph = True
+        if pag_applied_layers is not None:
+            self.set_pag_applied_layers(pag_applied_layers)
 
     def check_inputs(self, prompt, height, width, strength, callback_steps, negative_prompt=None, prompt_embeds=None,
                      negative_prompt_embeds=None):
@@ -75,7 +77,8 @@ class StableDiffusionInpaintPipeline(PipelineBase):
                  return_dict: bool = True, callback: Optional[Callable[[int, int, torch.FloatTensor], None]] = None,
                  callback_steps: int = 1, cross_attention_kwargs: Optional[Dict[str, Any]] = None, task_class=None,
                  masked_image_latents: Optional[torch.FloatTensor] = None,
-                 mask_latents: Optional[torch.FloatTensor] = None):
+                 mask_latents: Optional[torch.FloatTensor] = None, pag_scale: float = 0.0,
+                 pag_adaptive_scale: float = 0.0):
         self._refuse_ip_adapter_masks(cross_attention_kwargs)
         if task_class is not None:
             raise NotImplementedError("task_class is not used by the released checkpoints")
@@ -141,7 +144,8 @@ class StableDiffusionInpaintPipeline(PipelineBase):
             self._loop = DenoiseLoop(self.unet, self.scheduler)
         self._loop.bind(shape, do_cfg, guidance_scale, prompt_embeds, static_inputs=[] if four else [(m, 4), (mil, 5)],
                         eta=eta, generator=generator, noise_dtype=self._noise_dtype(prompt_embeds),
-                        blend=(image_latents, m, noise) if four else None)
+                        blend=(image_latents, m, noise) if four else None, pag_scale=pag_scale,
+                        pag_adaptive_scale=pag_adaptive_scale)
         cb = None
         if callback is not None:
             def cb(i, t, lat):

@@ -13,6 +13,7 @@ import torch
 
 from .. import _lib as L
 from .. import ip_adapter as IPA
+from .. import pag as PAGM
 from ._base import PipelineBase, hip_mask_prep, randn_tensor
 from ._loop import DenoiseLoop
 from .image_processor import VaeImageProcessor
@@ -37,7 +38,7 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
 
     def __init__(self, vae=None, text_encoder=None, text_encoder_brushnet=None, tokenizer=None, unet=None,
                  brushnet=None, scheduler=None, safety_checker=None, feature_extractor=None, image_encoder=None,
-                 requires_safety_checker: bool = False):
+                 requires_safety_checker: bool = False, pag_applied_layers=None):
         self.register_modules(vae=vae, text_encoder=text_encoder, text_encoder_brushnet=text_encoder_brushnet,
                               tokenizer=tokenizer, unet=unet, brushnet=brushnet, scheduler=scheduler,
                               safety_checker=safety_checker, feature_extractor=feature_extractor,
@@ -46,6 +47,8 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
         self.image_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor) if vae is not None else None
         self._loop = None
         self.use_graph = True
+        if pag_applied_layers is not None:
+            self.set_pag_applied_layers(pag_applied_layers)
 
     @property
     def guidance_scale(self):
@@ -268,7 +271,8 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"],
                  conditioning_latents: Optional[torch.FloatTensor] = None,
                  prompt_embedsU: Optional[torch.FloatTensor] = None,
-                 negative_prompt_embedsU: Optional[torch.FloatTensor] = None, **kwargs):
+                 negative_prompt_embedsU: Optional[torch.FloatTensor] = None, pag_scale: float = 0.0,
+                 pag_adaptive_scale: float = 0.0, **kwargs):
         callback = kwargs.pop("callback", None)
         callback_steps = kwargs.pop("callback_steps", 1)
         self._check_ip_inputs(ip_adapter_image, ip_adapter_image_embeds)
@@ -368,7 +372,8 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
                         side_static_inputs=[(conditioning_latents, self.unet.config.in_channels)],
                         side_scale=scales[0], guess_mode=guess_mode, eta=eta, generator=generator,
                         noise_dtype=self._noise_dtype(prompt_embeds), timestep_cond=timestep_cond,
-                        added_cond_kwargs=added_cond_kwargs, ip_adapter_masks=ip_adapter_masks)
+                        added_cond_kwargs=added_cond_kwargs, ip_adapter_masks=ip_adapter_masks, pag_scale=pag_scale,
+                        pag_adaptive_scale=pag_adaptive_scale)
         cb = None
         bad = [k for k in callback_on_step_end_tensor_inputs if k not in self._callback_tensor_inputs]
         if bad:                                                                              # check_inputs, :775-780
@@ -399,6 +404,8 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
                             state["prompt_embeds"] = pe
                             side_rt = self._loop.side_rt
                             ctx = pe.chunk(2)[1] if (guess_mode and do_cfg and pe.shape[0] == 2 * nb) else pe
+                            if pag_scale > 0:                   # (the side network runs [.., cond, cond])
+                                ctx = PAGM.layout(ctx, nb, do_cfg)
                             side_rt.set_context(ctx.to(device), force=True)
                         state["negative_prompt_embeds"] = ret.pop("negative_prompt_embeds", state["negative_prompt_embeds"])
                 if callback is not None and self._legacy_callback_row(i, n, num_inference_steps) and \

@@ -21,8 +21,10 @@ from .pipeline_PowerPaint import StableDiffusionInpaintPipeline
 
 class StableDiffusionControlNetInpaintPipeline(StableDiffusionInpaintPipeline):
     def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, controlnet=None, scheduler=None,
-                 safety_checker=None, feature_extractor=None, requires_safety_checker: bool = False):
-        super().__init__(vae, text_encoder, tokenizer, unet, scheduler, safety_checker, feature_extractor)
+                 safety_checker=None, feature_extractor=None, requires_safety_checker: bool = False,
+                 pag_applied_layers=None):
+        super().__init__(vae, text_encoder, tokenizer, unet, scheduler, safety_checker, feature_extractor,
+                         pag_applied_layers=pag_applied_layers)
         if isinstance(controlnet, (list, tuple)):                               # pipeline_PowerPaint_ControlNet.py:305-306
             controlnet = MultiControlNetModel(controlnet)
         self.controlnet = controlnet
@@ -114,7 +116,8 @@ class StableDiffusionControlNetInpaintPipeline(StableDiffusionInpaintPipeline):
                  control_guidance_start: Union[float, List[float]] = 0.0,
                  control_guidance_end: Union[float, List[float]] = 1.0,
                  masked_image_latents: Optional[torch.FloatTensor] = None,
-                 mask_latents: Optional[torch.FloatTensor] = None):
+                 mask_latents: Optional[torch.FloatTensor] = None, pag_scale: float = 0.0,
+                 pag_adaptive_scale: float = 0.0):
         self._refuse_ip_adapter_masks(cross_attention_kwargs)
         multi = isinstance(self.controlnet, MultiControlNetModel)
         if multi:
@@ -205,7 +208,8 @@ class StableDiffusionControlNetInpaintPipeline(StableDiffusionInpaintPipeline):
         self._loop.bind(shape, do_cfg, guidance_scale, prompt_embeds, prompt_embeds_side=prompt_embeds,
                         static_inputs=[] if four else [(m, 4), (mil, 5)], controlnet_cond=control_image,
                         side_scale=bind_scale, guess_mode=guess_mode, eta=eta, generator=generator,
-                        noise_dtype=self._noise_dtype(prompt_embeds), blend=(image_latents, m, noise) if four else None)
+                        noise_dtype=self._noise_dtype(prompt_embeds), blend=(image_latents, m, noise) if four else None,
+                        pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale)
         cb = None
         if callback is not None:
             def cb(i, t, lat):

@@ -107,7 +107,7 @@ class NetRuntime:
                 self.arena.view(ptr, (nq,), torch.float32).copy_(w)
 
     def _build(self, arena: Arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond=False, twin=False,
-               freeu=False, ip_n=(), ip_masked=False):
+               freeu=False, ip_n=(), ip_masked=False, pag=None):
         net = self.net
         pb_setup = Builder(arena, dtype=net.dtype)
         pb_setup.gemm_tile, pb_setup.gemm_splitk = self.gemm_tile, self.gemm_splitk
@@ -194,6 +194,8 @@ class NetRuntime:
                                word=arena.alloc(256), row=self._tome_row,
                                bufs={pre: tuple(arena.alloc(B * b.h * b.w * 4) for _ in range(3)) for pre, b in layout.items()})
             kw["tome"] = lay["tome"]
+        if pag is not None:
+            kw["pag"] = pag
         if pad_uncond:
             if net.kind == "unet":
                 raise L.PPError("pad_uncond is an output layout of the side networks (BrushNet / ControlNet)")
@@ -230,8 +232,11 @@ class NetRuntime:
 
     def ensure(self, B: int, H: int, W: int, nctx: int, cin_total: int, wiring=("plain",), cond_hw=None,
                scale: float = 1.0, pad_uncond: bool = False, twin: bool = False, freeu=None, ip_n=(),
-               ip_masked: bool = False):
-        """freeu: None, or (s1, s2, b1, b2) of UNet2DConditionModel.enable_freeu -- on / off is part of the plan key (the
+               ip_masked: bool = False, pag=None):
+        """pag: None, or the engine.PAG setting of a UNet (the transformers whose self-attention is the identity for the last
+        pag.n batch items) -- part of the plan key; without it the key and the plan of a network that never had it.  Refused
+        together with token merging.
+        freeu: None, or (s1, s2, b1, b2) of UNet2DConditionModel.enable_freeu -- on / off is part of the plan key (the
         plan gains one pp_freeu launch per resnet of up blocks 0 and 1), the values live in device memory the launches read.
         ip_n: images per loaded IP-Adapter in this call's embeds, (images, hidden states per image) for a Plus adapter (part of
         the key only while adapters are loaded).
@@ -256,6 +261,11 @@ class NetRuntime:
         tm = getattr(getattr(self, "net", None), "tome", None)
         if tm is not None:                                       # (without token merging: the key of a plan that never had it)
             key += (("tome", tuple(tm)),)
+        if pag is not None:
+            if tm is not None and tm.ratio > 0:
+                from .pag import check_supported
+                check_supported(tome=True)
+            key += (("pag", tuple(pag.layers), int(pag.n)),)
         if isinstance(scale, (list, tuple)):
             scale = tuple(float(v) for v in scale)       # (one representation: a list never equals the stored tuple)
         if key == self.key:
@@ -269,11 +279,11 @@ class NetRuntime:
         self._tome_row = C.c_void_p(0)
         dry = Arena()
         self._build(dry, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None, ip_n,
-                    bool(ip_masked))
+                    bool(ip_masked), pag)
         self.arena = Arena(_align(dry.peak, 4096), self.device)
         self.lay, self.setup_plan, self.step_plan, self.outputs = self._build(
             self.arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None, ip_n,
-            bool(ip_masked))
+            bool(ip_masked), pag)
         self.twin = bool(twin)
         self.pad_uncond = bool(pad_uncond)
         self.key = key
