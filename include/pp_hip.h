@@ -986,6 +986,28 @@ int pp_tome_unmerge(const void* a, int lda, const void* pos, int batch, int n, i
 int pp_attn_identity_v(const void* vt, int ldvt, int batch0, int batch, int n, int C, void* out, int ldo, void* stream);
 int pp_pag_combine(float* eps, int cfg, float guidance, const float* pag_table, const int32_t* step_dev, int n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * guidance_rescale (added under ABI 29: purely additive).  diffusers' `rescale_noise_cfg` (Lin et al., "Common Diffusion
+ * Noise Schedules and Sample Steps are Flawed", section 3.4): the guided prediction of every sample is pulled back to the
+ * standard deviation of that sample's conditional prediction.  No counterpart in the reference.
+ *
+ * pp_cfg_rescale: eps fp32 [segs][batch][per], the `per` = C*H*W values of one sample contiguous.  segs = 2: (e_u, e_c),
+ *   pag_table NULL (step_dev is not read and may be NULL).  segs = 3: (e_u, e_c, e_p), pag_table non-NULL and
+ *   s = pag_table[step_dev[0]] as pp_pag_combine reads it (step_dev read and NOT moved).  phi = phi_dev[0]: one fp32 in
+ *   device memory, read by the launch (a captured graph sees the value the cell holds when it is replayed).  With
+ *       m = e_u + guidance * (e_c - e_u)  [+ s * (e_c - e_p)]            (the step kernels' / pp_pag_combine's expression)
+ *       SSD(x[b]) = sum_i (x[b][i] - mean(x[b]))^2                        (two passes: the mean first; never sum x^2)
+ *   segment 0 of sample b becomes, in place,   m * (phi * sqrt(SSD(e_c[b]) / SSD(m[b])) + (1 - phi)).
+ *   Only the ratio of the two deviations enters, so torch.std's n - 1 cancels.  A sample whose m has no variance divides by
+ *   0, as the library does.  The other segments, the table, the cell and the counter are not written.  The scheduler's step
+ *   launch behind it runs with cfg = 0 on segment 0.
+ *   One launch, one workgroup per sample, no atomics: a sample's result depends on its own values, on `per` and on whether
+ *   the 16-byte path is taken (per % 4 == 0 and eps 16-byte aligned) -- not on batch, on its index in the batch or on the run.
+ *   batch >= 1, per >= 2 (need not be a multiple of 4), eps 4-byte aligned; PP_ERR_BAD_ARG otherwise, and for segs outside
+ *   {2, 3}, segs = 3 without a table or step counter, segs = 2 with a table, NULL eps or phi_dev -- all without a launch. */
+int pp_cfg_rescale(float* eps, int segs, float guidance, const float* pag_table, const float* phi_dev, const int32_t* step_dev,
+                   int batch, int per, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

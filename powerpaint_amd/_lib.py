@@ -201,6 +201,7 @@ SIGNATURES = {
     "pp_tome_unmerge": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "pp_attn_identity_v": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "pp_pag_combine": (C.c_int, [vp, C.c_int, f32, vp, vp, C.c_int, vp]),
+    "pp_cfg_rescale": (C.c_int, [vp, C.c_int, f32, vp, vp, vp, C.c_int, C.c_int, vp]),
 }
 
 _lib = None

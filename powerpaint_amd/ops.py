@@ -794,3 +794,20 @@ def pag_combine(eps: torch.Tensor, cfg: bool, guidance: float, pag_table: torch.
     L.check(L.lib().pp_pag_combine(_p(eps), int(bool(cfg)), float(guidance), _p(pag_table), _p(step), eps[0].numel(), _s()),
             "pp_pag_combine")
     return eps
+
+
+def cfg_rescale(eps: torch.Tensor, guidance: float, phi_cell: torch.Tensor, pag_table: Optional[torch.Tensor] = None,
+                step: Optional[torch.Tensor] = None):
+    """pp_cfg_rescale, in place: eps fp32 [2 or 3 segments, batch, ...] contiguous, (e_u, e_c) or with `pag_table` (fp32 [rows],
+    `step` int32 [1] on the device) (e_u, e_c, e_p); phi_cell fp32 [1] on the device, read by the launch.  Segment 0 becomes
+    the guided prediction rescaled per sample (diffusers' rescale_noise_cfg)."""
+    segs = 3 if pag_table is not None else 2
+    if eps.dtype != torch.float32 or not eps.is_contiguous() or eps.dim() < 3 or eps.shape[0] != segs or \
+            phi_cell.dtype != torch.float32 or phi_cell.numel() != 1:
+        raise L.PPError(f"cfg_rescale: eps must be contiguous fp32 [{segs}, batch, ...], phi_cell one fp32")
+    if pag_table is not None and (pag_table.dtype != torch.float32 or step is None or step.dtype != torch.int32):
+        raise L.PPError("cfg_rescale: pag_table must be fp32 and come with the int32 step counter")
+    L.check(L.lib().pp_cfg_rescale(_p(eps), segs, float(guidance), _p(pag_table) if pag_table is not None else None,
+                                   _p(phi_cell), _p(step) if step is not None else None, eps.shape[1], eps[0, 0].numel(), _s()),
+            "pp_cfg_rescale")
+    return eps

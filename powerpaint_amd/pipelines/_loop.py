@@ -23,6 +23,11 @@ In front of the step launch pp_pag_combine writes  e_u + g (e_c - e_u) + s_i (e_
 a device table with one scale per schedule row, and the step launch runs with cfg = 0 on that segment.  The scales are data:
 a new scale pair reaches a captured graph without a re-capture.
 
+`guidance_rescale > 0` with CFG (powerpaint_amd/guidance.py, diffusers' rescale_noise_cfg): pp_cfg_rescale stands where
+pp_pag_combine stands (with PAG's table when PAG is on, replacing that launch): the combine, then per sample the factor
+phi sqrt(SSD(e_c) / SSD(combine)) + 1 - phi, into segment 0; the step launch runs with cfg = 0.  phi lives in a one-float
+device cell that `run` refills: a new value reaches a captured graph without a re-capture.  0, or no CFG: the program without it.
+
 Several ControlNets (`side` = a MultiControlNetModel, pipeline_PowerPaint_ControlNet.py:306,1678-1694): one runtime per
 net (own arena, time-embedding table, hoisted control-image embedding, twin-prefix decision); the step is
     head(net 0) .. head(net N-1), head(UNet), plan(net 0) .. plan(net N-1), plan(UNet), scheduler step
@@ -44,6 +49,7 @@ from typing import Callable, List, Optional
 import torch
 
 from .. import _lib as L
+from .. import guidance as GDM
 from .. import pag as PAGM
 from ..engine import Plan
 from ..schedulers import _SchedulerBase
@@ -80,7 +86,7 @@ class DenoiseLoop:
              static_inputs=(), side_static_inputs=(), controlnet_cond=None, side_scale: float = 1.0,
              guess_mode: bool = False, eta: float = 0.0, generator=None, noise_dtype=torch.float32, blend=None,
              timestep_cond=None, added_cond_kwargs=None, ip_adapter_masks=None, pag_scale: float = 0.0,
-             pag_adaptive_scale: float = 0.0):
+             pag_adaptive_scale: float = 0.0, guidance_rescale: float = 0.0):
         """Compile the per-step program.  latents_shape = (B, 4, h, w) of the *un-duplicated* latents.
         ip_adapter_masks: `cross_attention_kwargs["ip_adapter_masks"]` of the call, [adapters, 1, H, W]; the UNet only, as the
         image embeds.  Their values are device memory the UNet's launches read (NetRuntime.set_ip_masks): new masks of the
@@ -104,7 +110,9 @@ class DenoiseLoop:
         unconditional half of the UNet batch gets zeros.
         pag_scale > 0 (diffusers' PAGMixin): perturbed-attention guidance in the transformers `unet.pag_layers()`; per-call
         inputs arrive as without it (un-duplicated or as the CFG pair) and are laid out `[.., cond, cond]` here.  The scale
-        pair is no part of the plan key: `_fill_pag_table` writes one scale per schedule row into device memory."""
+        pair is no part of the plan key: `_fill_pag_table` writes one scale per schedule row into device memory.
+        guidance_rescale > 0 with do_cfg (diffusers' rescale_noise_cfg): pp_cfg_rescale in front of the step launch.  Whether it
+        is on is part of the key; its value is not: `run` writes it into a one-float device cell.  Without CFG: no effect."""
         B, sch = latents_shape[0], self.scheduler
         pag = float(pag_scale) > 0.0
         if pag:
@@ -163,6 +171,10 @@ class DenoiseLoop:
         self._pag = (float(pag_scale), float(pag_adaptive_scale)) if pag else None
         if pag:                                  # (the table's address is part of the key, the scales in it are not: `run` fills it)
             key += (("pag", 0 if self.foreign else self._pag_table_for(int(ts.numel()), ts.device).data_ptr()),)
+        self._rescale = GDM.check_guidance_rescale(guidance_rescale) if do_cfg else 0.0
+        self._rescale = self._rescale if self._rescale > 0.0 else None
+        if self._rescale is not None:            # (the cell's address is part of the key, phi in it is not: `run` fills it)
+            key += (("rescale", 0 if self.foreign else self._phi_cell_for(ts.device).data_ptr()),)
         if key == self._key and self.program is not None:
             # The conditioning scale is a by-value argument of the zero-conv launches: `prepare` has patched the launch
             # records (eager runs see it), but a graph captured with another value still carries the old one.
@@ -367,7 +379,15 @@ class DenoiseLoop:
             if self._noisy and (getattr(self, "_var_noise", None) is None or self._var_noise.shape != lat.shape):
                 self._var_noise = torch.zeros_like(lat)
             noise = self._var_noise if self._noisy else lat      # (a step that reads no noise: any valid address)
-            if self._pag is not None:
+            if self._rescale is not None:
+                # guidance_rescale (CFG is on): the combine -- PAG's three-way one with its table when PAG is on, in the place
+                # of pp_pag_combine -- and the per-sample rescale into segment 0; the step launch behind it runs with cfg = 0
+                B = lat.shape[0]
+                prog.add("cfg_rescale", lib.pp_cfg_rescale, rt.outputs["eps"], 3 if self._pag is not None else 2,
+                         float(guidance_scale), self._pag_table.data_ptr() if self._pag is not None else None,
+                         self._phi_cell.data_ptr(), step.data_ptr(), B, lat.numel() // B)
+                do_cfg = False
+            elif self._pag is not None:
                 # perturbed-attention guidance: the three-way (two-way) combine into segment 0 of eps, its scale read from this
                 # row of the table; the step launch behind it takes segment 0 as it is (cfg = 0)
                 prog.add("pag_combine", lib.pp_pag_combine, rt.outputs["eps"], int(do_cfg), float(guidance_scale),
@@ -404,6 +424,20 @@ class DenoiseLoop:
             self._pag_rows = PAGM.scale_rows(self._pag[0], self._pag[1], tsl)
             self._pag_table.copy_(torch.tensor(self._pag_rows, dtype=torch.float32))
             self._pag_filled = want
+
+    # ---- guidance_rescale: the one-float cell
+    def _phi_cell_for(self, device) -> torch.Tensor:
+        """fp32 [1] at a stable address (a captured graph reads it)."""
+        c = getattr(self, "_phi_cell", None)
+        if c is None or c.device != device:
+            self._phi_cell, self._phi_filled = torch.zeros(1, dtype=torch.float32, device=device), None
+        return self._phi_cell
+
+    def _fill_phi_cell(self):
+        """This call's guidance_rescale -> the device cell, when it changed."""
+        if self._rescale != self._phi_filled:
+            self._phi_cell.copy_(torch.tensor([self._rescale], dtype=torch.float32))
+            self._phi_filled = self._rescale
 
     def _assemble(self, multi, heads, skips, tail):
         """`self.program`: every head, every network's plan without the launches its head replaces, the tail.  Several
@@ -604,6 +638,8 @@ class DenoiseLoop:
         self._fill_temb_tables()
         if self._pag is not None:
             self._fill_pag_table(self._keep[0])
+        if self._rescale is not None:
+            self._fill_phi_cell()
         self.latents.copy_(latents.to(self.latents.device, torch.float32))
         ents, scale_schedule, varying = self._schedule(scale_schedule, num_steps)
         if ents is not None and use_graph:        # (every set's graph before the first step)
@@ -696,11 +732,15 @@ class DenoiseLoop:
             else:
                 self.program.run(stream)
             eps = self.rt.eps_tensor()
+            # (guidance_rescale is only ever on with CFG: the conditional prediction is the second segment of two or three)
+            text = eps.chunk(3 if self._pag is not None else 2)[1] if self._rescale is not None else None
             if self._pag is not None:
                 eps = PAGM.combine(eps, self._do_cfg, self._g, PAGM.scale_rows(self._pag[0], self._pag[1], [float(t)])[0])
             elif self._do_cfg:
                 eu, ec = eps.chunk(2)
                 eps = eu + self._g * (ec - eu)
+            if text is not None:
+                eps = GDM.rescale_noise_cfg(eps, text, self._rescale)
             lat = sch.step(eps, t, lat, **self._extra_step_kwargs, return_dict=False)[0].to(torch.float32)
             if self._blend is not None:                       # pipeline_PowerPaint.py:1025-1039, with the scheduler's own add_noise
                 x0, mk, nz = self._blend

@@ -9,6 +9,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import torch
 
 from ._base import PipelineBase, hip_mask_prep, prepare_mask_and_masked_image
+from .. import guidance as GDM
 from ._loop import DenoiseLoop
 from .image_processor import VaeImageProcessor
 
@@ -26,8 +27,9 @@ class StableDiffusionInpaintPipeline(PipelineBase):
             self.set_pag_applied_layers(pag_applied_layers)
 
     def check_inputs(self, prompt, height, width, strength, callback_steps, negative_prompt=None, prompt_embeds=None,
-                     negative_prompt_embeds=None):
-        """pipeline_PowerPaint.py:553-602."""
+                     negative_prompt_embeds=None, guidance_rescale=0.0):
+        """pipeline_PowerPaint.py:553-602; `guidance_rescale` (no counterpart there): a finite number >= 0."""
+        GDM.check_guidance_rescale(guidance_rescale)
         if strength < 0 or strength > 1:
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         if height % 8 != 0 or width % 8 != 0:
@@ -78,7 +80,7 @@ class StableDiffusionInpaintPipeline(PipelineBase):
                  callback_steps: int = 1, cross_attention_kwargs: Optional[Dict[str, Any]] = None, task_class=None,
                  masked_image_latents: Optional[torch.FloatTensor] = None,
                  mask_latents: Optional[torch.FloatTensor] = None, pag_scale: float = 0.0,
-                 pag_adaptive_scale: float = 0.0):
+                 pag_adaptive_scale: float = 0.0, guidance_rescale: float = 0.0):
         self._refuse_ip_adapter_masks(cross_attention_kwargs)
         if task_class is not None:
             raise NotImplementedError("task_class is not used by the released checkpoints")
@@ -86,7 +88,7 @@ class StableDiffusionInpaintPipeline(PipelineBase):
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         prompt, negative_prompt = promptA, negative_promptA
         self.check_inputs(prompt, height, width, strength, callback_steps, negative_prompt, prompt_embeds,
-                          negative_prompt_embeds)
+                          negative_prompt_embeds, guidance_rescale=guidance_rescale)
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
         elif prompt is not None and isinstance(prompt, list):
@@ -145,7 +147,7 @@ class StableDiffusionInpaintPipeline(PipelineBase):
         self._loop.bind(shape, do_cfg, guidance_scale, prompt_embeds, static_inputs=[] if four else [(m, 4), (mil, 5)],
                         eta=eta, generator=generator, noise_dtype=self._noise_dtype(prompt_embeds),
                         blend=(image_latents, m, noise) if four else None, pag_scale=pag_scale,
-                        pag_adaptive_scale=pag_adaptive_scale)
+                        pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale)
         cb = None
         if callback is not None:
             def cb(i, t, lat):

@@ -12,6 +12,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import torch
 
 from .. import _lib as L
+from .. import guidance as GDM
 from .. import ip_adapter as IPA
 from .. import pag as PAGM
 from ._base import PipelineBase, hip_mask_prep, randn_tensor
@@ -240,6 +241,12 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
                 out.append(e)
         return out
 
+    def check_inputs(self, ip_adapter_image=None, ip_adapter_image_embeds=None, guidance_rescale=0.0):
+        """What this `__call__` checks before anything runs: the IP-Adapter branches of the reference's `check_inputs`, and
+        `guidance_rescale` (no counterpart there): a finite number >= 0."""
+        self._check_ip_inputs(ip_adapter_image, ip_adapter_image_embeds)
+        GDM.check_guidance_rescale(guidance_rescale)
+
     @staticmethod
     def _check_ip_inputs(ip_adapter_image, ip_adapter_image_embeds):
         """The IP-Adapter branches of `check_inputs`, pipeline_PowerPaint_Brushnet_CA.py:853-866."""
@@ -272,10 +279,10 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
                  conditioning_latents: Optional[torch.FloatTensor] = None,
                  prompt_embedsU: Optional[torch.FloatTensor] = None,
                  negative_prompt_embedsU: Optional[torch.FloatTensor] = None, pag_scale: float = 0.0,
-                 pag_adaptive_scale: float = 0.0, **kwargs):
+                 pag_adaptive_scale: float = 0.0, guidance_rescale: float = 0.0, **kwargs):
         callback = kwargs.pop("callback", None)
         callback_steps = kwargs.pop("callback_steps", 1)
-        self._check_ip_inputs(ip_adapter_image, ip_adapter_image_embeds)
+        self.check_inputs(ip_adapter_image, ip_adapter_image_embeds, guidance_rescale)
         # `cross_attention_kwargs` reaches the UNet only (:1430-1441): its `ip_adapter_masks` confine each adapter's image
         # prompt to a region (checked here, before anything runs; never dropped)
         ip_adapter_masks = (cross_attention_kwargs or {}).get("ip_adapter_masks")
@@ -373,7 +380,7 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
                         side_scale=scales[0], guess_mode=guess_mode, eta=eta, generator=generator,
                         noise_dtype=self._noise_dtype(prompt_embeds), timestep_cond=timestep_cond,
                         added_cond_kwargs=added_cond_kwargs, ip_adapter_masks=ip_adapter_masks, pag_scale=pag_scale,
-                        pag_adaptive_scale=pag_adaptive_scale)
+                        pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale)
         cb = None
         bad = [k for k in callback_on_step_end_tensor_inputs if k not in self._callback_tensor_inputs]
         if bad:                                                                              # check_inputs, :775-780

@@ -117,7 +117,7 @@ class StableDiffusionControlNetInpaintPipeline(StableDiffusionInpaintPipeline):
                  control_guidance_end: Union[float, List[float]] = 1.0,
                  masked_image_latents: Optional[torch.FloatTensor] = None,
                  mask_latents: Optional[torch.FloatTensor] = None, pag_scale: float = 0.0,
-                 pag_adaptive_scale: float = 0.0):
+                 pag_adaptive_scale: float = 0.0, guidance_rescale: float = 0.0):
         self._refuse_ip_adapter_masks(cross_attention_kwargs)
         multi = isinstance(self.controlnet, MultiControlNetModel)
         if multi:
@@ -141,7 +141,7 @@ class StableDiffusionControlNetInpaintPipeline(StableDiffusionInpaintPipeline):
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         prompt = promptA
         self.check_inputs(prompt, height, width, strength, callback_steps, negative_promptA, prompt_embeds,
-                          negative_prompt_embeds)
+                          negative_prompt_embeds, guidance_rescale=guidance_rescale)
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
         elif prompt is not None and isinstance(prompt, list):
@@ -209,7 +209,7 @@ class StableDiffusionControlNetInpaintPipeline(StableDiffusionInpaintPipeline):
                         static_inputs=[] if four else [(m, 4), (mil, 5)], controlnet_cond=control_image,
                         side_scale=bind_scale, guess_mode=guess_mode, eta=eta, generator=generator,
                         noise_dtype=self._noise_dtype(prompt_embeds), blend=(image_latents, m, noise) if four else None,
-                        pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale)
+                        pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale)
         cb = None
         if callback is not None:
             def cb(i, t, lat):
