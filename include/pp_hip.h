@@ -450,6 +450,24 @@ int pp_attention_log2_ok(int nq, int nk, int d);
 int pp_attention_fwd_variant(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo,
                              int batch, int heads, int nq, int nk, int d, float scale, int dtype, int variant,
                              void* stream);
+/* Tiled self-attention (HyperTile; entries added under ABI v29): the tokens of a batch item are an h x w grid in row-major
+ * order, cut into nh x nw tiles of th x tw = (h / nh) x (w / nw) tokens, and a query attends only to the keys of its own
+ * tile -- block-diagonal attention, one launch of the tiled form of attn_pipe_kernel.  Token r of tile (ty, tx) is row
+ * (ty*th + r / tw) * w + tx*tw + r % tw of its batch item.  Layouts exactly as pp_attention_fwd with nq = nk = h*w and
+ * ldvt >= h*w; `variant` takes the PP_ATTN_* codes: AUTO picks by the occupancy rule of pp_attention_fwd_variant computed on
+ * the tiled grid (batch * heads * nh * nw * ceil(th*tw / 256) >= 512 -> 64 queries per wave), PP_ATTN_PIPE_LOG2 expects the
+ * pre-multiplied q as above, PP_ATTN_PHASED has no tiled form (PP_ERR_UNSUPPORTED).
+ * pp_attention_tiled_ok(h, w, nh, nw, d) == 1 exactly where h % nh == 0, w % nw == 0, nh * nw > 1, the pipelined kernel
+ * takes (nq, nk, d) = (th*tw, th*tw, d) (pp_attention_log2_ok), and nw == 1 or tw % 32 == 0 (a 32-key half of an LDS tile
+ * then lies inside one run of tw contiguous rows); everywhere else pp_attention_fwd_tiled returns PP_ERR_UNSUPPORTED.
+ * Padding as pp_attention_fwd: columns [h*w, ldvt) of vt may hold any finite values.  Keys outside a query's tile are never
+ * loaded (so they may hold anything at all), nothing outside rows [0, batch*h*w) x columns [0, heads*d) of o is written, and
+ * every element inside is.  A bad argument (null or misaligned pointer strides, h % nh != 0, w % nw != 0, ldvt < h*w, an
+ * unknown variant or dtype) returns PP_ERR_BAD_ARG without a launch. */
+int pp_attention_tiled_ok(int h, int w, int nh, int nw, int d);
+int pp_attention_fwd_tiled(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo,
+                           int batch, int heads, int h, int w, int nh, int nw, int d, float scale, int variant,
+                           int dtype, void* stream);
 /* [rows = b*nk + t][cols] bf16 (row stride ld) -> vt[b][col][t] (row stride ldvt).  Used for the cross-attention V
  * (computed once per call: encoder_hidden_states are step-invariant) and as the unfused fallback for self-attention. */
 int pp_transpose_v(const void* v, int ld, int batch, int nk, int cols, void* vt, int ldvt, void* stream);

@@ -148,6 +148,9 @@ SIGNATURES = {
                                    C.c_int, C.c_int, f32, C.c_int, vp]),
     "pp_attention_fwd_variant": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_int, f32, C.c_int, C.c_int, vp]),
+    "pp_attention_tiled_ok": (C.c_int, [C.c_int] * 5),
+    "pp_attention_fwd_tiled": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_int, C.c_int, f32, C.c_int, C.c_int, vp]),
     "pp_transpose_v": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "pp_conv3x3_direct": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp,
                                     vp, C.c_int, vp]),

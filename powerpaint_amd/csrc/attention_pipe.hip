@@ -61,6 +61,19 @@ struct PCfg {
 
 constexpr float RESCALE_THR = 8.0f;
 
+// Tiled form (HyperTile, pp_attention_fwd_tiled): the tokens of a batch item are a grid of w columns cut into tiles of th x tw
+// tokens, and a workgroup's queries and keys are the nq = nk = th * tw tokens of ONE tile: token r of the tile is row
+// org + (r / tw) * w + r % tw of the batch item, org = the tile's first token.  The untiled form carries an empty struct.
+template <int TILED> struct PipeGeo {};
+template <> struct PipeGeo<1> {
+  int ntok;   // h * w: rows of a batch item in q / k / o
+  int w;      // grid width
+  int tw, th; // tile width / height
+  int nw;     // tiles per grid row
+  int nqb;    // query blocks (workgroups) per tile
+  int gap;    // rows between the end of a run of tw keys and the start of the tile's next run: w - tw (0: contiguous tiles)
+};
+
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // OPT (round 3; bit mask, PP_ATTN_OPT_DEFAULT ships):
@@ -83,11 +96,11 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 //      QK^T ones behind the running-max phase (the reference S(t+1) is baked with is the one P(t) uses), and the rare
 //      reference update (a lane's tile maximum more than RESCALE_THR above its reference; always at the first tile) fixes
 //      up the 16 scores per lane and block it arrived too late for, in a wave-uniform branch.  Needs bit 8.
-template <int D, int KB, int dbg, int EDT, int NW, int QB, int OPT>
+template <int D, int KB, int dbg, int EDT, int NW, int QB, int OPT, int TILED = 0>
 __global__ void __launch_bounds__(64 * NW, (KB == 32 && QB == 1 ? 4 : 2))
 attn_pipe_kernel(const uint16_t* __restrict__ q, int ldq, const uint16_t* __restrict__ k, int ldk,
                  const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ o, int ldo, int heads, int nq, int nk,
-                 float scale_log2e) {
+                 float scale_log2e, PipeGeo<TILED> geo) {
   // dbg (PP_ATTN_DBG, timing experiments only; results are garbage): 1 no MFMA, 2 no exp, 4 no tile DMA / barrier,
   // 8 no LDS fragment reads, 16 no output store
   constexpr int SUBS = (OPT & 16) ? 2 : 1;
@@ -105,7 +118,25 @@ attn_pipe_kernel(const uint16_t* __restrict__ q, int ldq, const uint16_t* __rest
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = blockIdx.y, b = blockIdx.z;
-  const int q0 = blockIdx.x * (QW * NW) + wave * QW;
+  // (tiled: blockIdx.x = tile * nqb + query block inside the tile; nq = nk = tokens of a tile, rows per batch item = ntok)
+  int qblk = blockIdx.x, org = 0, rows_b = nq, rows_kb = nk;
+  if constexpr (TILED) {
+    static_assert(KT == 64, "the tiled key walk moves in 32-key halves of a 64-key LDS tile");
+    const int tile = qblk / geo.nqb, ty = tile / geo.nw;
+    qblk -= tile * geo.nqb;
+    org = ty * geo.th * geo.w + (tile - ty * geo.nw) * geo.tw;
+    rows_b = rows_kb = geo.ntok;
+  }
+  // row of q / o (inside the batch item) of the wave's query `r`: the tile's token map
+  auto qtoken = [&](int r) {
+    if constexpr (TILED) {
+      const int ry = r / geo.tw;
+      return org + ry * geo.w + (r - ry * geo.tw);
+    } else {
+      return r;
+    }
+  };
+  const int q0 = qblk * (QW * NW) + wave * QW;
   const int qi = lane & 31, half = lane >> 5;
   const int ntiles = nk / KB;
 
@@ -125,7 +156,7 @@ attn_pipe_kernel(const uint16_t* __restrict__ q, int ldq, const uint16_t* __rest
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
     const int qrow = q0 + 32 * qb + qi;
-    const uint16_t* qp = q + ((size_t)b * nq + (qrow < nq ? qrow : 0)) * ldq + h * D;
+    const uint16_t* qp = q + ((size_t)b * rows_b + qtoken(qrow < nq ? qrow : 0)) * ldq + h * D;
 #pragma unroll
     for (int s = 0; s < C::DS; ++s) {
       const int dc = 16 * s + 8 * half;
@@ -140,27 +171,30 @@ attn_pipe_kernel(const uint16_t* __restrict__ q, int ldq, const uint16_t* __rest
   // carry an out-of-range source offset -> they write zeros, into a dummy KB of LDS when the whole instruction is dead.
   // Everything that changes from tile to tile is SCALAR state advanced with a handful of SALU ops per stage (descriptor
   // base / size, ring offsets) -- the per-stage bookkeeping must not eat the issue slots of the 2 waves per SIMD.
-  const uint16_t* k_bh = k + (size_t)b * nk * ldk + h * D;
+  const uint16_t* k_bh = k + (size_t)b * rows_kb * ldk + h * D;
   const uint16_t* vt_bh = vt + ((size_t)b * heads + h) * D * (size_t)ldvt;
   constexpr int LPK = (C::KI + NW - 1) / NW, LPV = (C::VI + NW - 1) / NW;
   static_assert(LPK + LPV == C::LPW || LPK + LPV <= C::LPW, "DMA split");
   int vo[LPK + LPV];
   int rel[LPK + LPV];       // LDS offset inside the ring slot, or -1: dead instruction -> dummy area   (wave-uniform)
+  bool hi[TILED ? LPK + LPV : 1];   // (tiled) a LIVE lane whose slot holds keys 32..63 of the LDS tile: the second 32-key half
 #pragma unroll
   for (int i = 0; i < LPK + LPV; ++i) {
     int off = (int)PP_OOB;
+    bool up = false;
     if (i < LPK) {
       const int g = i * NW + wave;
       const int L = 64 * g + lane, r = L / C::KSL, p = L - r * C::KSL;
-      if (g < C::KI && r < KT && p < D / 8) off = (r * ldk + p * 8) * 2;
+      if (g < C::KI && r < KT && p < D / 8) { off = (r * ldk + p * 8) * 2; up = r >= 32; }
       rel[i] = g < C::KI ? g * 1024 : -1;
     } else {
       const int g = (i - LPK) * NW + wave;
       const int L = 64 * g + lane, r = L / C::VSL, p = L - r * C::VSL;
-      if (g < C::VI && r < D && p < KT / 8) off = (r * ldvt + p * 8) * 2;
+      if (g < C::VI && r < D && p < KT / 8) { off = (r * ldvt + p * 8) * 2; up = p >= 4; }
       rel[i] = g < C::VI ? g * 1024 : -1;
     }
     vo[i] = off;
+    if constexpr (TILED) hi[i] = up;
   }
   int kread = SUBS == 1 ? 1 : 0, vread = C::NVB - 1;   // ring slots stage 0 reads: K(1), V(-1)  (SUBS = 2: K(1) = 2nd half of tile 0)
   int kring = 0, vring = 0;                 // ring slots of the NEXT tile to issue
@@ -168,25 +202,53 @@ attn_pipe_kernel(const uint16_t* __restrict__ q, int ldq, const uint16_t* __rest
   // The descriptors never change: the tile advance is the scalar offset operand of the DMA (soffset is not part of the
   // range check, so dead lanes -- voffset out of range -- still read zeros), and the two look-ahead issues past the last
   // tile get a zero-sized descriptor.  ~20 SALU instructions per stage instead of ~45: the SIMD is issue-bound.
-  const uint32_t kbytes = (uint32_t)((nk - 1) * ldk + D) * 2u, vbytes = (uint32_t)D * (uint32_t)ldvt * 2u;
+  // Tiled: the descriptors span the batch item's K rows / the head's V^T rows as before.  The per-lane offsets stay
+  // loop-invariant and relative to the first key of the LDS tile; the walk over the tile's runs is scalar: `wtok` / `wcol` =
+  // the next 32-key half's first token (row of K, column of V^T) and its column inside the run.  A half never straddles a
+  // run (tw % 32 == 0, or gap == 0), so an LDS tile is the half at soffset plus a second half `xtra` rows further than the
+  // 32 a contiguous tile would put it (0, or `gap` where the run ended between the halves): added to the lanes of the
+  // second half only.  Largest live address: the tile's last token < ntok (K row) <= ldvt (V^T column); the range check
+  // sees voffset alone, vo + xtra <= ((63 + gap) * ldk + D) * 2 < kbytes and (39 * ldvt + 64 + gap) * 2 <= vbytes.
+  const uint32_t kbytes = (uint32_t)((rows_kb - 1) * ldk + D) * 2u, vbytes = (uint32_t)D * (uint32_t)ldvt * 2u;
   const int kstep = KT * ldk * 2, vstep = KT * 2;
   int ksoff = 0, vsoff = 0;
+  int wtok = org, wcol = 0, kxtra = 0, vxtra = 0;
+  auto half_step = [&]() {
+    if constexpr (TILED) {
+      wtok += 32;
+      wcol += 32;
+      if (wcol >= geo.tw) { wcol -= geo.tw; wtok += geo.gap; }
+    }
+  };
   auto issue = [&]() {
     const bool live = t_issue * SUBS < ntiles;      // (t_issue counts LDS tiles)
+    if constexpr (TILED) {
+      const int tok0 = wtok;
+      half_step();
+      const int x = wtok - tok0 - 32;
+      half_step();
+      ksoff = tok0 * ldk * 2;
+      vsoff = tok0 * 2;
+      kxtra = x * ldk * 2;
+      vxtra = x * 2;
+    }
     const __amdgpu_buffer_rsrc_t rs_k = make_rsrc(k_bh, live ? kbytes : 0u);
     const __amdgpu_buffer_rsrc_t rs_v = make_rsrc(vt_bh, live ? vbytes : 0u);
     char* kdst = smem + kring * C::KTILE;
     char* vdst = smem + C::VBASE + vring * C::VTILE;
 #pragma unroll
     for (int i = 0; i < LPK + LPV; ++i) {
-      const int voff = vo[i];
+      int voff = vo[i];
+      if constexpr (TILED) voff = hi[i] ? voff + (i < LPK ? kxtra : vxtra) : voff;
       char* dst = rel[i] < 0 ? smem + C::DUMMY : (i < LPK ? kdst : vdst) + rel[i];
       if (i < LPK) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_k, (lds_ptr_t)dst, 16, voff, ksoff, 0, 0);
       else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_v, (lds_ptr_t)dst, 16, voff, vsoff, 0, 0);
     }
     ++t_issue;
-    ksoff += kstep;
-    vsoff += vstep;
+    if constexpr (!TILED) {
+      ksoff += kstep;
+      vsoff += vstep;
+    }
     kring = kring + 1 == C::NKB ? 0 : kring + 1;
     vring = vring + 1 == C::NVB ? 0 : vring + 1;
   };
@@ -478,7 +540,7 @@ attn_pipe_kernel(const uint16_t* __restrict__ q, int ldq, const uint16_t* __rest
     const float inv = 1.0f / l_tot;
     const int qrow = q0 + 32 * qb + qi;
     if (qrow < nq) {
-      uint16_t* op = o + ((size_t)b * nq + qrow) * ldo + h * D;
+      uint16_t* op = o + ((size_t)b * rows_b + qtoken(qrow)) * ldo + h * D;
 #pragma unroll
       for (int dt = 0; dt < C::DT; ++dt)
 #pragma unroll
@@ -518,8 +580,33 @@ static int launch_pipe(const void* q, int ldq, const void* k, int ldk, const voi
     return PP_ERR_LAUNCH;
   const dim3 grid((nq + 32 * QB * NW - 1) / (32 * QB * NW), heads, batch), block(64 * NW);
   hipLaunchKernelGGL((attn_pipe_kernel<D, KB, DBG, EDT, NW, QB, OPT>), grid, block, C::LDS, st, (const uint16_t*)q, ldq,
-                     (const uint16_t*)k, ldk, (const uint16_t*)vt, ldvt, (uint16_t*)o, ldo, heads, nq, nk, sl2);
+                     (const uint16_t*)k, ldk, (const uint16_t*)vt, ldvt, (uint16_t*)o, ldo, heads, nq, nk, sl2, PipeGeo<0>{});
   PP_CHECK_LAUNCH("attn_pipe_kernel");
+  return PP_OK;
+}
+
+// The tiled form of the same instantiation: nh x nw tiles of an h x w token grid, grid.x = tiles * query blocks per tile.
+template <int KB, int EDT, int QB, int OPT>
+static int launch_pipe_tiled(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo,
+                             int batch, int heads, int h, int w, int nh, int nw, float sl2, hipStream_t st) {
+  constexpr int D = 40, NW = 4;
+  using C = PCfg<D, KB, NW, (OPT & 16) ? 2 : 1>;
+  if (pp_func_lds(reinterpret_cast<const void*>(attn_pipe_kernel<D, KB, 0, EDT, NW, QB, OPT, 1>), C::LDS,
+                  "hipFuncSetAttribute(attention pipe, tiled)") != PP_OK)
+    return PP_ERR_LAUNCH;
+  PipeGeo<1> geo;
+  geo.ntok = h * w;
+  geo.w = w;
+  geo.tw = w / nw;
+  geo.th = h / nh;
+  geo.nw = nw;
+  const int nt = geo.th * geo.tw;
+  geo.nqb = (nt + 32 * QB * NW - 1) / (32 * QB * NW);
+  geo.gap = w - geo.tw;
+  const dim3 grid(nh * nw * geo.nqb, heads, batch), block(64 * NW);
+  hipLaunchKernelGGL((attn_pipe_kernel<D, KB, 0, EDT, NW, QB, OPT, 1>), grid, block, C::LDS, st, (const uint16_t*)q, ldq,
+                     (const uint16_t*)k, ldk, (const uint16_t*)vt, ldvt, (uint16_t*)o, ldo, heads, nt, nt, sl2, geo);
+  PP_CHECK_LAUNCH("attn_pipe_kernel (tiled)");
   return PP_OK;
 }
 
@@ -612,5 +699,42 @@ int pp_attention_pipe_launch(const void* q, int ldq, const void* k, int ldk, con
   }
   if (dtype == PP_DT_F16) return launch_pipe<64, 0, PP_DT_F16>(PP_ARGS);
   return launch_pipe<64, 0, PP_DT_BF16>(PP_ARGS);
+#undef PP_ARGS
+}
+
+// ---- tiled self-attention (HyperTile): include/pp_hip.h, pp_attention_fwd_tiled
+extern "C" int pp_attention_tiled_ok(int h, int w, int nh, int nw, int d) {
+  if (h <= 0 || w <= 0 || nh <= 0 || nw <= 0 || h % nh || w % nw || (long long)nh * nw <= 1) return 0;
+  const long long nt = (long long)(h / nh) * (w / nw);
+  if (nt > 0x7fffffff || !pp_attention_log2_ok((int)nt, (int)nt, d)) return 0;      // what the pipelined kernel takes today
+  return (nw == 1 || (w / nw) % 32 == 0) ? 1 : 0;      // a 32-key half of an LDS tile never straddles a run
+}
+
+extern "C" int pp_attention_fwd_tiled(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o,
+                                      int ldo, int batch, int heads, int h, int w, int nh, int nw, int d, float scale,
+                                      int variant, int dtype, void* stream) {
+  if (!q || !k || !vt || !o || batch <= 0 || heads <= 0 || h <= 0 || w <= 0 || nh <= 0 || nw <= 0 || !pp_dt_ok(dtype))
+    return PP_ERR_BAD_ARG;
+  if (h % nh || w % nw || (long long)h * w > 0x7fffffff) return PP_ERR_BAD_ARG;
+  if (ldq % 8 || ldk % 8 || ldvt % 8 || ldo % 4 || ldq <= 0 || ldk <= 0 || ldo <= 0 || ldvt < h * w) return PP_ERR_BAD_ARG;
+  if (variant < PP_ATTN_AUTO || variant > PP_ATTN_PIPE_LOG2) return PP_ERR_BAD_ARG;
+  if (variant == PP_ATTN_PHASED || !pp_attention_tiled_ok(h, w, nh, nw, d)) return PP_ERR_UNSUPPORTED;
+  // (the key walk keeps byte offsets of a batch item's K rows in 32-bit scalars, as the untiled kernel does)
+  if ((long long)h * w * ldk * 2 > 0x7fffffffLL) return PP_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const float sl2 = scale * 1.4426950408889634f;
+  const int nt = (h / nh) * (w / nw);
+  // the occupancy rule of pp_attention_pipe_launch on the tiled grid: every tile is a batch item of its own
+  const long long wg2 = (long long)batch * heads * nh * nw * ((nt + 255) / 256);
+  const bool log2q = variant == PP_ATTN_PIPE_LOG2;
+  const bool q64 = variant == PP_ATTN_PIPE_Q64 || ((variant == PP_ATTN_AUTO || log2q) && wg2 >= 512);
+  constexpr int P64 = PP_ATTN_OPT_DEFAULT, P32 = PP_ATTN_OPT_DEFAULT & ~16;
+#define PP_ARGS q, ldq, k, ldk, vt, ldvt, o, ldo, batch, heads, h, w, nh, nw, sl2, st
+  if (log2q) {
+    if (q64) PP_DT_SWITCH(dtype, return (launch_pipe_tiled<32, EDT, 2, P64 | 64>(PP_ARGS)));
+    PP_DT_SWITCH(dtype, return (launch_pipe_tiled<64, EDT, 1, P32 | 64>(PP_ARGS)));
+  }
+  if (q64) PP_DT_SWITCH(dtype, return (launch_pipe_tiled<32, EDT, 2, P64>(PP_ARGS)));
+  PP_DT_SWITCH(dtype, return (launch_pipe_tiled<64, EDT, 1, P32>(PP_ARGS)));
 #undef PP_ARGS
 }

@@ -575,6 +575,19 @@ class Builder:
         self.plan.count("attention", 4.0 * B * heads * nq * nk * d)
         return out
 
+    def attention_tiled(self, q: int, ldq: int, k: int, ldk: int, vt: int, ldvt: int, B: int, heads: int, h: int, w: int,
+                        nh: int, nw: int, d: int, out: int = 0, ldo: int = 0, log2q: bool = False) -> int:
+        """Self-attention restricted to the nh x nw tiles of the h x w token grid (HyperTile: pp_attention_fwd_tiled, the tiled
+        form of the pipelined kernel): the same operands as `attention` with nq = nk = h * w, one launch, and 1 / (nh nw) of its
+        scores -- which is what the plan counts."""
+        Cc, n = heads * d, h * w
+        if not out:
+            out, ldo = self.alloc(B * n * Cc * 2), Cc
+        self.plan.add("attention", self.lib.pp_attention_fwd_tiled, q, ldq, k, ldk, vt, ldvt, out, ldo, B, heads, h, w, nh, nw,
+                      d, float(d) ** -0.5, L.PP_ATTN_PIPE_LOG2 if log2q else L.PP_ATTN_AUTO, self.dt)
+        self.plan.count("attention", 4.0 * B * heads * n * (n // (nh * nw)) * d)
+        return out
+
     def ip_attn_add(self, q: int, ldq: int, k_ip: int, v_ip: int, o: int, ldo: int, B: int, heads: int, nq: int, nk: int,
                     d: int, scale, row_w: int = 0):
         """IP-Adapter's image-prompt term added in place to a cross-attention output (csrc/ip_attn.hip): `scale` is a
@@ -736,6 +749,20 @@ class ToMeBlock(NamedTuple):
 TOME_TABLE_ROWS = 1000       # network evaluations of one pipeline call the window table holds
 
 
+class HyperTile(NamedTuple):
+    """Tiled self-attention at the top level (powerpaint_amd/hypertile.py, DESIGN.md "HyperTile"): the target tile size in
+    pixels.  Part of a plan's key."""
+    tile_size: int
+
+
+def hypertile_split(v: int, tile_size: int) -> int:
+    """Tiles along a latent side of v pixels: v // side, side = the smallest divisor of v that is >= min(T, v) with
+    T = max(32, tile_size) // 8 latent pixels (HyperTile's rule at swap_size = 1)."""
+    T = min(max(32, int(tile_size)) // 8, v)
+    side = next(s for s in range(T, v + 1) if v % s == 0)
+    return v // side
+
+
 class PAG(NamedTuple):
     """Perturbed-attention guidance on a UNet (powerpaint_amd/pag.py, DESIGN.md "Perturbed-attention guidance"): the
     transformers whose self-attention is the identity for the LAST `n` batch items.  Part of a plan's key; the scales are not
@@ -845,6 +872,17 @@ class _TransformerBlock:
         Cc, hw, B, d = x.C, self.hw, x.B, x.C // net.heads
         r = self.tome_r()
         pg = net._pag_step
+        ht = (net._ht_step or {}).get(self.pre)
+        if ht is not None and ht[2]:
+            # HyperTile: the same operands, the tiled entry; under PAG on the leading batch items, as the untiled launch is
+            if r:
+                raise L.PPError(f"{self.pre}: HyperTile together with token merging (ToMe) is not implemented")
+            perturbed = pg.n if pg is not None and self.pre in pg.layers else 0
+            a = pb.attention_tiled(qk, ldqk, qk + 2 * Cc, ldqk, vt, ldvt, B - perturbed, net.heads, x.H, x.W, ht[0], ht[1], d,
+                                   out=pb.alloc(B * hw * Cc * 2), ldo=Cc, log2q=log2q)
+            if perturbed:
+                pb.plan.add("attn_identity_v", pb.lib.pp_attn_identity_v, vt, ldvt, B - perturbed, perturbed, hw, Cc, a, Cc)
+            return a
         if pg is not None and self.pre in pg.layers:
             # perturbed-attention guidance: softmax attention on the leading batch items (same pointers, smaller batch); for the
             # trailing pg.n items attn1's output is V itself, copied out of V^T into the same buffer
@@ -1091,6 +1129,37 @@ class SDNet:
 
     _tome_step: Optional[Dict[str, object]] = None
     _pag_step: Optional[PAG] = None  # perturbed-attention guidance of the step plan being built (build_step(pag=...))
+    _ht_step: Optional[Dict[str, Tuple[int, int, bool, str]]] = None   # hypertile_layout of the step plan being built
+    hypertile: Optional[HyperTile] = None   # tiled top-level self-attention (powerpaint_amd/hypertile.py)
+
+    def hypertile_layout(self, H: int, W: int) -> Dict[str, Tuple[int, int, bool, str]]:
+        """THE place that decides which self-attentions run tiled on an H x W latent: {prefix: (nh, nw, tiled, reason)} over
+        every transformer in execution order ({} without the patch).  A block tiles when its token grid is the latent grid
+        itself (depth 0), the rule gives more than one tile and pp_attention_tiled_ok takes the geometry; `reason` says which
+        of these failed."""
+        t = self.hypertile
+        if t is None:
+            return {}
+        n = len(self.boc)
+        sizes = level_sizes(H, W, n)
+        out = {}
+        for pre, c in self._attn_specs():
+            part = pre.split(".")
+            lvl = n - 1 if part[0] == "mid_block" else (int(part[1]) if part[0] == "down_blocks" else n - 1 - int(part[1]))
+            h, w = sizes[lvl]
+            d = c // self.heads
+            if lvl != 0 or (h, w) != (H, W):
+                out[pre] = (1, 1, False, f"depth {lvl}: only the blocks on the latent grid itself are tiled (max_depth = 0)")
+                continue
+            nh, nw = hypertile_split(h, t.tile_size), hypertile_split(w, t.tile_size)
+            if nh * nw == 1:
+                out[pre] = (1, 1, False, f"the rule leaves a {h}x{w} latent in one tile at tile_size {t.tile_size}")
+            elif not L.lib().pp_attention_tiled_ok(h, w, nh, nw, d):
+                out[pre] = (nh, nw, False, f"{nh}x{nw} tiles of {h // nh}x{w // nw} tokens at head dim {d} are outside "
+                                           f"pp_attention_tiled_ok (include/pp_hip.h)")
+            else:
+                out[pre] = (nh, nw, True, "tiled")
+        return out
     tome: Optional[ToMe] = None      # token merging (powerpaint_amd/tome.py: apply_patch / remove_patch)
 
     def tome_layout(self, H: int, W: int) -> Tuple[Dict[str, ToMeBlock], int]:
@@ -1867,6 +1936,9 @@ class SDNet:
         # holds the pointer to the device word naming the row, per block the persistent (best_dst, score, pos) buffers, and
         # (filled in here) the batch each block runs on
         self._tome_step = tome
+        if self.hypertile is not None and tome and tome.get("layout"):
+            raise L.PPError("HyperTile together with token merging (ToMe) on the same network is not implemented")
+        self._ht_step = self.hypertile_layout(H, W) or None
         brush = add_down is not None
         add_down = list(add_down) if brush else None
         add_up = list(add_up) if brush else None

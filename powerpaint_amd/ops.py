@@ -477,6 +477,18 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, batch: int, he
     return o
 
 
+def attention_tiled(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, batch: int, heads: int, h: int, w: int, nh: int,
+                    nw: int, d: int, scale: Optional[float] = None, variant: int = L.PP_ATTN_AUTO,
+                    out: Optional[torch.Tensor] = None, ldo: Optional[int] = None):
+    """Self-attention inside the nh x nw tiles of an h x w token grid (pp_attention_fwd_tiled): operands as `attention` with
+    nq = nk = h * w.  Shapes: pp_attention_tiled_ok(h, w, nh, nw, d); anything else raises."""
+    o = _attn_out(out, ldo, batch * h * w, heads * d, q)
+    L.check(L.lib().pp_attention_fwd_tiled(_p(q), q.stride(0), _p(k), k.stride(0), _p(vt), vt.stride(1), _p(o), o.stride(0),
+                                           batch, heads, h, w, nh, nw, d, scale if scale is not None else d ** -0.5,
+                                           int(variant), L.dtype_code(q.dtype), _s()), "pp_attention_fwd_tiled")
+    return o
+
+
 def xattn_fold(k: torch.Tensor, vt: torch.Tensor, batch: int, nctx: int, heads: int, wq: torch.Tensor, wo: torch.Tensor,
                q_colsum=None, q_bias=None, scale: Optional[float] = None, kperm=False, gt=None, gcs=None, gbias=None,
                ht=None):

@@ -261,6 +261,11 @@ class NetRuntime:
         tm = getattr(getattr(self, "net", None), "tome", None)
         if tm is not None:                                       # (without token merging: the key of a plan that never had it)
             key += (("tome", tuple(tm)),)
+        ht = getattr(getattr(self, "net", None), "hypertile", None)
+        if ht is not None:                                       # (without HyperTile: the key of a plan that never had it)
+            if tm is not None:
+                raise L.PPError("HyperTile together with token merging (ToMe) on the same network is not implemented")
+            key += (("hypertile", tuple(ht)),)
         if pag is not None:
             if tm is not None and tm.ratio > 0:
                 from .pag import check_supported
