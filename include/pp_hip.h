@@ -1026,6 +1026,43 @@ int pp_pag_combine(float* eps, int cfg, float guidance, const float* pag_table, 
 int pp_cfg_rescale(float* eps, int segs, float guidance, const float* pag_table, const float* phi_dev, const int32_t* step_dev,
                    int batch, int per, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * (added under ABI 29; purely additive) AsymmetricAutoencoderKL -- the mask-conditioned VAE decoder of diffusers-0.27
+ * (autoencoder_asym_kl.py; vae.py: MaskConditionEncoder / MaskConditionDecoder; Zhu et al., arXiv:2306.04632).
+ *
+ * pp_conv4x4s2: nn.Conv2d(cin, cout, kernel_size=4, stride=2, padding=1) (layers 2..4 of the condition encoder) as an implicit
+ *   GEMM on the matrix cores over all sixteen taps: 16 cin cout MACs per output pixel (+ the padding of the 128 x 128 tiles).
+ *     x    : 16-bit NHWC [batch][hin][win][cin], 16-byte aligned, cin % 64 == 0, hin, win >= 2
+ *     w    : 16-bit [cout][16 cin], column (4 ky + kx) cin + c; 16-byte aligned; cout % 4 == 0
+ *     bias : fp32 [cout] or NULL, added to the fp32 accumulator before the one rounding
+ *     out  : 16-bit NHWC [batch][(hin - 2) / 2 + 1][(win - 2) / 2 + 1][cout], 8-byte aligned
+ *     relu_in != 0: the convolution reads max(x, 0) -- applied as the operand is loaded, x itself is not written (the
+ *       decoder's blends read the pre-ReLU tensor).  A NaN with the sign bit set is read as 0.
+ * pp_relu: out[i] = max(x[i], 0) over n 16-bit values (n % 8 == 0, 16-byte aligned, out may be x); the same sign-bit rule.
+ * pp_masked_image_pack: out[b][p][k] = (1 - mask[b][p]) * image[b][k][p] for k < c, 0 for c <= k < 8: fp32 NCHW image
+ *   [batch][c][h w] and fp32 mask [batch][h w] -> the 8-channel 16-bit NHWC image pp_conv3x3_direct reads (16-byte aligned).
+ *   c <= 8.  fp32 arithmetic, one rounding.
+ * pp_mask_blend: the blend in front of every up block of MaskConditionDecoder and behind the last,
+ *       out[b][y][x][k] = sample * m + cond * (1 - m),   m = mask[b][y * mask_h / h][x * mask_w / w]
+ *   (F.interpolate(mode="nearest") of the full-resolution mask; mask_h % h == 0 and mask_w % w == 0), computed as
+ *   fma(sample, m, cond * (1 - m)) in fp32 -- three roundings -- and rounded once to `dtype`.  Linear in m: any float mask.
+ *     sample, cond, out : 16-bit NHWC [batch][h][w][c], 16-byte aligned, c % 64 == 0; out may be sample
+ *     mask              : fp32 [batch][mask_h][mask_w], one plane per batch item
+ *     acc               : NULL, or int64 [batch][groups][2], c % groups == 0: the launch ADDS (sum, sum of squares) of the
+ *                         values it stored, per group, in the fixed point of PPGemmArgs.gn_acc (what pp_groupnorm_apply_acc
+ *                         reads): fp32 partial sums of 8 values per thread in a fixed order, then 64-bit integer atomics, so
+ *                         the result does not depend on the order of the workgroups.  No floating-point atomics.
+ *     cond == NULL      : nothing is blended or written; the launch only adds the statistics of `sample` to acc (the
+ *                         unconditioned decode takes its statistics on the same route, so that a mask of ones reproduces it
+ *                         bit for bit). */
+int pp_conv4x4s2(const void* x, int batch, int hin, int win, int cin, const void* w, const float* bias, int cout, int relu_in,
+                 void* out, int dtype, void* stream);
+int pp_relu(const void* x, void* out, long long n, int dtype, void* stream);
+int pp_masked_image_pack(const float* image, const float* mask, int batch, int c, int h, int w, void* out, int dtype,
+                         void* stream);
+int pp_mask_blend(const void* sample, const void* cond, const float* mask, void* out, int batch, int h, int w, int c,
+                  int mask_h, int mask_w, int64_t* acc, int groups, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

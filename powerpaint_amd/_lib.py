@@ -205,6 +205,10 @@ SIGNATURES = {
     "pp_attn_identity_v": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "pp_pag_combine": (C.c_int, [vp, C.c_int, f32, vp, vp, C.c_int, vp]),
     "pp_cfg_rescale": (C.c_int, [vp, C.c_int, f32, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "pp_conv4x4s2": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "pp_relu": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp]),
+    "pp_masked_image_pack": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "pp_mask_blend": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
 }
 
 _lib = None

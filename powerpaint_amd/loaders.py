@@ -64,6 +64,25 @@ def read_config(d: str) -> dict:
     return {k: v for k, v in cfg.items() if not k.startswith("_")}
 
 
+def config_class_name(d: str) -> str:
+    """`_class_name` of <d>/config.json ("" if the file does not say)."""
+    f = os.path.join(d, "config.json")
+    if not os.path.isfile(f):
+        raise L.PPError(f"{f} not found")
+    with open(f) as fh:
+        return json.load(fh).get("_class_name", "") or ""
+
+
+def load_vae(root: str, device="cuda", torch_dtype=None, subfolder: Optional[str] = "vae", revision=None):
+    """The VAE of a pipeline folder, by the `_class_name` of its config.json: `AsymmetricAutoencoderKL` (the mask-conditioned
+    decoder; computes in `torch_dtype` if that is a 16-bit format) or, for every other name, `AutoencoderKL` as before."""
+    from . import models as PM
+    if config_class_name(resolve_dir(root, subfolder, revision=revision)) == "AsymmetricAutoencoderKL":
+        return PM.AsymmetricAutoencoderKL.from_pretrained(root, subfolder=subfolder, device=device, torch_dtype=torch_dtype,
+                                                          revision=revision)
+    return PM.AutoencoderKL.from_pretrained(root, subfolder=subfolder, device=device, revision=revision)
+
+
 def load_model(model, filename: str, strict: bool = True, device="cpu") -> Tuple[list, list]:
     """`safetensors.torch.load_model` for the HIP models (and for nn.Modules): (missing, unexpected) keys."""
     sd = read_state_dict(filename)
@@ -96,7 +115,8 @@ class PretrainedMixin:
         cfg = read_config(d)
         cfg.update(kw)
         # torch_dtype = the 16-bit format the network computes in (the reference's default is fp16, app.py:548,559) for
-        # the networks that take one (UNet / BrushNet / ControlNet); fp32 / None -> bf16; VAE and CLIP tower: bf16
+        # the networks that take one (UNet / BrushNet / ControlNet / AsymmetricAutoencoderKL); fp32 / None -> bf16;
+        # AutoencoderKL and the CLIP towers: bf16
         import inspect
         import torch
         if torch_dtype in (torch.float16, torch.bfloat16) and "dtype" in inspect.signature(cls.__init__).parameters:
@@ -153,7 +173,7 @@ class PipelinePretrainedMixin:
             index = {k: v for k, v in json.load(fh).items() if not k.startswith("_")}
         loaders = {"unet": lambda: PM.UNet2DConditionModel.from_pretrained(root, subfolder="unet", device=device,
                                                                            torch_dtype=torch_dtype),
-                   "vae": lambda: PM.AutoencoderKL.from_pretrained(root, subfolder="vae", device=device),
+                   "vae": lambda: load_vae(root, device=device, torch_dtype=torch_dtype),
                    "text_encoder": lambda: PM.CLIPTextModel.from_pretrained(root, subfolder="text_encoder", device=device),
                    "image_encoder": lambda: PM.CLIPVisionModelWithProjection.from_pretrained(root, subfolder="image_encoder",
                                                                                              device=device),

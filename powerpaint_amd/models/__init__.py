@@ -1,3 +1,4 @@
+from .autoencoder_asym_kl import AsymmetricAutoencoderKL
 from .autoencoder_kl import AutoencoderKL
 from .BrushNet_CA import BrushNetModel
 from .clip_text import CLIPTextModel
@@ -5,5 +6,5 @@ from .clip_vision import CLIPVisionModelWithProjection
 from .controlnet import ControlNetModel, MultiControlNetModel
 from .unet_2d_condition import UNet2DConditionModel
 
-__all__ = ["BrushNetModel", "UNet2DConditionModel", "ControlNetModel", "MultiControlNetModel", "AutoencoderKL", "CLIPTextModel",
-           "CLIPVisionModelWithProjection"]
+__all__ = ["BrushNetModel", "UNet2DConditionModel", "ControlNetModel", "MultiControlNetModel", "AutoencoderKL",
+           "AsymmetricAutoencoderKL", "CLIPTextModel", "CLIPVisionModelWithProjection"]

@@ -448,13 +448,36 @@ class PipelineBase(PipelinePretrainedMixin):
             lat = vae.encode(image).latent_dist.sample(generator=generator)
         return vae.config.scaling_factor * lat
 
-    def _finish(self, latents, output_type, return_dict, prompt_dtype, generator=None):
+    def _decode_condition(self, init_image, mask, generator, device, dtype):
+        """The `condition_kwargs` of the reference's decode (pipeline_PowerPaint.py:1043-1049, pipeline_PowerPaint_ControlNet.py:
+        1317-1324): with an AsymmetricAutoencoderKL as `vae`, the preprocessed init image and the preprocessed mask go to
+        `decode`.  The reference also calls `_encode_vae_image(init_image, generator)` there and drops the result; all that call
+        leaves behind is the generator, advanced by the posterior's noise draw -- the draw is made (same shape, the dtype of this
+        VAE's moments, same per-item order for a list of generators) and discarded, the encoder does not run.  `dtype`: that of
+        the masked-image latents, which the reference casts both tensors to.  {} for every other VAE."""
+        from ..models.autoencoder_asym_kl import AsymmetricAutoencoderKL
+        vae = getattr(self, "vae", None)
+        if not isinstance(vae, AsymmetricAutoencoderKL) or init_image is None or mask is None:
+            return {}
+        dt = next(iter(vae.parameters())).dtype
+        init_image = init_image.to(device=device, dtype=dtype)
+        n, f = init_image.shape[0], vae._enc_scale
+        lat = (1, vae.config.latent_channels, init_image.shape[2] // f, init_image.shape[3] // f)
+        if isinstance(generator, list):
+            for i in range(n):
+                randn_tensor(lat, generator=generator[i], device=device, dtype=dt)
+        else:
+            randn_tensor((n,) + lat[1:], generator=generator, device=device, dtype=dt)
+        return {"image": init_image.clone(), "mask": mask.clone().to(device=device, dtype=dtype)}
+
+    def _finish(self, latents, output_type, return_dict, prompt_dtype, generator=None, condition=None):
+        """condition: callable -> the keyword arguments `vae.decode` gets on top (evaluated only when an image is decoded)."""
         if output_type != "latent":
             vae = getattr(self, "vae", None)
             if vae is None:
                 raise ValueError('no VAE registered: use output_type="latent"')
             image = vae.decode(latents.to(next(iter(vae.parameters())).dtype) / vae.config.scaling_factor,
-                               return_dict=False)[0]
+                               return_dict=False, **(condition() if condition is not None else {}))[0]
             ip = getattr(self, "image_processor", None)
             if ip is not None:
                 image = ip.postprocess(image, output_type=output_type, do_denormalize=[True] * image.shape[0])

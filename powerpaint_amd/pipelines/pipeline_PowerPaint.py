@@ -154,4 +154,5 @@ class StableDiffusionInpaintPipeline(PipelineBase):
                 if self._legacy_callback_row(i, len(timesteps), num_inference_steps) and i % callback_steps == 0:
                     callback(i, t, lat)
         out = self._loop.run(latents, len(timesteps), use_graph=self.use_graph, callback=cb, timesteps=timesteps)
-        return self._finish(out.clone(), output_type, return_dict, prompt_embeds.dtype)
+        return self._finish(out.clone(), output_type, return_dict, prompt_embeds.dtype,
+                            condition=lambda: self._decode_condition(init_image, mk, generator, device, mil.dtype))
