@@ -300,6 +300,8 @@ class Builder:
         self.gn_acc_used = 0
         # device word the in-kernel split-K combine counts placement violations in (NetRuntime.check_faults); 0 = none given
         self.fault_ptr = 0
+        # (name, Act[, accumulator pointer]) of block outputs, in plan order, for the builds that record them (vae.py)
+        self.taps: List[Tuple] = []
 
     # -- memory
     def alloc(self, nbytes: int) -> int:

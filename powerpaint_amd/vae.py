@@ -19,8 +19,23 @@ rotated by 180 degrees that is exactly a symmetric pad-1 stride-2 conv with 180-
 sizes), and every other layer commutes with the rotation once its 3x3 filters are rotated too.  So the encoder runs
 "upside down" on the stock conv kernel -- rotated input, all encoder filters rotated at pack time, moments rotated
 back -- instead of growing a new padding mode in the hot GEMM loader.  tests/test_vae.py checks the identity on CPU.
+
+Arena zero fill.  The runtimes allocate their arena zero-filled, and ONE buffer relies on it: the pad channels of `x_in`
+(channels [latent_channels, 8) of the latents, [in_channels, 8) of the image), which pp_nchw_to_nhwc never writes and
+pp_conv3x3_direct multiplies by the zero-padded rows of its weights.  Everything else a plan reads it has written before:
+the GroupNorm and split-K workspaces, K with its pad rows (S's pad columns, the only values computed from rows the K GEMM
+did not write, are never read: the softmax runs over n columns), the pad columns of P (pp_softmax_rows writes zeros) and of
+V^T (pp_transpose_v writes zeros), the four channels of the image buffer (conv_out's weights and bias are padded to 4 with
+zeros).  vae_asym.py adds nothing to the list: pp_masked_image_pack writes all 8 channels of `img8`, the runtime copies the
+whole mask planes, pp_zero_u64 clears the blend accumulators.  tests/test_vae_blocks_gpu.py runs every plan on an arena filled
+with NaNs outside its input buffers and requires the same bits.
+
+Taps.  Every build function records (name, Act) of each block output in `Builder.taps`, in plan order, under the state-dict
+prefix of the block (`decoder.mask_blend.<i>` with the accumulator pointer as a third entry for the blends; the decoder's image
+as an `_Image`); the runtimes keep the list of their build on the real arena as `lay["taps"]`.  No mark / release is taken at
+the top level of a build function, so every tap keeps its bytes until the plan ends.
 """
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -41,6 +56,19 @@ def _pad_to(t: torch.Tensor, dim: int, n: int) -> torch.Tensor:
 
 def _rot(w: torch.Tensor) -> torch.Tensor:
     return w.flip(2, 3)
+
+
+class _Image(NamedTuple):
+    """The decoder's output buffer as a tap: fp32 NCHW [B][C][H][W] (every other tap is an NHWC Act of the 16-bit format)."""
+    ptr: int
+    B: int
+    C: int
+    H: int
+    W: int
+
+    @property
+    def nbytes(self) -> int:
+        return self.B * self.C * self.H * self.W * 4
 
 
 class VAENet:
@@ -199,6 +227,7 @@ class VAENet:
         out = pb.new_act(x.B, x.H, x.W, cout)
         pb.plan.add("conv3x3_direct", pb.lib.pp_conv3x3_direct, x.ptr, x.B, x.H, x.W, x.C, self.P[name + ".weight"],
                     self.P[name + ".bias"], cout, 1, 0, None, out.ptr, pb.dt)
+        pb.taps.append((name, out))
         return out
 
     def _resnet(self, pb: Builder, pre: str, x: Act, cout: int) -> Act:
@@ -215,6 +244,7 @@ class VAENet:
             sc = x.ptr
         pb.conv3x3(h, P[f"{pre}.conv2.weight"], cout, P[f"{pre}.conv2.bias"], res1=sc, out=out)
         pb.release(m)
+        pb.taps.append((pre, out))
         return out
 
     def _attention(self, pb: Builder, pre: str, x: Act) -> Act:
@@ -247,6 +277,7 @@ class VAENet:
         pb.linear(o, x.rows, Cc, P[f"{pre}.to_out.0.weight"], Cc, P[f"{pre}.to_out.0.bias"], res1=x.ptr, out=out.ptr,
                   name="linear")
         pb.release(m)
+        pb.taps.append((pre, out))
         return out
 
     def _mid(self, pb: Builder, side: str, x: Act) -> Act:
@@ -268,10 +299,13 @@ class VAENet:
             if i != len(rev) - 1:
                 pre = f"decoder.up_blocks.{i}.upsamplers.0.conv"
                 x = pb.conv3x3(x, P[pre + ".weight"], c, P[pre + ".bias"], up=True)
+                pb.taps.append((pre, x))
         x = pb.groupnorm(x, P["decoder.conv_norm_out.weight"], P["decoder.conv_norm_out.bias"], EPS, True,
                          groups=self.groups)
+        pb.taps.append(("decoder.conv_norm_out", x))
         pb.plan.add("conv_out", pb.lib.pp_conv3x3_smallcout, x.ptr, x.B, x.H, x.W, x.C, P["decoder.conv_out.weight"],
                     P["decoder.conv_out.bias"], 4, out_nchw, pb.dt)
+        pb.taps.append(("decoder.conv_out", _Image(out_nchw, x.B, 4, x.H, x.W)))
         return (x.B, 4, x.H, x.W)
 
     def build_encode(self, pb: Builder, img: Act) -> Act:
@@ -286,9 +320,11 @@ class VAENet:
                     raise L.PPError("AutoencoderKL.encode: image sides must be multiples of 8")
                 pre = f"encoder.down_blocks.{i}.downsamplers.0.conv"
                 x = pb.conv3x3(x, P[pre + ".weight"], c, P[pre + ".bias"], stride=2)
+                pb.taps.append((pre, x))
         x = self._mid(pb, "encoder", x)
         x = pb.groupnorm(x, P["encoder.conv_norm_out.weight"], P["encoder.conv_norm_out.bias"], EPS, True,
                          groups=self.groups)
+        pb.taps.append(("encoder.conv_norm_out", x))
         x = self._direct(pb, x, "encoder.conv_out", 8)
         return self._direct(pb, x, "quant_conv", 8)
 
@@ -310,6 +346,7 @@ class VAERuntime:
             lay["shape"] = self.net.build_decode(pb, lay["x_in"], lay["img"])
         else:
             lay["moments"] = self.net.build_encode(pb, lay["x_in"])
+        lay["taps"] = pb.taps
         return lay, pb.plan
 
     def ensure(self, B: int, H: int, W: int):

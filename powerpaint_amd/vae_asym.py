@@ -26,7 +26,7 @@ import torch
 
 from . import _lib as L
 from .engine import Act, Arena, Builder, ParamPack, Plan, _align, _conv_igemm
-from .vae import EPS, _LEGACY, VAENet, _pad_to, _rot, _conv_direct
+from .vae import EPS, _LEGACY, VAENet, _Image, _pad_to, _rot, _conv_direct
 
 BLOCK_DOWN, BLOCK_UP = "DownEncoderBlock2D", "UpDecoderBlock2D"
 
@@ -242,6 +242,7 @@ class AsymVAENet(VAENet):
             sc = x.ptr
         pb.conv3x3(h, P[f"{pre}.conv2.weight"], cout, P[f"{pre}.conv2.bias"], res1=sc, out=out)
         pb.release(m)
+        pb.taps.append((pre, out))
         return out
 
     def _conv4x4(self, pb: Builder, x: Act, name: str, cout: int) -> Act:
@@ -250,6 +251,7 @@ class AsymVAENet(VAENet):
         pb.plan.add("conv4x4s2", pb.lib.pp_conv4x4s2, x.ptr, x.B, x.H, x.W, x.C, self.P[name + ".weight"],
                     self.P[name + ".bias"], cout, 1, out.ptr, pb.dt)
         pb.plan.count("conv4x4s2", 2.0 * out.rows * cout * 16 * x.C)       # all sixteen taps, nothing skipped
+        pb.taps.append((name, out))
         return out
 
     def build_condition(self, pb: Builder, img8: Act) -> List[Act]:
@@ -263,6 +265,7 @@ class AsymVAENet(VAENet):
         pb.plan.add("relu", pb.lib.pp_relu, l0.ptr, r0.ptr, l0.rows * l0.C, pb.dt)
         pb.conv3x3(r0, P[pre + "1.weight"], ch[1], P[pre + "1.bias"], out=l1)
         pb.release(m)
+        pb.taps.append((pre + "1", l1))
         l2 = self._conv4x4(pb, l1, pre + "2", ch[2])
         l3 = self._conv4x4(pb, l2, pre + "3", ch[3])
         l4 = self._conv4x4(pb, l3, pre + "4", ch[4])
@@ -297,6 +300,7 @@ class AsymVAENet(VAENet):
                 raise L.PPError(f"AsymmetricAutoencoderKL: no condition-encoder output of shape {(x.B, x.C, x.H, x.W)}")
             pb.plan.add("mask_blend", pb.lib.pp_mask_blend, x.ptr, c.ptr if cond else None, mask or None,
                         x.ptr if cond else None, x.B, x.H, x.W, x.C, mask_hw[0], mask_hw[1], acc, self.groups, pb.dt)
+            pb.taps.append((f"decoder.mask_blend.{i}", x, acc))      # in place: the tensor is the tap in front of it
             return acc
 
         for i, c in enumerate(rev):
@@ -307,10 +311,13 @@ class AsymVAENet(VAENet):
             if i != len(rev) - 1:
                 pre = f"decoder.up_blocks.{i}.upsamplers.0.conv"
                 x = pb.conv3x3(x, P[pre + ".weight"], c, P[pre + ".bias"], up=True)
+                pb.taps.append((pre, x))
         acc = blend(x, nb - 1)
         x = self._norm_acc(pb, x, "decoder.conv_norm_out", True, acc)
+        pb.taps.append(("decoder.conv_norm_out", x))
         pb.plan.add("conv_out", pb.lib.pp_conv3x3_smallcout, x.ptr, x.B, x.H, x.W, x.C, P["decoder.conv_out.weight"],
                     P["decoder.conv_out.bias"], 4, out_nchw, pb.dt)
+        pb.taps.append(("decoder.conv_out", _Image(out_nchw, x.B, 4, x.H, x.W)))
         return (x.B, 4, x.H, x.W)
 
     def build_encode(self, pb: Builder, img: Act) -> Act:
@@ -325,9 +332,11 @@ class AsymVAENet(VAENet):
                     raise L.PPError("AsymmetricAutoencoderKL.encode: image sides must be multiples of 2^(down blocks - 1)")
                 pre = f"encoder.down_blocks.{i}.downsamplers.0.conv"
                 x = pb.conv3x3(x, P[pre + ".weight"], c, P[pre + ".bias"], stride=2)
+                pb.taps.append((pre, x))
         x = self._mid(pb, "encoder", x)
         x = pb.groupnorm(x, P["encoder.conv_norm_out.weight"], P["encoder.conv_norm_out.bias"], EPS, True,
                          groups=self.groups)
+        pb.taps.append(("encoder.conv_norm_out", x))
         x = self._direct(pb, x, "encoder.conv_out", 8)
         return self._direct(pb, x, "quant_conv", 8)
 
@@ -348,6 +357,7 @@ class AsymVAERuntime:
         lay = {"x_in": Act(arena.alloc(B * H * W * 8 * 2), B, H, W, 8)}
         if self.direction == "encode":
             lay["moments"] = self.net.build_encode(pb, lay["x_in"])
+            lay["taps"] = pb.taps
             return lay, pb.plan
         lay["img"] = arena.alloc(B * 4 * (8 * H) * (8 * W) * 4)
         if self.direction == "decode_cond":
@@ -356,6 +366,7 @@ class AsymVAERuntime:
             lay["shape"] = self.net.build_decode(pb, lay["x_in"], lay["img"], lay["img8"], lay["mask"], (8 * H, 8 * W))
         else:
             lay["shape"] = self.net.build_decode(pb, lay["x_in"], lay["img"])
+        lay["taps"] = pb.taps
         return lay, pb.plan
 
     def ensure(self, B: int, H: int, W: int):

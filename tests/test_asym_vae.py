@@ -147,6 +147,28 @@ def test_plans_on_a_dry_arena():
     assert "four up blocks" in odd.condition_mismatch()
 
 
+def test_taps_name_every_block_and_keep_their_bytes():
+    """`lay["taps"]` of the three plans, default (x-1-5) and TINY configuration: the names are the structure lists' in plan
+    order (condition encoder first, a blend in front of every up block and behind the last), no tap's bytes are handed out
+    again behind it, and a blend's tap is the tensor in front of it with its accumulator slot, one slot per blend."""
+    from collections import defaultdict
+
+    import vae_cases as VC
+    from powerpaint_amd.vae_asym import AsymVAERuntime
+    for cfg in (AC.X15, AC.TINY):
+        net = net_of(cfg)
+        net.P = defaultdict(lambda: 1 << 30)                                # pointers only: nothing runs on a dry arena
+        s = 2 ** (len(cfg["down"]) - 1)
+        for direction, (B, H, W) in (("decode", (2, 4, 6)), ("decode_cond", (2, 4, 6)), ("encode", (2, 4 * s, 6 * s))):
+            lay, plan, log = VC.dry_build(AsymVAERuntime(net, "cpu", direction), B, H, W)
+            taps = lay["taps"]
+            assert [t[0] for t in taps] == VC.expected_tap_names(net, direction.split("_")[0], direction == "decode_cond")
+            assert VC.tap_layout_violations(taps, log) == []
+            accs = [t[2] for t in taps if len(t) == 3]
+            assert len(accs) == (0 if direction == "encode" else 5) and len(set(accs)) == len(accs)
+            assert [c[2] for c in plan.calls].count("mask_blend") == len(accs)
+
+
 def test_loader_dispatches_on_class_name(tmp_path):
     from powerpaint_amd import loaders, models as PM
     c = AC.TINY
