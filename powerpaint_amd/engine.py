@@ -225,6 +225,8 @@ class Plan:
         self.flops = 0.0                 # algorithmic FLOPs (2*MAC of conv/linear/attention matmuls)
         self.flops_by_kind: Dict[str, float] = {}  # FLOPs the launches EXECUTE, by launch name
         self.flops_skipped = 0.0         # part of `flops` no launch executes (sub-pixel upsampling convs: 5 of 9 taps)
+        self.walk = None                 # SDNet.build_step: the modules the walk ran ({"down", "up", "cache"}: DeepCache's index table)
+        self.zero_conv_pos = None        # shallow form of a side network: which _zero_conv_specs positions its zero convs are
 
     def add(self, name: str, fn, *args):
         self.calls.append((fn, args, name))
@@ -540,22 +542,25 @@ class Builder:
                 a.gn_dup_batch, a.gn_dup_mask = t.dup_half, a.gn_dup_mask | (1 << k)
         return acc
 
-    def freeu(self, h: Act, sk: Act, bs: int, groups: int) -> Tuple[Act, Act]:
+    def freeu(self, h: Act, sk: Act, bs: int, groups: int, h_out: Optional[Act] = None) -> Tuple[Act, Act]:
         """FreeU in front of an up-block resnet, ONE launch (csrc/freeu.hip): the first half of the hidden tensor's channels
         times b, the skip tensor through the four-bin Fourier filter with scale s; `bs` = device pointer to (b, s).  Both
         tensors are rewritten IN PLACE: inside a UNet step neither has another reader behind this point (the hidden tensor
         is the previous block's output, the skip tensor's down-path consumer ran long before), every replay recomputes them,
         and neither is an output or a residual slot.  The launch also adds the statistics of concat(hidden', skip') to a
-        fresh accumulator, which the returned Acts carry for the resnet's norm1 (_subscribe_gn_stats)."""
+        fresh accumulator, which the returned Acts carry for the resnet's norm1 (_subscribe_gn_stats).
+        h_out: where the hidden tensor must SURVIVE the launch (DeepCache's cached tensor, which later evaluations read again),
+        the scaled copy goes there instead."""
         assert (h.B, h.H, h.W) == (sk.B, sk.H, sk.W)
+        ho = h_out.ptr if h_out is not None else h.ptr
         Ct, nbytes, acc = h.C + sk.C, h.B * groups * 2 * 8, 0
         if GN_STATS_IN_EPILOGUE and self.gn_acc_cap and Ct % groups == 0 and self.gn_acc_used + nbytes <= self.gn_acc_cap:
             acc = self.gn_acc_base + self.gn_acc_used
             self.gn_acc_used += nbytes
-        self.plan.add("freeu", self.lib.pp_freeu, h.ptr, h.ptr, h.C, sk.ptr, sk.ptr, sk.C, h.B, h.H, h.W, bs, acc or None,
+        self.plan.add("freeu", self.lib.pp_freeu, h.ptr, ho, h.C, sk.ptr, sk.ptr, sk.C, h.B, h.H, h.W, bs, acc or None,
                       groups, self.dt)
         filled = (acc, groups) if acc else None
-        return (Act(h.ptr, h.B, h.H, h.W, h.C, gn_filled=filled), Act(sk.ptr, sk.B, sk.H, sk.W, sk.C, gn_filled=filled))
+        return (Act(ho, h.B, h.H, h.W, h.C, gn_filled=filled), Act(sk.ptr, sk.B, sk.H, sk.W, sk.C, gn_filled=filled))
 
     def layernorm(self, x: int, rows: int, Cc: int, gamma: int, beta: int, eps: float = 1e-5, out: int = 0) -> int:
         out = out or self.alloc(rows * Cc * 2)
@@ -763,6 +768,13 @@ def hypertile_split(v: int, tile_size: int) -> int:
     T = min(max(32, int(tile_size)) // 8, v)
     side = next(s for s in range(T, v + 1) if v % s == 0)
     return v // side
+
+
+class DeepCache(NamedTuple):
+    """DeepCache (powerpaint_amd/deepcache.py): `branch` = cache_branch_id, part of the plan key; `interval` = cache_interval, host
+    schedule only (which of the two plans an evaluation runs) and no part of any key."""
+    branch: int
+    interval: int = 3
 
 
 class PAG(NamedTuple):
@@ -1163,6 +1175,11 @@ class SDNet:
                 out[pre] = (nh, nw, True, "tiled")
         return out
     tome: Optional[ToMe] = None      # token merging (powerpaint_amd/tome.py: apply_patch / remove_patch)
+    deepcache: Optional[DeepCache] = None      # shallow evaluations on a cached deep feature (powerpaint_amd/deepcache.py)
+
+    def skip_count(self) -> int:
+        """n: the skip tensors of the down path -- conv_in's output, every down layer's, every downsampler's (SD-1.5: 12)."""
+        return 1 + sum(self.L + (i != len(self.boc) - 1) for i in range(len(self.boc)))
 
     def tome_layout(self, H: int, W: int) -> Tuple[Dict[str, ToMeBlock], int]:
         """THE place that decides which transformers merge tokens, and how many: -> ({prefix: ToMeBlock} in execution order,
@@ -1896,7 +1913,8 @@ class SDNet:
                    add_mid: int = 0, add_up: Optional[List[int]] = None, ctrl_down: Optional[List[int]] = None,
                    ctrl_mid: int = 0, scale: float = 1.0, pad_uncond: bool = False, twin: bool = False,
                    freeu: int = 0, b1_eff: int = 0, tome: Optional[Dict[str, object]] = None,
-                   pag: Optional[PAG] = None) -> Dict[str, object]:
+                   pag: Optional[PAG] = None, depth: int = 0,
+                   cached: Optional[Dict[str, object]] = None) -> Dict[str, object]:
         """Append one forward pass.  x_in: NHWC bf16 input (already channel-concatenated).  Returns outputs:
         unet -> {"eps": ptr fp32 NCHW}; brushnet -> {"down": [Act], "mid": Act, "up": [Act]}; controlnet likewise.
         pad_uncond (side networks): the pipelines' guess mode runs the side branch on the conditional half of a CFG pair
@@ -1920,9 +1938,27 @@ class SDNet:
         (NetRuntime.set_timestep_cond fills it).  0: the parameter's own bias.
         pag (unet): perturbed-attention guidance -- in the transformers pag.layers the self-attention of the LAST pag.n batch
         items is the identity (`_TransformerBlock.attend`: the attention launch on the leading items, one pp_attn_identity_v
-        launch for the rest); the CFG twin prefix is not taken.  None: the plan of a UNet without it."""
+        launch for the rest); the CFG twin prefix is not taken.  None: the plan of a UNet without it.
+        depth = k > 0 (DeepCache, DESIGN.md "DeepCache"; k = cache_branch_id + 1): with S[0..n-1] the skip tensors in the order
+        the down path makes them and U[0..n-1] the up layers in execution order, `c` is the hidden tensor handed to U[n-1-k],
+        every side-network add on it included.  Without `cached` this is the FULL form: today's walk, launch for launch, which
+        also returns where c lives ("cache": Act; with FreeU at that layer the scaled hidden tensor goes to a copy, so that c
+        itself survives).  With `cached` = the outputs the full form returned this is the SHALLOW form of the same walk: the
+        down loop stops behind S[k], the mid block is left out, the up loop starts at U[n-1-k] on an Act for c that has no
+        producer (its norm takes the statistics launch), and the results -- eps, or the zero convs of the live positions --
+        land where the full form puts them, so whoever is wired to the one is wired to the other."""
         P, lib = self.P, pb.lib
         B, H, W = x_in.B, x_in.H, x_in.W
+        n = self.skip_count()
+        shallow = cached is not None
+        if depth and not 1 <= depth <= n - 1:
+            raise L.PPError(f"DeepCache: cache_branch_id {depth - 1} is outside 0..{n - 2} of this {self.kind} ({n} skip tensors)")
+        if shallow and not depth:
+            raise L.PPError("build_step(cached=...) is the shallow form of a depth > 0 walk")
+        if depth and ((tome and tome.get("layout")) or pag is not None):
+            raise L.PPError("DeepCache together with token merging (ToMe) or perturbed-attention guidance (PAG) is not implemented")
+        first_up = n - 1 - depth if depth else 0      # index of the first up layer the shallow form runs
+        walk = {"down": ["conv_in"], "up": [], "cache": None}
         if pag is not None:
             known = [p for p, _ in self._attn_specs()]
             if self.kind != "unet":
@@ -1996,6 +2032,8 @@ class SDNet:
         # 3. down
         for i, typ in enumerate(self.down_types):
             for j in range(self.L):
+                if shallow and len(skips) > depth:        # (the shallow form: S[k] is made, nothing below it runs)
+                    break
                 pre = f"down_blocks.{i}.resnets.{j}"
                 has_attn = typ == "CrossAttnDownBlock2D"
                 r2 = pop(add_down)
@@ -2004,31 +2042,52 @@ class SDNet:
                     ap = f"down_blocks.{i}.attentions.{j}"
                     s = self._transformer(pb, ap, s, self.kv[ap], res2=r2, twin=twin and i == 0 and j == 0)
                 skips.append(s)
-            if i != len(boc) - 1:
+                walk["down"].append(pre)
+            if i != len(boc) - 1 and not (shallow and len(skips) > depth):
                 pre = f"down_blocks.{i}.downsamplers.0.conv"
                 s = pb.conv3x3(s, P[pre + ".weight"], boc[i], P[pre + ".bias"], stride=2, res2=pop(add_down),
                                name="conv3x3")
                 skips.append(s)
+                walk["down"].append(f"down_blocks.{i}.downsamplers.0")
 
         # 4. mid
-        s = self._resnet(pb, "mid_block.resnets.0", s, boc[-1], temb_all)
-        s = self._transformer(pb, "mid_block.attentions.0", s, self.kv["mid_block.attentions.0"])
-        mid_res = add_mid if brush else (ctrl_mid if ctrl_down is not None else 0)
-        s = self._resnet(pb, "mid_block.resnets.1", s, boc[-1], temb_all, res2=mid_res)
+        if not shallow:
+            s = self._resnet(pb, "mid_block.resnets.0", s, boc[-1], temb_all)
+            s = self._transformer(pb, "mid_block.attentions.0", s, self.kv["mid_block.attentions.0"])
+            mid_res = add_mid if brush else (ctrl_mid if ctrl_down is not None else 0)
+            s = self._resnet(pb, "mid_block.resnets.1", s, boc[-1], temb_all, res2=mid_res)
+        prev_name = "mid_block"               # the module whose output the next up layer takes (names the cache point)
 
-        def zero_convs(feats: List[Act]) -> List[Act]:
+        def zero_convs(feats: List[Optional[Act]]) -> List[Act]:
+            """One zero conv per tensor of `feats`, in _zero_conv_specs order.  Shallow form: a position that is not live holds
+            None and gets no launch; the live ones write the full form's output tensors (`cached`)."""
             specs = self._zero_conv_specs()
             mult = 2 if pad_uncond else 1
-            outs = [pb.new_act(mult * f.B, f.H, f.W, c) for (_, c), f in zip(specs, feats)]
-            if pad_uncond:           # one zeroing launch over the whole (contiguous) block of padded outputs
-                end = outs[-1].ptr + outs[-1].rows * outs[-1].C * 2
-                pb.plan.add("zero_u64", lib.pp_zero_u64, outs[0].ptr, (end - outs[0].ptr + 7) // 8)
+            if shallow:
+                outs = list(cached["down"]) + [cached["mid"]] + list(cached.get("up", []))
+                pb.plan.zero_conv_pos = [p for p, f in enumerate(feats) if f is not None]
+            else:
+                outs = [pb.new_act(mult * f.B, f.H, f.W, c) for (_, c), f in zip(specs, feats)]
+            if pad_uncond:           # one zeroing launch over every (contiguous) run of padded outputs that gets written
+                run = None
+                for p, (f, o) in enumerate(zip(list(feats) + [None], outs + [None])):
+                    if f is not None:
+                        run = (run[0] if run else o.ptr, o.ptr + o.rows * o.C * 2)
+                    elif run:
+                        pb.plan.add("zero_u64", lib.pp_zero_u64, run[0], (run[1] - run[0] + 7) // 8)
+                        run = None
             for (pre, c), f, o in zip(specs, feats, outs):
+                if f is None:
+                    continue
                 pb.linear(f.ptr, f.rows, c, P[pre + ".weight"], c, P[pre + ".bias"], scale=scale,
                           out=o.ptr + (f.rows * c * 2 if pad_uncond else 0), name="zero_conv")
             return outs
 
         if self.kind == "controlnet":
+            pb.plan.walk = walk
+            if shallow:              # the zero convs 0..k; no mid residual (the UNet's shallow form does not read it)
+                outs = zero_convs(skips + [None] * (n - len(skips)) + [None])
+                return {"down": outs[:-1], "mid": outs[-1]}
             outs = zero_convs(skips + [s])
             return {"down": outs[:-1], "mid": outs[-1]}
 
@@ -2040,27 +2099,51 @@ class SDNet:
                 new.append(o)
             skips = new
 
-        brush_down = list(skips)
-        brush_mid = s
-        brush_up: List[Act] = []
+        brush_down: List[Optional[Act]] = list(skips) + [None] * (n - len(skips))
+        brush_mid = None if shallow else s
+        brush_up: List[Optional[Act]] = []
 
         # 5. up
         rev = list(reversed(boc))
+        u = 0                                # index of the up layer: U[u] takes S[n-1-u]
+        cache_act = None
         for i, typ in enumerate(self.up_types):
             has_attn = typ == "CrossAttnUpBlock2D"
             for j in range(self.L + 1):
+                live = not shallow or u >= first_up
+                r2 = pop(add_up)
+                u += 1
+                if not live:                 # (the shallow form: this layer's output is not needed, c lies behind it)
+                    brush_up.append(None)
+                    prev_name = f"up_blocks.{i}.resnets.{j}"
+                    continue
+                at_cache = bool(depth) and u - 1 == first_up
+                if at_cache:                 # c: what this layer is handed
+                    walk["cache"] = prev_name
+                    if shallow:
+                        c0 = cached["cache"]
+                        s = Act(c0.ptr, c0.B, c0.H, c0.W, c0.C)
+                    cache_act = s
                 sk = skips.pop()
                 assert sk.H == s.H and sk.W == s.W, "skip / hidden size mismatch (odd latent size?)"
-                r2 = pop(add_up)
                 if freeu and i < 2:         # (resolution_idx 0 takes (b1, s1), 1 takes (b2, s2); later up blocks are untouched)
-                    s, sk = pb.freeu(s, sk, freeu + 8 * i, self.groups)
+                    # (c must survive the launch: the shallow evaluations behind this one read it again)
+                    s, sk = pb.freeu(s, sk, freeu + 8 * i, self.groups, h_out=pb.new_act(s.B, s.H, s.W, s.C) if at_cache else None)
                 s = self._resnet(pb, f"up_blocks.{i}.resnets.{j}", s, rev[i], temb_all, x2=sk,
                                  res2=0 if has_attn else r2)
                 if has_attn:
                     ap = f"up_blocks.{i}.attentions.{j}"
                     s = self._transformer(pb, ap, s, self.kv[ap], res2=r2)
                 brush_up.append(s)
-            if i != len(boc) - 1:
+                prev_name = f"up_blocks.{i}.resnets.{j}"
+                walk["up"].append(prev_name)
+            if i != len(boc) - 1 and shallow and u - 1 < first_up:      # the upsampler behind a layer that did not run
+                pop(add_up)
+                brush_up.append(None)
+                prev_name = f"up_blocks.{i}.upsamplers.0"
+            elif i != len(boc) - 1:
+                walk["up"].append(f"up_blocks.{i}.upsamplers.0")
+                prev_name = f"up_blocks.{i}.upsamplers.0"
                 pre = f"up_blocks.{i}.upsamplers.0.conv"
                 # the upsampler resizes to the size of the skip tensor the next block pops: 2 h or, behind an odd level of the
                 # down path, 2 h - 1 per axis (`upsample_size`, unet_2d_condition.py:1311-1312; BrushNet_CA.py:874)
@@ -2075,11 +2158,12 @@ class SDNet:
         if self.kind == "brushnet":
             outs = zero_convs(brush_down + [brush_mid] + brush_up)
             nd = len(brush_down)
-            return {"down": outs[:nd], "mid": outs[nd], "up": outs[nd + 1:]}
+            pb.plan.walk = walk
+            return dict({"down": outs[:nd], "mid": outs[nd], "up": outs[nd + 1:]}, **({"cache": cache_act} if depth else {}))
 
         # 6. out: conv_norm_out + SiLU + conv_out -- one launch when the GroupNorm statistics arrive from the producer's
         # epilogue (the normalised 64x64x320 activation is then never written), else norm launch(es) + conv
-        eps = pb.alloc(B * self.out_channels * H * W * 4)
+        eps = cached["eps"] if shallow else pb.alloc(B * self.out_channels * H * W * 4)
         acc = 0
         if self.fuse_conv_out and lib.pp_gn_conv3x3_smallcout_supported(boc[0], self.out_channels, self.groups):
             acc = pb._subscribe_gn_stats(s, None, self.groups)
@@ -2092,4 +2176,5 @@ class SDNet:
             pb.plan.add("conv_out", lib.pp_conv3x3_smallcout, h.ptr, B, H, W, boc[0], P["conv_out.weight"],
                         P["conv_out.bias"], self.out_channels, eps, pb.dt)
         pb.plan.count("conv_out", 2.0 * B * H * W * self.out_channels * 9 * boc[0])
-        return {"eps": eps}
+        pb.plan.walk = walk
+        return dict({"eps": eps}, **({"cache": cache_act} if depth else {}))

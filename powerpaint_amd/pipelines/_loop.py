@@ -73,6 +73,8 @@ class DenoiseLoop:
         self.lib = L.lib()
         self.program: Optional[Plan] = None
         self.graph = None
+        self.program_shallow: Optional[Plan] = None     # DeepCache: the step over the networks' shallow plans, and its graph
+        self.graph_shallow = None
         self._key = None
         self._graph_scale = None      # side-branch conditioning scale baked into the captured graph (by-value kernel arg)
         self.keep_closed_nets = bool(keep_closed_nets)
@@ -118,6 +120,9 @@ class DenoiseLoop:
         if pag:
             PAGM.check_supported(tome=getattr(self.unet.net, "tome", None) is not None and self.unet.net.tome.ratio > 0,
                                  guess_mode=bool(guess_mode))
+            if getattr(self.unet.net, "deepcache", None) is not None:
+                raise L.PPError("DeepCache together with perturbed-attention guidance (PAG, pag_scale > 0) is not implemented: "
+                                "DeepCacheSDHelper.disable() first, or pag_scale = 0")
         if self.latents is None or tuple(self.latents.shape) != tuple(latents_shape):
             self.latents = torch.zeros(latents_shape, dtype=torch.float32, device=self.unet.device)
         lat = self.latents
@@ -149,6 +154,11 @@ class DenoiseLoop:
         rt, side_rt, side_rts = self._prepare_runtimes(
             latents_shape, Be, Bs, do_cfg, half, guess_mode, nets, side, prompt_embeds, prompt_embeds_side, static_inputs,
             side_static_inputs, controlnet_cond, side_scale, timestep_cond, added_cond_kwargs, ip_adapter_masks, pag=pag)
+        # DeepCache: every network of the loop is patched (each runtime then holds a shallow plan next to the full one) or none
+        deep = [getattr(r, "shallow_plan", None) is not None for r in side_rts + [rt]]
+        if any(deep) and not all(deep):
+            raise L.PPError("DeepCache is enabled on some networks of this pipeline and not on others: enable it on the pipeline "
+                            "(DeepCacheSDHelper(pipe)), so that every network is full or shallow together")
         if self.foreign:
             ts, step, src, mp = self._foreign_state(latents_shape, do_cfg, guidance_scale)
         else:
@@ -186,8 +196,14 @@ class DenoiseLoop:
         heads, skips = self._head_launches(side_rts, rt, ts, step, src, Be, Bs, do_cfg or pag, in_div)
         tail = self._tail_launches(rt, lat, mp, step, do_cfg, guidance_scale)
         self.rt, self.side_rt, self.side_rts = rt, side_rt, side_rts
-        self.graph = None
+        self.graph = self.graph_shallow = None
+        self.program_shallow = None
         self._assemble(multi, heads, skips, tail)
+        if all(deep):
+            # one more program: the shallow plans between the same kind of head launches and the SAME tail -- the step counter,
+            # the scheduler tables and the PAG / phi cells are read and moved by both programs alike
+            heads, skips = self._head_launches(side_rts, rt, ts, step, src, Be, Bs, do_cfg or pag, in_div, shallow=True)
+            self._assemble(multi, heads, skips, tail, shallow=True)
         self._keep = (ts, step, mp, lat)
         return self
 
@@ -324,26 +340,30 @@ class DenoiseLoop:
         self._do_cfg, self._g = bool(do_cfg), float(guidance_scale)
         return self._f_ts, self._f_step, self._f_x, None
 
-    def _head_launches(self, side_rts, rt, ts, step, src, Be, Bs, do_cfg, in_div):
+    def _head_launches(self, side_rts, rt, ts, step, src, Be, Bs, do_cfg, in_div, shallow: bool = False):
         """-> (heads, skips), per runtime: the launches at the head of the step; the plan indices they replace.
-        in_div: the table a sigma-space scheduler scales the networks' input by, else None."""
+        in_div: the table a sigma-space scheduler scales the networks' input by, else None.
+        shallow: for the runtimes' shallow plans (DeepCache); the time-embedding tables are the full plans' (same rows)."""
         lib, sch = self.lib, self.scheduler
         B, Cl, h, w = src.shape
         hw = h * w
         mod = B if do_cfg else 0
-        self._temb = {}
+        if not shallow:
+            self._temb = {}
         heads, skips = {}, {}
         for r in side_rts + [rt]:
             prog = Plan()
             heads[id(r)] = prog.calls
             skips[id(r)] = set()
-            info = self._temb_split(r, ts) if _temb_table_enabled() else None
+            plan = r.shallow_plan if shallow else r.step_plan
+            info = self._temb_split(r, ts, plan) if _temb_table_enabled() else None
             x = r.lay["x_in"]
             nb_r = Be if r is rt else Bs                    # (guess mode: the side network takes `latents` as is)
-            calls = r.step_plan.calls
+            calls = plan.calls
             zero = calls[0] if (calls and calls[0][2] == "zero_u64") else None
             if info is not None:
-                self._temb[id(r)] = info
+                if not shallow:
+                    self._temb[id(r)] = info
                 skips[id(r)] |= set(info["idx"])
             if info is not None and zero is not None:
                 # time-embedding row + network input + accumulator zeroing: ONE launch at the head of the step (pp_step_head)
@@ -439,31 +459,44 @@ class DenoiseLoop:
             self._phi_cell.copy_(torch.tensor([self._rescale], dtype=torch.float32))
             self._phi_filled = self._rescale
 
-    def _assemble(self, multi, heads, skips, tail):
+    def _assemble(self, multi, heads, skips, tail, shallow: bool = False):
         """`self.program`: every head, every network's plan without the launches its head replaces, the tail.  Several
-        ControlNets: the parts are kept, and one program per set of active nets is assembled on demand (`_set_entry`)."""
+        ControlNets: the parts are kept, and one program per set of active nets is assembled on demand (`_set_entry`).
+        shallow (DeepCache): the same assembly over the runtimes' shallow plans -> `self.program_shallow`."""
         rts = self.side_rts + [self.rt]
-        self._multi, self._sets = multi, {}
+        if multi and shallow:
+            self._parts_shallow = dict(heads=heads, skips=skips, tail=tail.calls)
+            self.program_shallow = self._set_shallow(self._set_entry(tuple(range(len(self.side_rts)))))
+            return
         if multi:
-            self._parts = dict(heads=heads, skips=skips, tail=tail.calls)
+            self._multi, self._sets = multi, {}
+            self._parts, self._parts_shallow = dict(heads=heads, skips=skips, tail=tail.calls), None
             self._guess_ramps = [self._guess_ramp] * len(self.side_rts)      # (same zero convs in every net: one ramp, per net)
             self.program = self._set_entry(tuple(range(len(self.side_rts))))["program"]    # (every net active: flops, tools)
             return
+        if not shallow:
+            self._multi, self._sets = multi, {}
         full = Plan()
         for r in rts:
             full.calls += heads[id(r)]
         for r in rts:
-            full.calls += [c for i, c in enumerate(r.step_plan.calls) if i not in skips[id(r)]]
-            full.flops += r.step_plan.flops_executed      # (a program's `flops`: what its launches execute)
+            plan = r.shallow_plan if shallow else r.step_plan
+            full.calls += [c for i, c in enumerate(plan.calls) if i not in skips[id(r)]]
+            full.flops += plan.flops_executed             # (a program's `flops`: what its launches execute)
         full.calls += tail.calls
-        self.program = full
+        if shallow:
+            self.program_shallow = full
+        else:
+            self.program = full
 
     # ---- time-embedding table
-    def _temb_split(self, r, ts):
-        """The four leading time-embedding launches of a network's step plan (`timestep_embedding` + three
+    def _temb_split(self, r, ts, plan=None):
+        """(plan: the runtime's step plan, or its shallow plan -- whose own four launches and result address are returned, with
+        the step plan's table.)  The four leading time-embedding launches of a network's step plan (`timestep_embedding` + three
         `linear_skinny`: sinusoid, time_embedding.linear_1/2, all time_emb_proj rows at once) and where their result
         lands; plus a [rows of the schedule][temb_total] fp32 table at a stable address.  None = unexpected layout."""
-        calls = r.step_plan.calls
+        plan = plan if plan is not None else r.step_plan
+        calls = plan.calls
         idx = [i for i, c in enumerate(calls) if c[2] in ("timestep_embedding", "linear_skinny")]
         if len(idx) != 4 or idx != list(range(idx[0], idx[0] + 4)) or calls[idx[0]][2] != "timestep_embedding":
             return None
@@ -476,7 +509,7 @@ class DenoiseLoop:
                            plan=None)
         ent = tabs[k]
         pver = getattr(r.net.params, "version", 0)
-        if ent["plan"] is not r.step_plan or ent.get("pver") != pver:     # new plan / weights rewritten in place: stale rows
+        if plan is r.step_plan and (ent["plan"] is not r.step_plan or ent.get("pver") != pver):     # new plan / weights rewritten in place: stale rows
             ent["plan"], ent["ts"], ent["pver"], ent["hkey"] = r.step_plan, None, pver, None
         return dict(idx=idx, out=out, total=total, table=ent["table"], ent=ent, rt=r)
 
@@ -546,8 +579,30 @@ class DenoiseLoop:
         prog.flops += self.rt.step_plan.flops_executed
         prog.calls += P["tail"]
         ent = self._sets[active] = dict(active=active, included=included, program=prog, records=records, graph=None,
-                                        scales=None)
+                                        scales=None, program_shallow=None, records_shallow={}, graph_shallow=None)
         return ent
+
+    def _set_shallow(self, ent):
+        """DeepCache: the set's program over the shallow plans (the same assembly; the zero convs of the live positions)."""
+        if ent["program_shallow"] is not None:
+            return ent["program_shallow"]
+        P, rts = self._parts_shallow, self.side_rts
+        prog = Plan()
+        for k in ent["included"]:
+            prog.calls += P["heads"][id(rts[k])]
+        prog.calls += P["heads"][id(self.rt)]
+        for n, k in enumerate(ent["included"]):
+            calls, ent["records_shallow"][k] = rts[k].chained_step_calls(rts[0], accumulate=n > 0, scale=0.0,
+                                                                         skip=P["skips"][id(rts[k])], shallow=True)
+            prog.calls += calls
+            prog.flops += rts[k].shallow_plan.flops_executed
+        if not ent["included"]:
+            prog.add("zero_u64", self.lib.pp_zero_u64, *rts[0].residual_block())
+        prog.calls += [c for i, c in enumerate(self.rt.shallow_plan.calls) if i not in P["skips"][id(self.rt)]]
+        prog.flops += self.rt.shallow_plan.flops_executed
+        prog.calls += P["tail"]
+        ent["program_shallow"], ent["scales"] = prog, None      # (the scales are written again, into both programs' records)
+        return prog
 
     def _set_scales(self, ent, scales):
         """Write this call's per-net scales into the set's zero-conv launch records (by-value kernel arguments: a graph
@@ -560,7 +615,11 @@ class DenoiseLoop:
             vals = [r * v for r in ramp] if ramp is not None else [v] * len(ent["records"][k])
             for rec, x in zip(ent["records"][k], vals):
                 rec.scale = float(x)
-        ent["scales"], ent["graph"] = want, None
+            if k in ent["records_shallow"]:
+                pos = self.side_rts[k].shallow_plan.zero_conv_pos
+                for rec, p_ in zip(ent["records_shallow"][k], pos):
+                    rec.scale = float(vals[p_])
+        ent["scales"], ent["graph"], ent["graph_shallow"] = want, None, None
 
     def _multi_schedule(self, scale_schedule, num_steps):
         """Per step: the set's entry, its scales written and (use_graph) its graph captured -- all before the first step."""
@@ -579,7 +638,26 @@ class DenoiseLoop:
             act = tuple(row[k] for k in ent["active"])
             if seen.setdefault(ent["active"], act) != act:
                 raise L.PPError("the scale of an active ControlNet changed inside one call")
+        if self._deep() and len(seen) > 1:
+            raise L.PPError("DeepCache with several ControlNets whose set of active nets changes during the call (guidance "
+                            "windows) is not implemented: one set per call, or DeepCacheSDHelper.disable()")
+        if self._deep():
+            for ent, _ in ents:
+                self._set_shallow(ent)
         return ents
+
+    # ---- DeepCache: which program an evaluation runs
+    def _deep(self) -> bool:
+        return getattr(self, "rt", None) is not None and getattr(self.rt, "shallow_plan", None) is not None and \
+            getattr(self.rt.net, "deepcache", None) is not None
+
+    def shallow_rows(self, num_steps: int) -> List[bool]:
+        """Per evaluation of a call (one per row of the schedule `run` steps through, counted from 0 at every call): does it
+        run the shallow program?  Evaluation e is full iff e % cache_interval == 0; without DeepCache every one is."""
+        if not self._deep():
+            return [False] * num_steps
+        iv = int(self.rt.net.deepcache.interval)
+        return [e % iv != 0 for e in range(num_steps)]
 
     def capture(self):
         """Capture one step into a hipGraph (torch.cuda.CUDAGraph).  The captured launches read the step counter from
@@ -587,6 +665,7 @@ class DenoiseLoop:
         self._graph_scale = self._scale_now()
         self._graph_ip = self.rt.ip_scales()          # (IP-Adapter scales: by-value arguments of the UNet's launches as well)
         self.graph = self._capture_program(self.program)
+        self.graph_shallow = None             # (captured with the same by-value arguments, so it goes with the full one)
 
     def _capture_program(self, program):
         torch.cuda.synchronize()
@@ -642,16 +721,21 @@ class DenoiseLoop:
             self._fill_phi_cell()
         self.latents.copy_(latents.to(self.latents.device, torch.float32))
         ents, scale_schedule, varying = self._schedule(scale_schedule, num_steps)
+        shallow = self.shallow_rows(num_steps)
         if ents is not None and use_graph:        # (every set's graph before the first step)
-            for ent, _ in ents:
-                if ent["graph"] is None:
+            for (ent, _), sh in zip(ents, shallow):
+                if ent["graph"] is None:          # (the full program first: its warm-up leaves a c the shallow one's can read)
                     ent["graph"] = self._capture_program(ent["program"])
+                if sh and ent["graph_shallow"] is None:
+                    ent["graph_shallow"] = self._capture_program(ent["program_shallow"])
         if not varying and scale_schedule and self.side_rt is not None and \
                 self._scale_now() != self._side_scale(scale_schedule[0]):
             self.side_rt._patch_scale(self._side_scale(scale_schedule[0]))   # (a previous call may have left a windowed value)
         if use_graph and not varying and (self.graph is None or self._graph_scale != self._scale_now() or
                                           getattr(self, "_graph_ip", ()) != self.rt.ip_scales()):
             self.capture()
+        if use_graph and not varying and ents is None and any(shallow) and self.graph_shallow is None:
+            self.graph_shallow = self._capture_program(self.program_shallow)
         stream = torch.cuda.current_stream().cuda_stream
         for i in range(num_steps):
             if varying and self.side_rt is not None:
@@ -661,15 +745,16 @@ class DenoiseLoop:
                                          self._noise_dtype)
             if z is not None:
                 self._var_noise.copy_(z)
+            sfx = "_shallow" if shallow[i] else ""
             if ents is not None:
                 if use_graph:
-                    ents[i][0]["graph"].replay()
+                    ents[i][0]["graph" + sfx].replay()
                 else:
-                    ents[i][0]["program"].run(stream)
+                    ents[i][0]["program" + sfx].run(stream)
             elif use_graph and not varying:
-                self.graph.replay()
+                (self.graph_shallow if shallow[i] else self.graph).replay()
             else:
-                self.program.run(stream)
+                (self.program_shallow if shallow[i] else self.program).run(stream)
             if callback is not None:
                 callback(i, timesteps[i] if timesteps is not None else None, self.latents)
         self._check_faults()
@@ -707,9 +792,11 @@ class DenoiseLoop:
         self._f_step.zero_()
         lat = latents.to(self.latents.device, torch.float32).clone()
         ents, scale_schedule, varying = self._schedule(scale_schedule, num_steps)
+        shallow = self.shallow_rows(num_steps)
         stream = torch.cuda.current_stream().cuda_stream
         for i in range(num_steps):
             t = tl[i]
+            sfx = "_shallow" if shallow[i] else ""
             x = sch.scale_model_input(lat, t) if hasattr(sch, "scale_model_input") else lat
             self._f_x.copy_(x)
             if varying and self.side_rt is not None:
@@ -717,20 +804,23 @@ class DenoiseLoop:
             if ents is not None:
                 ent = ents[i][0]
                 if use_graph:
-                    if ent["graph"] is None:
-                        ent["graph"] = self._capture_program(ent["program"])
+                    if ent["graph" + sfx] is None:
+                        ent["graph" + sfx] = self._capture_program(ent["program" + sfx])
                         self._f_step.fill_(i)
-                    ent["graph"].replay()
+                    ent["graph" + sfx].replay()
                 else:
-                    ent["program"].run(stream)
+                    ent["program" + sfx].run(stream)
             elif use_graph and not varying:
                 if self.graph is None or self._graph_scale != self._scale_now() or \
                         getattr(self, "_graph_ip", ()) != self.rt.ip_scales():
                     self.capture()
                     self._f_step.fill_(i)
-                self.graph.replay()
+                if shallow[i] and self.graph_shallow is None:
+                    self.graph_shallow = self._capture_program(self.program_shallow)
+                    self._f_step.fill_(i)
+                (self.graph_shallow if shallow[i] else self.graph).replay()
             else:
-                self.program.run(stream)
+                (self.program_shallow if shallow[i] else self.program).run(stream)
             eps = self.rt.eps_tensor()
             # (guidance_rescale is only ever on with CFG: the conditional prediction is the second segment of two or three)
             text = eps.chunk(3 if self._pag is not None else 2)[1] if self._rescale is not None else None

@@ -24,6 +24,8 @@ class NetRuntime:
         self.key = None
         self.arena: Optional[Arena] = None
         self.step_plan: Optional[Plan] = None
+        self.shallow_plan: Optional[Plan] = None       # DeepCache: the shallow form of the step (None without it)
+        self.dc_eval = 0
         self.setup_plan: Optional[Plan] = None
         self.outputs: Dict[str, object] = {}
         self._ctx_id = None
@@ -200,9 +202,25 @@ class NetRuntime:
             if net.kind == "unet":
                 raise L.PPError("pad_uncond is an output layout of the side networks (BrushNet / ControlNet)")
             kw["pad_uncond"] = True
+        dc = getattr(net, "deepcache", None)
+        if dc is not None:
+            kw["depth"] = int(dc.branch) + 1
         outs = net.build_step(pb, lay["x_in"], lay["t_dev"], scale=1.0, twin=twin, **kw)
         if pb.gn_acc_used:
             pb.plan.calls.insert(0, (L.lib().pp_zero_u64, (lay["gn_acc"], pb.gn_acc_used // 8), "zero_u64"))
+        if dc is not None:
+            # DeepCache: the shallow form of the same walk, a plan of its own on the same arena.  Its tensors lie ABOVE everything
+            # the full plan allocated: nothing it writes can touch c (which lives among the full plan's tensors), the setup
+            # plan's outputs or the input / residual slots.  The accumulator pool is shared -- every plan zeroes what it uses
+            # with its first launch, and nothing cached lives there.
+            ps = Builder(arena, dtype=net.dtype)
+            ps.gemm_tile, ps.gemm_splitk = self.gemm_tile, self.gemm_splitk
+            ps.gn_acc_base, ps.gn_acc_cap = lay["gn_acc"], gn_cap
+            ps.fault_ptr = lay["fault"]
+            net.build_step(ps, lay["x_in"], lay["t_dev"], scale=1.0, twin=twin, cached=outs, **kw)
+            if ps.gn_acc_used:
+                ps.plan.calls.insert(0, (L.lib().pp_zero_u64, (lay["gn_acc"], ps.gn_acc_used // 8), "zero_u64"))
+            lay["shallow_plan"] = ps.plan
         return lay, pb_setup.plan, pb.plan, outs
 
     def _residual_shapes(self, B, H, W, with_up: bool):
@@ -271,6 +289,13 @@ class NetRuntime:
                 from .pag import check_supported
                 check_supported(tome=True)
             key += (("pag", tuple(pag.layers), int(pag.n)),)
+        dc = getattr(getattr(self, "net", None), "deepcache", None)
+        if dc is not None:                                       # (without DeepCache: the key of a plan that never had it)
+            if tm is not None:
+                raise L.PPError("DeepCache together with token merging (ToMe) on the same network is not implemented")
+            if pag is not None:
+                raise L.PPError("DeepCache together with perturbed-attention guidance (PAG, pag_scale > 0) is not implemented")
+            key += (("deepcache", int(dc.branch)),)               # (cache_interval is host schedule: no part of the key)
         if isinstance(scale, (list, tuple)):
             scale = tuple(float(v) for v in scale)       # (one representation: a list never equals the stored tuple)
         if key == self.key:
@@ -289,6 +314,8 @@ class NetRuntime:
         self.lay, self.setup_plan, self.step_plan, self.outputs = self._build(
             self.arena, B, H, W, nctx, cin_total, wiring, cond_hw, scale, pad_uncond, twin, freeu is not None, ip_n,
             bool(ip_masked), pag)
+        self.shallow_plan = self.lay.pop("shallow_plan", None)
+        self.dc_eval = 0                                # evaluations since the plans were built / the helper was enabled
         self.twin = bool(twin)
         self.pad_uncond = bool(pad_uncond)
         self.key = key
@@ -421,13 +448,18 @@ class NetRuntime:
         vals = list(scale) if isinstance(scale, (list, tuple)) else [scale] * len(zc)
         for a, v in zip(zc, vals):
             a.scale = float(v)
+        if self.shallow_plan is not None:                  # (the shallow plan's zero convs: the live positions, the same values)
+            for a, p in zip(self.zero_conv_records(self.shallow_plan), self.shallow_plan.zero_conv_pos):
+                a.scale = float(vals[p])
+            self.graph_shallow = None
         self._scale = tuple(float(v) for v in scale) if isinstance(scale, (list, tuple)) else scale
         self.graph = None
 
     # ------------------------------------------------------------------ several side networks, one sum
-    def zero_conv_records(self):
-        """The PPGemmArgs of the step plan's zero-conv launches, in output order (down..., mid[, up...])."""
-        return [args[0]._obj for fn, args, name in self.step_plan.calls if name == "zero_conv"]
+    def zero_conv_records(self, plan: Optional[Plan] = None):
+        """The PPGemmArgs of the step plan's zero-conv launches, in output order (down..., mid[, up...]); of the shallow plan:
+        the live positions only (`plan.zero_conv_pos` names them)."""
+        return [args[0]._obj for fn, args, name in (plan or self.step_plan).calls if name == "zero_conv"]
 
     def residual_block(self) -> Tuple[int, int]:
         """(pointer, 64-bit words) of the contiguous arena block that holds every residual output of a side network
@@ -437,7 +469,7 @@ class NetRuntime:
         end = acts[-1].ptr + acts[-1].rows * acts[-1].C * 2
         return acts[0].ptr, (end - acts[0].ptr + 7) // 8
 
-    def chained_step_calls(self, target: "NetRuntime", accumulate: bool, scale, skip=()):
+    def chained_step_calls(self, target: "NetRuntime", accumulate: bool, scale, skip=(), shallow: bool = False):
         """This side network's step launches (indices in `skip` left out) with the zero convs writing into `target`'s
         residual buffers instead of its own: `accumulate=False` overwrites them (the first network of a sum),
         `accumulate=True` adds to what they hold IN PLACE, `out = res1 = target buffer` -- the sum of several ControlNets
@@ -446,16 +478,22 @@ class NetRuntime:
         The launch records are COPIES (the network's own plan, its scale and its outputs stay as they are); the caller keeps
         the returned records alive as long as the calls.  With pad_uncond the network's launch that zeroes the unconditional
         halves is pointed at the target's block when it overwrites and dropped when it accumulates.
+        shallow (DeepCache): the shallow plans of both, whose zero convs are the live positions (`scale` stays one value per
+        zero conv of the FULL plan).
         Returns (calls, records)."""
-        mine, theirs = self.zero_conv_records(), target.zero_conv_records()
+        plan = self.shallow_plan if shallow else self.step_plan
+        mine, theirs = self.zero_conv_records(plan), target.zero_conv_records(target.shallow_plan if shallow else None)
         if len(mine) != len(theirs) or any((a.M, a.N, a.ldo) != (b.M, b.N, b.ldo) for a, b in zip(mine, theirs)):
             raise L.PPError("side networks whose residuals are summed must produce residuals of the same shapes")
-        vals = [float(v) for v in scale] if isinstance(scale, (list, tuple)) else [float(scale)] * len(mine)
-        if len(vals) != len(mine):
-            raise L.PPError(f"{len(vals)} residual scales for {len(mine)} zero convs")
+        nfull = len(self.zero_conv_records())
+        vals = [float(v) for v in scale] if isinstance(scale, (list, tuple)) else [float(scale)] * nfull
+        if len(vals) != nfull:
+            raise L.PPError(f"{len(vals)} residual scales for {nfull} zero convs")
+        if shallow:
+            vals = [vals[p] for p in plan.zero_conv_pos]
         pad_ptr = self.residual_block()[0] if self.pad_uncond else 0
         calls, records, k = [], [], 0
-        for i, (fn, args, name) in enumerate(self.step_plan.calls):
+        for i, (fn, args, name) in enumerate(plan.calls):
             if i in skip:
                 continue
             if name == "zero_conv":
@@ -544,29 +582,47 @@ class NetRuntime:
         if "tome" in self.lay:
             self.tome_bind(None)
             self.tome_fill(1, self.net.tome_state)
+        shallow = self.next_is_shallow()
         if use_graph:
             if self.graph is None:
-                self.capture()
-            self.graph.replay()
+                self.capture()                     # (the full plan first: its warm-up leaves a valid c for the shallow plan's)
+            if shallow and self.__dict__.get("graph_shallow") is None:
+                self.graph_shallow = self._capture(self.shallow_plan)
+            (self.graph_shallow if shallow else self.graph).replay()
         else:
-            self.step_plan.run(_stream())
+            (self.shallow_plan if shallow else self.step_plan).run(_stream())
+
+    def next_is_shallow(self) -> bool:
+        """DeepCache, a module called directly: count this evaluation; it is full iff its number is a multiple of
+        cache_interval (the counter starts at 0 with every new plan and with DeepCacheSDHelper.enable())."""
+        dc = getattr(self.net, "deepcache", None)
+        if dc is None or self.shallow_plan is None:
+            return False
+        e, self.dc_eval = self.dc_eval, self.dc_eval + 1
+        return e % int(dc.interval) != 0
 
     def capture(self):
+        self.graph = self._capture(self.step_plan)
+        self.graph_shallow = None
+
+    def _capture(self, plan: Plan):
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self.step_plan.run(s.cuda_stream)      # warm-up (sets func attributes outside capture)
+            plan.run(s.cuda_stream)                # warm-up (sets func attributes outside capture)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self.step_plan.run(_stream())
-        self.graph = g
+            plan.run(_stream())
+        return g
 
     def combines_in_kernel(self) -> bool:
-        """Does the step plan hand tile counters to any split-K launch (PPGemmArgs.tile_ctr)?"""
-        return any(getattr(a, "tile_ctr", None) for a in getattr(self.step_plan, "keep", []))
+        """Does the step plan (or DeepCache's shallow plan: one fault word serves both) hand tile counters to any split-K
+        launch (PPGemmArgs.tile_ctr)?"""
+        return any(getattr(a, "tile_ctr", None) for p in (self.step_plan, self.shallow_plan)
+                   for a in getattr(p, "keep", []))
 
     def check_faults(self, blocking: bool = True):
         """The in-kernel split-K combine (csrc/gemm_combine.h) sums a tile's slabs through ONE XCD's L2.  Splits of a tile on
