@@ -38,12 +38,19 @@ is closed at a step (scale 0) is LEFT OUT of that step: one program and one capt
 nets (at most 2 N + 1 over a schedule), cached on the loop and picked per step on the host; with no net active the
 set's program zeroes the shared buffers itself.
 
+Which program a step runs: `_sets` maps a set of active side nets to a `_StepSet` -- its program, captured graph and
+zero-conv launch records, each as a pair [full, DeepCache-shallow].  Several ControlNets: one entry per tuple of active nets;
+every other loop: the one entry under `_all`.  `_build` assembles every program from `_parts[shallow]`, `_resolve` picks (and
+captures) what every step of a call replays before the first step, `_stale` is the one rule for a graph captured with other
+by-value arguments.
+
 A scheduler that is not one of powerpaint_amd.schedulers (any object with the diffusers protocol the reference
 duck-types: `.timesteps`, `.scale_model_input`, `.step(...)`, e.g. the UniPC scheduler app.py:197 installs) is driven
 the way the reference drives it: the network part of the step is the same captured launch program, the guidance
 combine and the scheduler's own `.step` run as that object's tensor code on the device, once per step.
 """
 import os
+from collections import namedtuple
 from typing import Callable, List, Optional
 
 import torch
@@ -60,6 +67,21 @@ def _temb_table_enabled() -> bool:
     return not (os.environ.get("PP_LAB") == "1" and os.environ.get("PP_TEMB_TABLE", "1") == "0")
 
 
+_Keep = namedtuple("_Keep", "ts step m_prev latents")      # what `bind` leaves for `run`: the device tensors one step reads and moves
+
+
+class _StepSet:
+    """The step programs of one set of active side networks.  `program`, `graph` and `records` are pairs indexed by `shallow`
+    (False: the full plans, True: DeepCache's shallow ones); `records`: per included net the launch records its scale is
+    written into (several ControlNets only); `scales`: the scales last written; `baked`: `_baked()` at the graphs' capture."""
+    __slots__ = ("active", "included", "program", "graph", "records", "scales", "baked")
+
+    def __init__(self, active, included):
+        self.active, self.included = active, included
+        self.program, self.graph, self.records = [None, None], [None, None], [{}, {}]
+        self.scales = self.baked = None
+
+
 class DenoiseLoop:
     def __init__(self, unet, scheduler, side=None, side_kind: Optional[str] = None, keep_closed_nets: bool = False):
         """keep_closed_nets (several ControlNets only): a net whose guidance window is closed at a step still runs, with
@@ -71,17 +93,45 @@ class DenoiseLoop:
             raise TypeError(f"{type(scheduler).__name__} does not follow the scheduler protocol (.timesteps, .step)")
         self.unet, self.scheduler, self.side, self.side_kind = unet, scheduler, side, side_kind
         self.lib = L.lib()
-        self.program: Optional[Plan] = None
-        self.graph = None
-        self.program_shallow: Optional[Plan] = None     # DeepCache: the step over the networks' shallow plans, and its graph
-        self.graph_shallow = None
         self._key = None
-        self._graph_scale = None      # side-branch conditioning scale baked into the captured graph (by-value kernel arg)
         self.keep_closed_nets = bool(keep_closed_nets)
-        self._multi = False           # several ControlNets bound: per-active-set programs (self._sets) instead of ONE program
-        self._sets = {}
+        self._multi = False           # several ControlNets bound: one entry of self._sets per set of active nets, else ONE entry
+        self._sets, self._all = {}, ()             # active nets -> _StepSet; the default entry's key: every side net active
+        self._parts = {}                           # shallow -> dict(heads, skips, tail): what `_build` assembles programs from
+        self.rt = self.side_rt = None
         self.side_rts = []
         self.latents: Optional[torch.Tensor] = None
+        self._keep: Optional[_Keep] = None
+        # what `bind` takes from its call: guidance (PAG pair, rescale phi, a foreign scheduler's CFG), blend buffers, noise
+        self._pag = self._rescale = self._blend = self._guess_ramp = self._gen = None
+        self._do_cfg, self._g, self._eta, self._noisy, self._noise_dtype = False, 0.0, 0.0, False, torch.float32
+        self._extra_step_kwargs = {}
+        self._temb, self._temb_tables = {}, {}     # per runtime: the time-embedding launches its head replaces; their tables
+        # device tensors at stable addresses (`_stable`): what each was made as; what the PAG table / phi cell were last filled with
+        self._made, self._filled = {}, {}
+        self._ticket = self._var_noise = self._pag_table = self._phi_cell = None
+        self._blend_x0 = self._blend_mask = self._blend_noise = self._f_ts = self._f_step = self._f_x = None
+
+    def _default(self, what: str, shallow: bool):
+        ent = self._sets.get(self._all)
+        return getattr(ent, what)[shallow] if ent is not None else None
+
+    # the default entry's: the step program (several ControlNets: every net active -- flops, tools) and its captured graph;
+    # DeepCache: the step over the networks' shallow plans, and its graph
+    program = property(lambda self: self._default("program", False))
+    program_shallow = property(lambda self: self._default("program", True))
+    graph = property(lambda self: self._default("graph", False))
+    graph_shallow = property(lambda self: self._default("graph", True))
+
+    def _stable(self, name: str, shape, dtype=torch.float32, device=None) -> torch.Tensor:
+        """The loop's device tensor `name` at a stable address (a captured graph reads it): allocated, as zeros, only when the
+        shape, dtype or device asked for changed -- and what it was last filled with is forgotten with it."""
+        made = (tuple(shape), dtype, str(device))
+        if self._made.get(name) != made:
+            setattr(self, name, torch.zeros(made[0], dtype=dtype, device=device))
+            self._made[name] = made
+            self._filled.pop(name, None)
+        return getattr(self, name)
 
     # ------------------------------------------------------------------
     def bind(self, latents_shape, do_cfg: bool, guidance_scale: float, prompt_embeds, prompt_embeds_side=None,
@@ -180,31 +230,30 @@ class DenoiseLoop:
                in_div.data_ptr() if in_div is not None else 0)
         self._pag = (float(pag_scale), float(pag_adaptive_scale)) if pag else None
         if pag:                                  # (the table's address is part of the key, the scales in it are not: `run` fills it)
-            key += (("pag", 0 if self.foreign else self._pag_table_for(int(ts.numel()), ts.device).data_ptr()),)
+            key += (("pag", 0 if self.foreign else self._stable("_pag_table", (int(ts.numel()),), device=ts.device).data_ptr()),)
         self._rescale = GDM.check_guidance_rescale(guidance_rescale) if do_cfg else 0.0
         self._rescale = self._rescale if self._rescale > 0.0 else None
         if self._rescale is not None:            # (the cell's address is part of the key, phi in it is not: `run` fills it)
-            key += (("rescale", 0 if self.foreign else self._phi_cell_for(ts.device).data_ptr()),)
+            key += (("rescale", 0 if self.foreign else self._stable("_phi_cell", (1,), device=ts.device).data_ptr()),)
         if key == self._key and self.program is not None:
             # The conditioning scale is a by-value argument of the zero-conv launches: `prepare` has patched the launch
             # records (eager runs see it), but a graph captured with another value still carries the old one.
-            if self.graph is not None and (self._scale_now() != self._graph_scale or
-                                           rt.ip_scales() != getattr(self, "_graph_ip", ())):
-                self.graph = None
+            if self._stale(self._sets[self._all]):
+                self._sets[self._all].graph = [None, None]
             return self
         self._key = key
-        heads, skips = self._head_launches(side_rts, rt, ts, step, src, Be, Bs, do_cfg or pag, in_div)
-        tail = self._tail_launches(rt, lat, mp, step, do_cfg, guidance_scale)
+        tail = self._tail_launches(rt, lat, mp, step, do_cfg, guidance_scale).calls
         self.rt, self.side_rt, self.side_rts = rt, side_rt, side_rts
-        self.graph = self.graph_shallow = None
-        self.program_shallow = None
-        self._assemble(multi, heads, skips, tail)
+        self._multi, self._sets, self._parts, self._all = multi, {}, {}, tuple(range(len(side_rts)))
+        # DeepCache: one more program, the shallow plans between the same kind of head launches and the SAME tail -- the step
+        # counter, the scheduler tables and the PAG / phi cells are read and moved by both programs alike
+        for shallow in (False, True) if all(deep) else (False,):
+            heads, skips = self._head_launches(side_rts, rt, ts, step, src, Be, Bs, do_cfg or pag, in_div, shallow=shallow)
+            self._parts[shallow] = dict(heads=heads, skips=skips, tail=tail)
+        ent = self._entry(self._all)
         if all(deep):
-            # one more program: the shallow plans between the same kind of head launches and the SAME tail -- the step counter,
-            # the scheduler tables and the PAG / phi cells are read and moved by both programs alike
-            heads, skips = self._head_launches(side_rts, rt, ts, step, src, Be, Bs, do_cfg or pag, in_div, shallow=True)
-            self._assemble(multi, heads, skips, tail, shallow=True)
-        self._keep = (ts, step, mp, lat)
+            self._build(ent, True)
+        self._keep = _Keep(ts, step, mp, lat)
         return self
 
     # ---- the parts of `bind`, in its order
@@ -215,10 +264,8 @@ class DenoiseLoop:
         _, Cl, h, w = latents_shape
         dev = self.unet.device
         x0, mk, nz = blend
-        want = ((1, Cl, h, w), (1, 1, h, w), tuple(latents_shape))
-        bufs = getattr(self, "_blend_bufs", None)
-        if bufs is None or tuple(tuple(b.shape) for b in bufs) != want:
-            bufs = self._blend_bufs = tuple(torch.zeros(sh, dtype=torch.float32, device=dev) for sh in want)
+        want = (("_blend_x0", (1, Cl, h, w)), ("_blend_mask", (1, 1, h, w)), ("_blend_noise", latents_shape))
+        bufs = tuple(self._stable(name, sh, device=dev) for name, sh in want)
         for b_, v in zip(bufs, (x0[:1], mk[:1], nz)):
             b_.copy_(v.to(device=dev, dtype=torch.float32).reshape(b_.shape))
         return bufs
@@ -329,16 +376,9 @@ class DenoiseLoop:
         input (scaled by the scheduler per step), all owned by the loop."""
         dev = self.unet.device
         tsv = torch.as_tensor(self.scheduler.timesteps).detach().to(dev, torch.float32).contiguous()
-        if getattr(self, "_f_ts", None) is None or self._f_ts.shape != tsv.shape:
-            self._f_ts = tsv
-            self._f_step = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._f_x = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
-        else:
-            self._f_ts.copy_(tsv)
-        if tuple(self._f_x.shape) != tuple(latents_shape):
-            self._f_x = torch.zeros(latents_shape, dtype=torch.float32, device=dev)
         self._do_cfg, self._g = bool(do_cfg), float(guidance_scale)
-        return self._f_ts, self._f_step, self._f_x, None
+        return (self._stable("_f_ts", tsv.shape, device=dev).copy_(tsv), self._stable("_f_step", (1,), torch.int32, dev),
+                self._stable("_f_x", latents_shape, device=dev), None)
 
     def _head_launches(self, side_rts, rt, ts, step, src, Be, Bs, do_cfg, in_div, shallow: bool = False):
         """-> (heads, skips), per runtime: the launches at the head of the step; the plan indices they replace.
@@ -394,11 +434,10 @@ class DenoiseLoop:
         fold_advance = (not self.foreign) and not (self._eta > 0) and self._blend is None and \
             not (os.environ.get("PP_LAB") == "1" and os.environ.get("PP_FOLD_ADVANCE", "1") == "0")     # (lab: the two launches)
         if not self.foreign:
-            if fold_advance and (getattr(self, "_ticket", None) is None or self._ticket.device != lat.device):
-                self._ticket = torch.zeros(1, dtype=torch.int32, device=lat.device)
-            if self._noisy and (getattr(self, "_var_noise", None) is None or self._var_noise.shape != lat.shape):
-                self._var_noise = torch.zeros_like(lat)
-            noise = self._var_noise if self._noisy else lat      # (a step that reads no noise: any valid address)
+            if fold_advance:
+                self._stable("_ticket", (1,), torch.int32, lat.device)
+            # (a step that reads no noise: any valid address)
+            noise = self._stable("_var_noise", lat.shape, lat.dtype, lat.device) if self._noisy else lat
             if self._rescale is not None:
                 # guidance_rescale (CFG is on): the combine -- PAG's three-way one with its table when PAG is on, in the place
                 # of pp_pag_combine -- and the per-sample rescale into segment 0; the step launch behind it runs with cfg = 0
@@ -427,67 +466,60 @@ class DenoiseLoop:
             prog.add("step_advance", lib.pp_step_advance, step.data_ptr())
         return prog
 
-    # ---- perturbed-attention guidance: the per-row scale table
-    def _pag_table_for(self, rows: int, device) -> torch.Tensor:
-        """fp32 [rows of the schedule] at a stable address (a captured graph reads it)."""
-        t = getattr(self, "_pag_table", None)
-        if t is None or t.numel() != rows or t.device != device:
-            self._pag_table, self._pag_filled = torch.zeros(rows, dtype=torch.float32, device=device), None
-        return self._pag_table
-
+    # ---- perturbed-attention guidance: the per-row scale table (fp32 [rows of the schedule]); guidance_rescale: the one-float cell
     def _fill_pag_table(self, ts):
         """s_i of every schedule row (pag.scale_rows) -> the device table, when the scale pair or the timesteps changed."""
         host = getattr(self.scheduler, "_ts_host", None) if not self.foreign else None
         tsl = [float(v) for v in (host if host is not None else ts).tolist()]
         want = (self._pag, tuple(tsl))
-        if want != self._pag_filled:
-            self._pag_rows = PAGM.scale_rows(self._pag[0], self._pag[1], tsl)
-            self._pag_table.copy_(torch.tensor(self._pag_rows, dtype=torch.float32))
-            self._pag_filled = want
-
-    # ---- guidance_rescale: the one-float cell
-    def _phi_cell_for(self, device) -> torch.Tensor:
-        """fp32 [1] at a stable address (a captured graph reads it)."""
-        c = getattr(self, "_phi_cell", None)
-        if c is None or c.device != device:
-            self._phi_cell, self._phi_filled = torch.zeros(1, dtype=torch.float32, device=device), None
-        return self._phi_cell
+        if want != self._filled.get("_pag_table"):
+            self._pag_table.copy_(torch.tensor(PAGM.scale_rows(self._pag[0], self._pag[1], tsl), dtype=torch.float32))
+            self._filled["_pag_table"] = want
 
     def _fill_phi_cell(self):
         """This call's guidance_rescale -> the device cell, when it changed."""
-        if self._rescale != self._phi_filled:
+        if self._rescale != self._filled.get("_phi_cell"):
             self._phi_cell.copy_(torch.tensor([self._rescale], dtype=torch.float32))
-            self._phi_filled = self._rescale
+            self._filled["_phi_cell"] = self._rescale
 
-    def _assemble(self, multi, heads, skips, tail, shallow: bool = False):
-        """`self.program`: every head, every network's plan without the launches its head replaces, the tail.  Several
-        ControlNets: the parts are kept, and one program per set of active nets is assembled on demand (`_set_entry`).
-        shallow (DeepCache): the same assembly over the runtimes' shallow plans -> `self.program_shallow`."""
-        rts = self.side_rts + [self.rt]
-        if multi and shallow:
-            self._parts_shallow = dict(heads=heads, skips=skips, tail=tail.calls)
-            self.program_shallow = self._set_shallow(self._set_entry(tuple(range(len(self.side_rts)))))
-            return
-        if multi:
-            self._multi, self._sets = multi, {}
-            self._parts, self._parts_shallow = dict(heads=heads, skips=skips, tail=tail.calls), None
-            self._guess_ramps = [self._guess_ramp] * len(self.side_rts)      # (same zero convs in every net: one ramp, per net)
-            self.program = self._set_entry(tuple(range(len(self.side_rts))))["program"]    # (every net active: flops, tools)
-            return
-        if not shallow:
-            self._multi, self._sets = multi, {}
-        full = Plan()
-        for r in rts:
-            full.calls += heads[id(r)]
-        for r in rts:
-            plan = r.shallow_plan if shallow else r.step_plan
-            full.calls += [c for i, c in enumerate(plan.calls) if i not in skips[id(r)]]
-            full.flops += plan.flops_executed             # (a program's `flops`: what its launches execute)
-        full.calls += tail.calls
-        if shallow:
-            self.program_shallow = full
-        else:
-            self.program = full
+    # ---- the program table: one entry (programs, graphs, launch records) per set of active side nets
+    def _entry(self, active) -> _StepSet:
+        """The entry of the side nets `active` (ascending indices), its full program assembled when it is new.  Several
+        ControlNets: the heads and plans of those nets only; keep_closed_nets: every net is in, the closed ones get scale 0.
+        Every other loop has the one entry `_all`, every side net in it."""
+        active = tuple(active)
+        ent = self._sets.get(active)
+        if ent is None:
+            included = list(active if (self._multi and not self.keep_closed_nets) else self._all)
+            ent = self._sets[active] = _StepSet(active, included)
+            self._build(ent, False)
+        return ent
+
+    def _build(self, ent: _StepSet, shallow: bool) -> Plan:
+        """`ent.program[shallow]` from `_parts[shallow]`: the heads of the included side nets and the UNet's, every network's
+        plan (shallow: its shallow plan) without the launches its head replaces, the tail -- the same call tuples in every
+        program.  Several ControlNets: the side plans as copies whose zero convs write net 0's residual buffers, the first
+        one overwriting them, the others adding in place (NetRuntime.chained_step_calls; the records kept for `_set_scales`);
+        no net included -> one zeroing launch over the buffers (the UNet plan is never rebuilt)."""
+        P, rts = self._parts[shallow], self.side_rts
+        plan_of = (lambda r: r.shallow_plan) if shallow else (lambda r: r.step_plan)
+        own = lambda r: [c for i, c in enumerate(plan_of(r).calls) if i not in P["skips"][id(r)]]      # noqa: E731
+        prog = Plan()
+        for r in [rts[k] for k in ent.included] + [self.rt]:
+            prog.calls += P["heads"][id(r)]
+            prog.flops += plan_of(r).flops_executed       # (a program's `flops`: what its launches execute)
+        for n, k in enumerate(ent.included):
+            if self._multi:
+                calls, ent.records[shallow][k] = rts[k].chained_step_calls(rts[0], accumulate=n > 0, scale=0.0,
+                                                                          skip=P["skips"][id(rts[k])], shallow=shallow)
+            else:
+                calls = own(rts[k])
+            prog.calls += calls
+        if self._multi and not ent.included:
+            prog.add("zero_u64", self.lib.pp_zero_u64, *rts[0].residual_block())
+        prog.calls += own(self.rt) + P["tail"]
+        ent.program[shallow], ent.scales = prog, None      # (the scales are written again, into both programs' records)
+        return prog
 
     # ---- time-embedding table
     def _temb_split(self, r, ts, plan=None):
@@ -502,8 +534,7 @@ class DenoiseLoop:
             return None
         a = calls[idx[-1]][1]
         out, total = int(a[6]), int(a[5])
-        tabs = self.__dict__.setdefault("_temb_tables", {})
-        k = (id(r), int(ts.numel()), total)
+        tabs, k = self._temb_tables, (id(r), int(ts.numel()), total)
         if k not in tabs:
             tabs[k] = dict(table=torch.zeros(int(ts.numel()), total, dtype=torch.float32, device=ts.device), ts=None,
                            plan=None)
@@ -516,8 +547,8 @@ class DenoiseLoop:
     def _fill_temb_tables(self):
         """(Re)compute the table rows when the timestep table changed since they were made: per row the network's own
         four launches, eagerly, with the step counter pointing at that row."""
-        ts, step = self._keep[0], self._keep[1]
-        for info in getattr(self, "_temb", {}).values():
+        ts, step = self._keep.ts, self._keep.step
+        for info in self._temb.values():
             ent, r = info["ent"], info["rt"]
             # (this package's schedulers keep the timesteps on the host: compare there -- a device compare synchronises)
             host = getattr(self.scheduler, "_ts_host", None) if not self.foreign else None
@@ -545,110 +576,66 @@ class DenoiseLoop:
 
     def _side_scale(self, v):
         """One entry of `run`'s scale schedule as the side runtime stores it (guess mode: the per-residual ramp)."""
-        ramp = getattr(self, "_guess_ramp", None)
+        ramp = self._guess_ramp
         return tuple(r * v for r in ramp) if ramp is not None else v
 
     def _scale_now(self):
-        sc = getattr(self.side_rt, "_scale", None) if getattr(self, "side_rt", None) is not None else None
+        sc = getattr(self.side_rt, "_scale", None)
         return tuple(sc) if isinstance(sc, (list, tuple)) else sc
 
-    # ---- several ControlNets: one program (and graph) per set of active nets
-    def _set_entry(self, active):
-        """The step program for the nets `active` (ascending indices): heads and plans of those nets only, the first one
-        overwriting net 0's residual buffers, the others adding to them in place; no net -> one zeroing launch over the
-        buffers (the UNet plan is never rebuilt).  keep_closed_nets: every net is in, the closed ones get scale 0."""
-        active = tuple(active)
-        ent = self._sets.get(active)
-        if ent is not None:
-            return ent
-        P, rts = self._parts, self.side_rts
-        included = list(range(len(rts))) if self.keep_closed_nets else list(active)
-        prog = Plan()
-        for k in included:
-            prog.calls += P["heads"][id(rts[k])]
-        prog.calls += P["heads"][id(self.rt)]
-        records = {}
-        for n, k in enumerate(included):
-            calls, records[k] = rts[k].chained_step_calls(rts[0], accumulate=n > 0, scale=0.0,
-                                                         skip=P["skips"][id(rts[k])])
-            prog.calls += calls
-            prog.flops += rts[k].step_plan.flops_executed
-        if not included:
-            prog.add("zero_u64", self.lib.pp_zero_u64, *rts[0].residual_block())
-        prog.calls += [c for i, c in enumerate(self.rt.step_plan.calls) if i not in P["skips"][id(self.rt)]]
-        prog.flops += self.rt.step_plan.flops_executed
-        prog.calls += P["tail"]
-        ent = self._sets[active] = dict(active=active, included=included, program=prog, records=records, graph=None,
-                                        scales=None, program_shallow=None, records_shallow={}, graph_shallow=None)
-        return ent
+    # ---- by-value kernel arguments: a captured graph carries the values of its capture
+    def _baked(self):
+        """What a graph captured now bakes in: the side scale patched into the one side runtime's plan (several ControlNets:
+        none, `_set_scales` drops the graphs it outdates) and the IP-Adapter scales of the UNet's launches."""
+        return self._scale_now(), self.rt.ip_scales()
 
-    def _set_shallow(self, ent):
-        """DeepCache: the set's program over the shallow plans (the same assembly; the zero convs of the live positions)."""
-        if ent["program_shallow"] is not None:
-            return ent["program_shallow"]
-        P, rts = self._parts_shallow, self.side_rts
-        prog = Plan()
-        for k in ent["included"]:
-            prog.calls += P["heads"][id(rts[k])]
-        prog.calls += P["heads"][id(self.rt)]
-        for n, k in enumerate(ent["included"]):
-            calls, ent["records_shallow"][k] = rts[k].chained_step_calls(rts[0], accumulate=n > 0, scale=0.0,
-                                                                         skip=P["skips"][id(rts[k])], shallow=True)
-            prog.calls += calls
-            prog.flops += rts[k].shallow_plan.flops_executed
-        if not ent["included"]:
-            prog.add("zero_u64", self.lib.pp_zero_u64, *rts[0].residual_block())
-        prog.calls += [c for i, c in enumerate(self.rt.shallow_plan.calls) if i not in P["skips"][id(self.rt)]]
-        prog.flops += self.rt.shallow_plan.flops_executed
-        prog.calls += P["tail"]
-        ent["program_shallow"], ent["scales"] = prog, None      # (the scales are written again, into both programs' records)
-        return prog
+    def _stale(self, ent: _StepSet) -> bool:
+        return ent.baked != self._baked()
 
-    def _set_scales(self, ent, scales):
-        """Write this call's per-net scales into the set's zero-conv launch records (by-value kernel arguments: a graph
-        captured with other values is dropped).  Within a call every scale of a set is constant."""
-        want = tuple(float(scales[k]) if k in ent["active"] else 0.0 for k in ent["included"])
-        if want == ent["scales"]:
+    def _set_scales(self, ent: _StepSet, scales):
+        """Several ControlNets: write this call's per-net scales into the set's zero-conv launch records, of both programs
+        (by-value kernel arguments: graphs captured with other values are dropped).  Within a call every scale of a set is
+        constant.  (Same zero convs in every net: the one guess-mode ramp serves each.)"""
+        want = tuple(float(scales[k]) if k in ent.active else 0.0 for k in ent.included)
+        if want == ent.scales:
             return
-        for k, v in zip(ent["included"], want):
-            ramp = self._guess_ramps[k]
-            vals = [r * v for r in ramp] if ramp is not None else [v] * len(ent["records"][k])
-            for rec, x in zip(ent["records"][k], vals):
+        full, sh = ent.records
+        for k, v in zip(ent.included, want):
+            ramp = self._guess_ramp
+            vals = [r * v for r in ramp] if ramp is not None else [v] * len(full[k])
+            for rec, x in zip(full[k], vals):
                 rec.scale = float(x)
-            if k in ent["records_shallow"]:
-                pos = self.side_rts[k].shallow_plan.zero_conv_pos
-                for rec, p_ in zip(ent["records_shallow"][k], pos):
+            if k in sh:
+                for rec, p_ in zip(sh[k], self.side_rts[k].shallow_plan.zero_conv_pos):
                     rec.scale = float(vals[p_])
-        ent["scales"], ent["graph"], ent["graph_shallow"] = want, None, None
+        ent.scales, ent.graph = want, [None, None]
 
-    def _multi_schedule(self, scale_schedule, num_steps):
-        """Per step: the set's entry, its scales written and (use_graph) its graph captured -- all before the first step."""
+    def _multi_schedule(self, scale_schedule, num_steps) -> List[_StepSet]:
+        """Several ControlNets -> per step the set's entry, this call's scales written into it."""
         n = len(self.side_rts)
         if scale_schedule is None:
             raise L.PPError("several ControlNets need a per-step schedule of per-net scales")
         rows = [[float(v) for v in row] for row in scale_schedule[:num_steps]]
         if len(rows) < num_steps or any(len(r) != n for r in rows):
             raise L.PPError(f"scale_schedule must hold {num_steps} rows of {n} per-net scales")
-        ents = []
-        for row in rows:
-            ent = self._set_entry(tuple(k for k, v in enumerate(row) if v != 0.0))
-            ents.append((ent, row))
+        ents = [self._entry(k for k, v in enumerate(row) if v != 0.0) for row in rows]
         seen = {}
-        for ent, row in ents:
-            act = tuple(row[k] for k in ent["active"])
-            if seen.setdefault(ent["active"], act) != act:
+        for ent, row in zip(ents, rows):
+            act = tuple(row[k] for k in ent.active)
+            if seen.setdefault(ent.active, act) != act:
                 raise L.PPError("the scale of an active ControlNet changed inside one call")
         if self._deep() and len(seen) > 1:
             raise L.PPError("DeepCache with several ControlNets whose set of active nets changes during the call (guidance "
                             "windows) is not implemented: one set per call, or DeepCacheSDHelper.disable()")
-        if self._deep():
-            for ent, _ in ents:
-                self._set_shallow(ent)
+        for ent, row in zip(ents, rows):
+            if self._deep() and ent.program[True] is None:      # (a set's shallow program: on demand)
+                self._build(ent, True)
+            self._set_scales(ent, row)
         return ents
 
     # ---- DeepCache: which program an evaluation runs
     def _deep(self) -> bool:
-        return getattr(self, "rt", None) is not None and getattr(self.rt, "shallow_plan", None) is not None and \
+        return self.rt is not None and getattr(self.rt, "shallow_plan", None) is not None and \
             getattr(self.rt.net, "deepcache", None) is not None
 
     def shallow_rows(self, num_steps: int) -> List[bool]:
@@ -659,13 +646,13 @@ class DenoiseLoop:
         iv = int(self.rt.net.deepcache.interval)
         return [e % iv != 0 for e in range(num_steps)]
 
-    def capture(self):
-        """Capture one step into a hipGraph (torch.cuda.CUDAGraph).  The captured launches read the step counter from
-        device memory, so the same graph serves every step."""
-        self._graph_scale = self._scale_now()
-        self._graph_ip = self.rt.ip_scales()          # (IP-Adapter scales: by-value arguments of the UNet's launches as well)
-        self.graph = self._capture_program(self.program)
-        self.graph_shallow = None             # (captured with the same by-value arguments, so it goes with the full one)
+    def capture(self, ent: Optional[_StepSet] = None):
+        """Capture one step (of the default entry, or of `ent`) into a hipGraph (torch.cuda.CUDAGraph).  The captured launches
+        read the step counter from device memory, so the same graph serves every step.  A shallow graph captured with other
+        by-value arguments goes with the full one."""
+        ent = ent if ent is not None else self._sets[self._all]
+        ent.baked = self._baked()
+        ent.graph = [self._capture_program(ent.program[False]), None]
 
     def _capture_program(self, program):
         torch.cuda.synchronize()
@@ -690,19 +677,36 @@ class DenoiseLoop:
         torch.cuda.synchronize()
         return g
 
-    def _schedule(self, scale_schedule, num_steps):
-        """The prologue `run` and `_run_foreign` share -> (ents, scale_schedule, varying).  Several ControlNets: per step
-        the set's entry with this call's scales written, no scalar schedule.  Else the schedule as one scale per step (a
-        wrapper around one net hands rows of one scale) and whether it varies inside the call."""
-        ents = None
+    def _resolve(self, scale_schedule, num_steps, use_graph):
+        """Before the first step of a call -> (per step what `_launch` launches, the per-step scales `_patch_scale` gets when
+        the one side net's scale varies inside the call, else None).  Per step: the entry (several ControlNets: the set
+        active at that step, this call's scales written; else the one entry, a constant scale patched in), its full or
+        shallow program, or with use_graph that program's graph, captured here where there is none or a stale one -- the
+        full one of an entry first: its warm-up leaves a cache tensor the shallow one's reads.  A varying scale runs eagerly."""
+        patches = None
         if self._multi:
             ents = self._multi_schedule(scale_schedule, num_steps)
-            for ent, row in ents:
-                self._set_scales(ent, row)
-            scale_schedule = None
-        elif scale_schedule is not None:
-            scale_schedule = [s[0] if isinstance(s, (list, tuple)) else s for s in scale_schedule]
-        return ents, scale_schedule, scale_schedule is not None and len(set(scale_schedule)) > 1
+        else:
+            ents = [self._sets[self._all]] * num_steps
+            # (a wrapper around one net hands rows of one scale)
+            sched = [s[0] if isinstance(s, (list, tuple)) else s for s in scale_schedule or ()]
+            if len(set(sched)) > 1:
+                use_graph, patches = False, sched if self.side_rt is not None else None
+            elif sched and self.side_rt is not None and self._scale_now() != self._side_scale(sched[0]):
+                self.side_rt._patch_scale(self._side_scale(sched[0]))    # (a previous call may have left a windowed value)
+        steps = []
+        for ent, sh in zip(ents, self.shallow_rows(num_steps)):
+            if use_graph and (ent.graph[False] is None or self._stale(ent)):
+                self.capture(ent)
+            if use_graph and sh and ent.graph[True] is None:
+                ent.graph[True] = self._capture_program(ent.program[True])
+            steps.append((ent.graph if use_graph else ent.program)[sh])
+        return steps, patches
+
+    @staticmethod
+    def _launch(what, stream):
+        """One step: a program's launches into `stream`, or the replay of its captured graph."""
+        what.run(stream) if isinstance(what, Plan) else what.replay()
 
     def run(self, latents: torch.Tensor, num_steps: int, use_graph: bool = True,
             callback: Optional[Callable] = None, timesteps=None, scale_schedule: Optional[List[float]] = None):
@@ -710,51 +714,27 @@ class DenoiseLoop:
         if self.foreign:
             return self._run_foreign(latents, num_steps, use_graph, callback, timesteps, scale_schedule)
         self.scheduler.reset()
-        if getattr(self, "_ticket", None) is not None:
+        if self._ticket is not None:
             self._ticket.zero_()       # (an aborted launch must not leave the step counter's ticket mid-count)
-        if self._keep[2] is not None:
-            self._keep[2].zero_()
+        if self._keep.m_prev is not None:
+            self._keep.m_prev.zero_()
         self._fill_temb_tables()
         if self._pag is not None:
-            self._fill_pag_table(self._keep[0])
+            self._fill_pag_table(self._keep.ts)
         if self._rescale is not None:
             self._fill_phi_cell()
         self.latents.copy_(latents.to(self.latents.device, torch.float32))
-        ents, scale_schedule, varying = self._schedule(scale_schedule, num_steps)
-        shallow = self.shallow_rows(num_steps)
-        if ents is not None and use_graph:        # (every set's graph before the first step)
-            for (ent, _), sh in zip(ents, shallow):
-                if ent["graph"] is None:          # (the full program first: its warm-up leaves a c the shallow one's can read)
-                    ent["graph"] = self._capture_program(ent["program"])
-                if sh and ent["graph_shallow"] is None:
-                    ent["graph_shallow"] = self._capture_program(ent["program_shallow"])
-        if not varying and scale_schedule and self.side_rt is not None and \
-                self._scale_now() != self._side_scale(scale_schedule[0]):
-            self.side_rt._patch_scale(self._side_scale(scale_schedule[0]))   # (a previous call may have left a windowed value)
-        if use_graph and not varying and (self.graph is None or self._graph_scale != self._scale_now() or
-                                          getattr(self, "_graph_ip", ()) != self.rt.ip_scales()):
-            self.capture()
-        if use_graph and not varying and ents is None and any(shallow) and self.graph_shallow is None:
-            self.graph_shallow = self._capture_program(self.program_shallow)
+        steps, patches = self._resolve(scale_schedule, num_steps, use_graph)
         stream = torch.cuda.current_stream().cuda_stream
         for i in range(num_steps):
-            if varying and self.side_rt is not None:
-                self.side_rt._patch_scale(self._side_scale(scale_schedule[i]))
+            if patches is not None:
+                self.side_rt._patch_scale(self._side_scale(patches[i]))
             # this row's noise, by the scheduler's own rule (stream-ordered before the step that consumes it)
             z = self.scheduler.noise_for(self.scheduler.begin_index + i, self.latents.shape, self._gen, self.latents.device,
                                          self._noise_dtype)
             if z is not None:
                 self._var_noise.copy_(z)
-            sfx = "_shallow" if shallow[i] else ""
-            if ents is not None:
-                if use_graph:
-                    ents[i][0]["graph" + sfx].replay()
-                else:
-                    ents[i][0]["program" + sfx].run(stream)
-            elif use_graph and not varying:
-                (self.graph_shallow if shallow[i] else self.graph).replay()
-            else:
-                (self.program_shallow if shallow[i] else self.program).run(stream)
+            self._launch(steps[i], stream)
             if callback is not None:
                 callback(i, timesteps[i] if timesteps is not None else None, self.latents)
         self._check_faults()
@@ -764,7 +744,7 @@ class DenoiseLoop:
         """Where a plan combines split-K in-kernel (launches of 2 / 4 co-resident splits: pp_gemm_combine_ctr_bytes()): the
         plan's fault word is examined WITHOUT a synchronisation -- copied to pinned memory behind this call's work, read by a
         later call (NetRuntime.check_faults).  `flush_faults()` is the blocking form for a caller that synchronises anyway."""
-        for r in [getattr(self, "rt", None)] + list(getattr(self, "side_rts", [])):
+        for r in [self.rt] + self.side_rts:
             if r is not None and r.combines_in_kernel():
                 r.check_faults(blocking=blocking)
 
@@ -791,36 +771,15 @@ class DenoiseLoop:
         self._fill_temb_tables()
         self._f_step.zero_()
         lat = latents.to(self.latents.device, torch.float32).clone()
-        ents, scale_schedule, varying = self._schedule(scale_schedule, num_steps)
-        shallow = self.shallow_rows(num_steps)
+        steps, patches = self._resolve(scale_schedule, num_steps, use_graph)
         stream = torch.cuda.current_stream().cuda_stream
         for i in range(num_steps):
             t = tl[i]
-            sfx = "_shallow" if shallow[i] else ""
             x = sch.scale_model_input(lat, t) if hasattr(sch, "scale_model_input") else lat
             self._f_x.copy_(x)
-            if varying and self.side_rt is not None:
-                self.side_rt._patch_scale(self._side_scale(scale_schedule[i]))
-            if ents is not None:
-                ent = ents[i][0]
-                if use_graph:
-                    if ent["graph" + sfx] is None:
-                        ent["graph" + sfx] = self._capture_program(ent["program" + sfx])
-                        self._f_step.fill_(i)
-                    ent["graph" + sfx].replay()
-                else:
-                    ent["program" + sfx].run(stream)
-            elif use_graph and not varying:
-                if self.graph is None or self._graph_scale != self._scale_now() or \
-                        getattr(self, "_graph_ip", ()) != self.rt.ip_scales():
-                    self.capture()
-                    self._f_step.fill_(i)
-                if shallow[i] and self.graph_shallow is None:
-                    self.graph_shallow = self._capture_program(self.program_shallow)
-                    self._f_step.fill_(i)
-                (self.graph_shallow if shallow[i] else self.graph).replay()
-            else:
-                (self.program_shallow if shallow[i] else self.program).run(stream)
+            if patches is not None:
+                self.side_rt._patch_scale(self._side_scale(patches[i]))
+            self._launch(steps[i], stream)
             eps = self.rt.eps_tensor()
             # (guidance_rescale is only ever on with CFG: the conditional prediction is the second segment of two or three)
             text = eps.chunk(3 if self._pag is not None else 2)[1] if self._rescale is not None else None

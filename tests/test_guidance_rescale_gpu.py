@@ -212,8 +212,8 @@ def test_controlnet_pipeline_two_nets_one_window_closing():
                mask_latents=mask.to(DEV), masked_image_latents=mil.to(DEV), output_type="latent", return_dict=False,
                guidance_rescale=PHI)[0]
     for ent in pipe._loop._sets.values():                 # (one program per set of active nets: each has the launch)
-        names = _names(ent["program"].calls)
-        assert names.count("cfg_rescale") == 1 and ent["program"].calls[names.index("cfg_rescale") + 1][1][1] == 0
+        names = _names(ent.program[False].calls)
+        assert names.count("cfg_rescale") == 1 and ent.program[False].calls[names.index("cfg_rescale") + 1][1][1] == 0
     assert len(pipe._loop._sets) == 2
     close(out, ref, "guidance_rescale ControlNet pipeline, two nets, one window closing")
 

@@ -552,7 +552,7 @@ def test_time_embedding_chain_is_where_the_loop_expects_it():
         net.load_state_dict(net.synthetic_state_dict(meta=True), "cpu", materialize=False)
         rt = NetRuntime(net, "cpu")
         rt.ensure(2, 16, 16, 77, 9 if kind != "controlnet" else 4, ("plain",), cond_hw=(128, 128))
-        info = DenoiseLoop._temb_split(types.SimpleNamespace(), rt, torch.zeros(7))
+        info = DenoiseLoop._temb_split(types.SimpleNamespace(_temb_tables={}), rt, torch.zeros(7))
         assert info is not None, kind
         names = [rt.step_plan.calls[i][2] for i in info["idx"]]
         assert names == ["timestep_embedding", "linear_skinny", "linear_skinny", "linear_skinny"], (kind, names)

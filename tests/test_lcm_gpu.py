@@ -252,7 +252,7 @@ def test_fused_loop_with_two_controlnets_whose_windows_differ():
         record(f"[lcm] loop audit, two ControlNets with windows, {'graph' if use_graph else 'eager'}: worst err / bound {w:.3g}")
     assert len(loop._sets) > 2
     for ent in loop._sets.values():
-        names = _names(ent["program"].calls)
+        names = _names(ent.program[False].calls)
         assert names[-1] == "cfg_lcm_step" and names.count("cfg_lcm_step") == 1 and "step_advance" not in names
 
 

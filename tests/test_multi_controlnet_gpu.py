@@ -298,9 +298,9 @@ def test_closed_windows_are_skipped_exactly():
         skip = DenoiseLoop(unet, PS.DDIMScheduler(), side=w, side_kind="controlnet")
         out_skip = _loop_run(skip, unet, nets, rows, use_graph=True, guess=guess)
         assert sorted(skip._sets) == sorted(set(sets) | {(0, 1)})
-        unet_names = [c[2] for i, c in enumerate(skip.rt.step_plan.calls) if i not in skip._parts["skips"][id(skip.rt)]]
-        tail = _names(skip._parts["tail"])
-        heads = skip._parts["heads"]
+        unet_names = [c[2] for i, c in enumerate(skip.rt.step_plan.calls) if i not in skip._parts[False]["skips"][id(skip.rt)]]
+        tail = _names(skip._parts[False]["tail"])
+        heads = skip._parts[False]["heads"]
         for st in set(sets):
             want = []
             for k in st:
@@ -308,21 +308,21 @@ def test_closed_windows_are_skipped_exactly():
             want += _names(heads[id(skip.rt)])
             for n, k in enumerate(st):
                 rt = skip.side_rts[k]
-                body = [c[2] for i, c in enumerate(rt.step_plan.calls) if i not in skip._parts["skips"][id(rt)]]
+                body = [c[2] for i, c in enumerate(rt.step_plan.calls) if i not in skip._parts[False]["skips"][id(rt)]]
                 if guess and n > 0:
                     body.remove("zero_u64")                     # (the zeroing of the unconditional halves: once per step)
                 want += body
             if not st:
                 want += ["zero_u64"]
             want += unet_names + tail
-            assert _names(skip._sets[st]["program"].calls) == want, st
+            assert _names(skip._sets[st].program[False].calls) == want, st
         # nothing but the networks' own launches (and ONE zeroing launch for the empty set): the sum costs no launch
-        assert len(skip._sets[()]["program"].calls) == len(heads[id(skip.rt)]) + 1 + len(unet_names) + len(tail)
+        assert len(skip._sets[()].program[False].calls) == len(heads[id(skip.rt)]) + 1 + len(unet_names) + len(tail)
         out_skip_eager = _loop_run(skip, unet, nets, rows, use_graph=False, guess=guess)
         keep = DenoiseLoop(unet, PS.DDIMScheduler(), side=w, side_kind="controlnet", keep_closed_nets=True)
         out_keep = _loop_run(keep, unet, nets, rows, use_graph=True, guess=guess)
         for st in keep._sets:
-            assert _names(keep._sets[st]["program"].calls) == _names(keep._sets[(0, 1)]["program"].calls)
+            assert _names(keep._sets[st].program[False].calls) == _names(keep._sets[(0, 1)].program[False].calls)
         assert torch.equal(out_skip, out_keep), f"guess={guess}: skipping closed nets changed the latents"
         assert torch.equal(out_skip, out_skip_eager)
         every = _loop_run(skip, unet, nets, [[0.5, 0.8]] * 4, use_graph=True, guess=guess)

@@ -403,10 +403,10 @@ def test_fused_loop_with_two_controlnets_whose_windows_differ():
                run_kw=dict(scale_schedule=rows), oracle_eps=oracle_eps if use_graph else None)
     assert len(loop._sets) > 2
     for ent in loop._sets.values():
-        names = _names(ent["program"].calls)
+        names = _names(ent.program[False].calls)
         assert names[-1] == "cfg_sigma_step" and names.count("cfg_sigma_step") == 1 and "step_advance" not in names
-        heads = [c for c in ent["program"].calls if c[2] == "step_head"]
-        assert len(heads) == len(ent["included"]) + 1 and all(c[0] is L.lib().pp_step_head_scaled for c in heads)
+        heads = [c for c in ent.program[False].calls if c[2] == "step_head"]
+        assert len(heads) == len(ent.included) + 1 and all(c[0] is L.lib().pp_step_head_scaled for c in heads)
     _same_launch_count_as_ddim(loop, unet, bind, side=side)
 
 

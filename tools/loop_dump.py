@@ -5,7 +5,9 @@ scalar argument and every field of each ctypes struct (PPGemmArgs) verbatim, eve
 appearance within the case -- two runs whose buffers sit elsewhere compare equal, a mis-wired pointer does not -- and
 `program.flops`.  Cases: the eleven scheduler classes x {UNet alone, BrushNet + 4-channel UNet, one ControlNet, two ControlNets
 whose guidance windows differ (the program of every active set)} x CFG on / off; DDIM at eta = 0.5; the 4-channel blend for DDIM,
-LCM, Euler a and Heun; guess mode with a ControlNet; a duck-typed scheduler; each refusal as one line carrying the error text.
+LCM, Euler a and Heun; guess mode with a ControlNet; a duck-typed scheduler; each refusal as one line carrying the error text;
+DeepCache on every configuration (the shallow program next to the full one; two ControlNets: per set); perturbed-attention
+guidance and guidance_rescale, alone and together; a MultiControlNetModel around one net; keep_closed_nets.
 Two trees whose dumps are equal byte for byte bind the same programs (TREE: the checkout to import from, default this one)."""
 import ctypes
 import os
@@ -17,6 +19,7 @@ sys.path.insert(0, tree)
 import torch
 from powerpaint_amd import _lib as L
 from powerpaint_amd import models as PM, pipelines as PP, schedulers as PS
+from powerpaint_amd.engine import DeepCache
 from powerpaint_amd.pipelines._loop import DenoiseLoop
 
 DEV = "cuda:0"
@@ -105,8 +108,19 @@ def scheduler(name, opts):
     return sch
 
 
-def bound(config, sch, do_cfg, **kw):
-    """-> [(tag, program)] of one bind."""
+def set_programs(loop, active, deep):
+    """-> (full, shallow or None): the programs of one set of active ControlNets, its row of scales written."""
+    ent = loop._entry(active)
+    if deep and ent.program[True] is None:
+        loop._build(ent, True)
+    loop._set_scales(ent, next((r for r in ROWS if tuple(k for k, v in enumerate(r) if v != 0.0) == active), [0.5, 0.8]))
+    return ent.program
+
+
+def bound(config, sch, do_cfg, deep=False, keep_closed_nets=False, **kw):
+    """-> [(tag, program)] of one bind; deep: DeepCache on every network, the shallow program behind each full one."""
+    for m in [unet9, unet4, brush] + cnets:
+        m.net.deepcache = DeepCache(0, 2) if deep else None
     p, shape, v1 = pe(do_cfg), (B, 4, S, S), [(mask, 4), (mil, 5)]
     if config == "unet":
         loop = DenoiseLoop(unet9, sch).bind(shape, do_cfg, 7.5, p, static_inputs=v1, **kw)
@@ -118,13 +132,17 @@ def bound(config, sch, do_cfg, **kw):
     elif config == "controlnet":
         loop = DenoiseLoop(unet9, sch, side=cnets[0], side_kind="controlnet").bind(
             shape, do_cfg, 7.5, p, prompt_embeds_side=p, static_inputs=v1, controlnet_cond=imgs[0], side_scale=0.7, **kw)
+    elif config == "wrapped controlnet":
+        loop = DenoiseLoop(unet9, sch, side=PM.MultiControlNetModel(cnets[:1]), side_kind="controlnet").bind(
+            shape, do_cfg, 7.5, p, prompt_embeds_side=p, static_inputs=v1, controlnet_cond=imgs[:1], side_scale=[0.7], **kw)
     else:
-        loop = DenoiseLoop(unet9, sch, side=PM.MultiControlNetModel(cnets), side_kind="controlnet").bind(
+        loop = DenoiseLoop(unet9, sch, side=PM.MultiControlNetModel(cnets), side_kind="controlnet",
+                           keep_closed_nets=keep_closed_nets).bind(
             shape, do_cfg, 7.5, p, prompt_embeds_side=p, static_inputs=v1, controlnet_cond=imgs, side_scale=[0.5, 0.8], **kw)
-        for ent, row in loop._multi_schedule(ROWS, STEPS):
-            loop._set_scales(ent, row)
-        return [(f"set {k}", loop._sets[k]["program"]) for k in sorted(loop._sets)]
-    return [("", loop.program)]
+        sets = sorted({tuple(k for k, v in enumerate(r) if v != 0.0) for r in ROWS} | {(0, 1)})
+        progs = [(f"set {k}", set_programs(loop, k, deep)) for k in sets]
+        return [(tag + sfx, pr) for tag, pair in progs for sfx, pr in zip(("", " shallow"), pair) if pr is not None]
+    return [("", loop.program)] + ([(" shallow", loop.program_shallow)] if deep else [])
 
 
 lines, n_cases = [], 0
@@ -162,6 +180,29 @@ for config in ("unet", "controlnet"):
 case("KDPM2DiscreteScheduler unet4 blend", "unet4", "KDPM2DiscreteScheduler", SD15, True, blend=blend)
 case("EulerDiscreteScheduler unet PP_LAB=1 PP_TEMB_TABLE=0", "unet", "EulerDiscreteScheduler", SD15, True,
      env=dict(PP_LAB="1", PP_TEMB_TABLE="0"))
+ALL = ("unet", "brushnet", "controlnet", "two controlnets")
+for name, opts in (CLASSES[0], CLASSES[4], CLASSES[6], CLASSES[7]):
+    for config in ALL:
+        for do_cfg in (True, False):
+            case(f"{name} {config} cfg={do_cfg} DeepCache", config, name, opts, do_cfg, deep=True)
+for config in ("unet", "controlnet", "two controlnets"):
+    case(f"duck-typed scheduler {config} cfg=True DeepCache", config, "Duck", {}, True, deep=True)
+for config in ALL:
+    for do_cfg in (True, False):
+        case(f"DDIMScheduler {config} cfg={do_cfg} pag", config, "DDIMScheduler", {}, do_cfg, pag_scale=3.0, pag_adaptive_scale=0.1)
+for name, opts in (CLASSES[0], CLASSES[6]):
+    for config in ALL:
+        for pag_scale in (0.0, 3.0):
+            case(f"{name} {config} guidance_rescale pag_scale={pag_scale}", config, name, opts, True, guidance_rescale=0.7,
+                 pag_scale=pag_scale)
+case("duck-typed scheduler two controlnets cfg=True", "two controlnets", "Duck", {}, True)
+for do_cfg in (True, False):
+    case(f"DDIMScheduler wrapped controlnet cfg={do_cfg}", "wrapped controlnet", "DDIMScheduler", {}, do_cfg)
+    case(f"DDIMScheduler two controlnets keep_closed_nets cfg={do_cfg}", "two controlnets", "DDIMScheduler", {}, do_cfg,
+         keep_closed_nets=True)
+case("DDIMScheduler wrapped controlnet DeepCache", "wrapped controlnet", "DDIMScheduler", {}, True, deep=True)
+case("DDIMScheduler two controlnets keep_closed_nets DeepCache", "two controlnets", "DDIMScheduler", {}, True, deep=True,
+     keep_closed_nets=True)
 assert sum(": refused: " in ln for ln in lines) == 2, "both refusals were to be met, and nothing else refused"
 open(out, "w").write("\n".join(lines) + "\n")
 print(len(lines), "lines,", n_cases, "cases,", sum(ln.startswith("## ") for ln in lines), "programs and refusals, library",

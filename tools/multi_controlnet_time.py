@@ -75,7 +75,7 @@ def main():
         torch.cuda.synchronize()
         assert torch.isfinite(out).all()
         loop = p._loop
-        sets = {k: len(v["program"].calls) for k, v in loop._sets.items()} if loop._multi else None
+        sets = {k: len(v.program[False].calls) for k, v in loop._sets.items()} if loop._multi else None
         print(f"{name}: launches per step {len(loop.program.calls)}, twin prefix UNet {loop.rt.twin} nets "
               f"{[r.twin for r in loop.side_rts]}" + (f", launches per active set {sets}" if sets else ""))
     times = {name: [] for name, _, _ in variants}
