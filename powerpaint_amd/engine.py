@@ -216,6 +216,20 @@ class Act:
         return self.rows * self.C * 2
 
 
+class TapF32(NamedTuple):
+    """A recorded tensor (Builder.taps) that is no NHWC Act of the 16-bit format: fp32, dense, `shape` as stored (the UNet's
+    eps: NCHW; temb_all: one row)."""
+    ptr: int
+    shape: Tuple[int, ...]
+
+    @property
+    def nbytes(self) -> int:
+        n = 4
+        for d in self.shape:
+            n *= d
+        return n
+
+
 class Plan:
     """Flat list of C-ABI launches with baked arguments."""
 
@@ -302,7 +316,10 @@ class Builder:
         self.gn_acc_used = 0
         # device word the in-kernel split-K combine counts placement violations in (NetRuntime.check_faults); 0 = none given
         self.fault_ptr = 0
-        # (name, Act[, accumulator pointer]) of block outputs, in plan order, for the builds that record them (vae.py)
+        # (name, Act[, accumulator pointer]) of block outputs, in plan order, for the builds that record them (vae.py).
+        # SDNet.build_step: (name, Act | TapF32) of a block output, which keeps its bytes to the end of the plan, and
+        # (name, Act, call) of a tensor inside a block, whose memory is released behind the block: `call` is the entry of
+        # plan.calls that completes it (the tuple itself: an index would move when a launch is put in front of the plan)
         self.taps: List[Tuple] = []
 
     # -- memory
@@ -311,6 +328,10 @@ class Builder:
 
     def new_act(self, B, H, W, Cc) -> Act:
         return Act(self.alloc(B * H * W * Cc * 2), B, H, W, Cc)
+
+    def tap_inner(self, name: str, act: "Act"):
+        """Record a tensor inside a block: complete once the launch recorded last has run."""
+        self.taps.append((name, act, self.plan.calls[-1]))
 
     def mark(self):
         return self.arena.mark()
@@ -821,6 +842,16 @@ class _TransformerBlock:
         self.rows_o = 2 * x.rows if twin else x.rows
         self.tiles = (x.C + 159) // 160
 
+    def tap(self, what: str, ptr: int, rows: int):
+        """Record one of the tensors the chosen form stores (Builder.taps); the launch recorded last completes it."""
+        x = self.x
+        self.pb.tap_inner(f"{self.pre}.{what}", Act(ptr, rows // self.hw, x.H, x.W, x.C))
+
+    def attend_tapped(self, hs: int, *args, **kw) -> int:
+        a = self.attend(hs, *args, **kw)
+        self.tap("attn1", a, self.rows)
+        return a
+
     def producer(self, rows: int) -> int:
         """Row-moment buffer written by the GEMM that produces the next LayerNorm's input."""
         return self.pb.alloc(rows * self.tiles * 8) if self.net.fold_ln else 0
@@ -855,23 +886,25 @@ class _TransformerBlock:
                             P[f"{tb}.attn1.qkv.weight_kp"], P[f"{tb}.attn1.qkv.colsum"], P[f"{tb}.attn1.qkv.bias"], 1e-5, hs, Cc,
                             qk, 2 * Cc, vt, hw, rows, Cc, hw, (float(d) ** -0.5) * 1.4426950408889634 if log2q else 1.0, pb.dt)
                 pb.plan.count("tfront", 2.0 * rows * Cc * Cc + 2.0 * rows * 3 * Cc * Cc)     # (proj_in + QKV)
-                return hs, self.attend(hs, qk, 2 * Cc, vt, hw, log2q=log2q)
+                self.tap("proj_in", hs, rows)
+                return hs, self.attend_tapped(hs, qk, 2 * Cc, vt, hw, log2q=log2q)
         st = self.producer(rows)
         n = pb.groupnorm(x, P[f"{pre}.norm.weight"], P[f"{pre}.norm.bias"], 1e-6, False, groups=net.groups)
         hs = pb.linear(n.ptr, rows, Cc, P[f"{pre}.proj_in.weight"], Cc, P[f"{pre}.proj_in.bias"], row_stats_out=st,
                        name="conv1x1")
+        self.tap("proj_in", hs, rows)
         ln, kw = self.normed(hs, st, "norm1", "attn1.qkv", rows)
         if hw % 8 == 0:       # fused QKV GEMM, V written transposed by the epilogue
             vt = pb.alloc(x.B * Cc * hw * 2)
             qk = pb.linear(ln, rows, Cc, P[f"{tb}.attn1.qkv.weight"], 3 * Cc, out_vt=vt, vt_col0=2 * Cc, vt_ld=hw,
                            rows_per_batch=hw, name="linear", **kw)
-            return hs, self.attend(hs, qk, 2 * Cc, vt, hw)
+            return hs, self.attend_tapped(hs, qk, 2 * Cc, vt, hw)
         # tiny latents (hw < 8, e.g. 2x2): V^T rows must be 16-byte aligned and zero padded -> unfused transpose
         ldvt = _align(hw, 8)
         vt = pb.alloc(x.B * Cc * ldvt * 2)
         qkv = pb.linear(ln, rows, Cc, P[f"{tb}.attn1.qkv.weight"], 3 * Cc, name="linear", **kw)
         pb.plan.add("transpose_v", pb.lib.pp_transpose_v, qkv + 4 * Cc, 3 * Cc, x.B, hw, Cc, vt, ldvt)
-        return hs, self.attend(hs, qkv, 3 * Cc, vt, ldvt)
+        return hs, self.attend_tapped(hs, qkv, 3 * Cc, vt, ldvt)
 
     def tome_r(self) -> int:
         """Sources this block merges in front of its self-attention (0: none -- SDNet.tome_layout decides)."""
@@ -946,10 +979,12 @@ class _TransformerBlock:
                         P[f"{tb}.attn2.to_out.bias"], o, Cc, st or None, rows_o, Cc, hw, wrap,
                         P[f"{tb}.attn1.to_out.weight"], P[f"{tb}.attn1.to_out.bias"], pb.dt)
             pb.plan.count("xattn_block", 6.0 * rows_o * Cc * Cc + 4.0 * rows_o * net._nctx * Cc)   # (+ attn1.to_out)
+            self.tap("attn2", o, rows_o)
             return o, st
         st = self.producer(rows)
         hs = pb.linear(a, rows, Cc, P[f"{tb}.attn1.to_out.weight"], Cc, P[f"{tb}.attn1.to_out.bias"], res1=hs,
                        row_stats_out=st, name="linear")
+        self.tap("attn1_out", hs, rows)
         ln, kw = self.normed(hs, st, "norm2", "attn2.to_q", rows)
         if form is XAttnForm.TWO_GEMM:
             # the folded sub-block as two GEMMs with one (G^T, H^T) per batch item (setup plan: pp_xattn_fold(kperm = 2))
@@ -981,6 +1016,7 @@ class _TransformerBlock:
             st = self.producer(rows)
             hs = pb.linear(a, rows, Cc, P[f"{tb}.attn2.to_out.weight"], Cc, P[f"{tb}.attn2.to_out.bias"], res1=hs,
                            row_stats_out=st, name="linear")
+        self.tap("attn2", hs, rows_o)
         return hs, st
 
     def feed_forward(self, hs: int, st: int, out: int, res2: int):
@@ -1707,10 +1743,12 @@ class SDNet:
 
         h = pb.conv3x3(x, P[f"{pre}.conv1.weight"], cout, P[f"{pre}.conv1.bias"], x2=x2,
                        rowvec=temb_all + 4 * self.temb_off[pre], name="conv3x3", gn_in=gn("norm1"))
+        pb.tap_inner(pre + ".conv1", h)
         if cin != cout and self.merge_shortcut:
             pb.conv3x3(h, P[f"{pre}.conv2.weight"], cout, P[f"{pre}.conv2.bias"], res2=res2, out=out, x3=x, x4=x2,
                        name="conv3x3", gn_in=gn("norm2"))
             pb.release(m)
+            pb.taps.append((pre, out))
             return out
         if cin != cout:
             sc = pb.linear(x.ptr, x.rows, x.C, P[f"{pre}.conv_shortcut.weight"], cout, P[f"{pre}.conv_shortcut.bias"],
@@ -1721,6 +1759,7 @@ class SDNet:
         pb.conv3x3(h, P[f"{pre}.conv2.weight"], cout, P[f"{pre}.conv2.bias"], res1=sc, res2=res2, out=out,
                    name="conv3x3", gn_in=gn("norm2"))
         pb.release(m)
+        pb.taps.append((pre, out))
         return out
 
     def xattn_form(self, lib, c: int, hw: int, B: int, nctx: int) -> XAttnForm:
@@ -1763,6 +1802,7 @@ class SDNet:
         hs, st = t.cross_attention(hs, a, self.xa.get(pre), kv)
         out.producer = t.feed_forward(hs, st, out.ptr, res2)
         pb.release(m)
+        pb.taps.append((pre, out))
         return out
 
     def _resampler(self, pb: Builder, R: str, sp, x_in: int, N: int, S: int, lat0: int) -> int:
@@ -2003,6 +2043,7 @@ class SDNet:
                     P["time_embedding.linear_2.bias"], te, temb, te, 0, 0, pb.dt)
         pb.plan.add("linear_skinny", lib.pp_linear_skinny, temb, 1, te, P["temb_all.weight"], P["temb_all.bias"],
                     self.temb_total, temb_all, self.temb_total, L.PP_ACT_SILU, 0, pb.dt)
+        pb.taps.append(("temb_all", TapF32(temb_all, (self.temb_total,))))
 
         # 2. conv_in: the implicit-GEMM conv over the zero-padded input (4 / 9 real channels in one 64-deep K chunk per
         # tap: 6x the algorithmic MACs, still 4x faster than the scalar direct conv at 64x64 -- 9 short K steps on the
@@ -2021,11 +2062,14 @@ class SDNet:
         if self.kind == "controlnet":
             s = conv_in(self.cond_emb.ptr)
             skips = [s]
+            pb.taps.append(("conv_in", s))
         else:
             s = conv_in(None)
             skips = [s]                       # captured BEFORE the BrushNet add (unet_2d_condition.py:1220-1223)
+            pb.taps.append(("conv_in", s))
             if brush:
                 s = conv_in(pop(add_down))
+                pb.taps.append(("conv_in.add_sample", s))
         if twin:                              # the half the prefix goes on with (skips[0] stays the full, twice-stored tensor)
             s = Act(s.ptr, B // 2, s.H, s.W, s.C, producer=s.producer)
 
@@ -2048,6 +2092,7 @@ class SDNet:
                 s = pb.conv3x3(s, P[pre + ".weight"], boc[i], P[pre + ".bias"], stride=2, res2=pop(add_down),
                                name="conv3x3")
                 skips.append(s)
+                pb.taps.append((f"down_blocks.{i}.downsamplers.0", s))
                 walk["down"].append(f"down_blocks.{i}.downsamplers.0")
 
         # 4. mid
@@ -2081,6 +2126,7 @@ class SDNet:
                     continue
                 pb.linear(f.ptr, f.rows, c, P[pre + ".weight"], c, P[pre + ".bias"], scale=scale,
                           out=o.ptr + (f.rows * c * 2 if pad_uncond else 0), name="zero_conv")
+                pb.taps.append((pre, o))
             return outs
 
         if self.kind == "controlnet":
@@ -2096,6 +2142,7 @@ class SDNet:
             for sk, cp in zip(skips, ctrl_down):
                 o = pb.new_act(sk.B, sk.H, sk.W, sk.C)
                 pb.add(sk.ptr, cp, o.ptr, sk.rows * sk.C)
+                pb.taps.append((f"skip_add.{len(new)}", o))
                 new.append(o)
             skips = new
 
@@ -2153,6 +2200,7 @@ class SDNet:
                 else:
                     s = pb.conv3x3(s, P[pre + ".weight"], rev[i], P[pre + ".bias"], up=True, up_size=tgt,
                                    res2=pop(add_up), name="conv3x3")
+                pb.taps.append((f"up_blocks.{i}.upsamplers.0", s))
                 brush_up.append(s)
 
         if self.kind == "brushnet":
@@ -2176,5 +2224,6 @@ class SDNet:
             pb.plan.add("conv_out", lib.pp_conv3x3_smallcout, h.ptr, B, H, W, boc[0], P["conv_out.weight"],
                         P["conv_out.bias"], self.out_channels, eps, pb.dt)
         pb.plan.count("conv_out", 2.0 * B * H * W * self.out_channels * 9 * boc[0])
+        pb.taps.append(("eps", TapF32(eps, (B, self.out_channels, H, W))))
         pb.plan.walk = walk
         return dict({"eps": eps}, **({"cache": cache_act} if depth else {}))

@@ -208,6 +208,9 @@ class NetRuntime:
         outs = net.build_step(pb, lay["x_in"], lay["t_dev"], scale=1.0, twin=twin, **kw)
         if pb.gn_acc_used:
             pb.plan.calls.insert(0, (L.lib().pp_zero_u64, (lay["gn_acc"], pb.gn_acc_used // 8), "zero_u64"))
+        # what build_step recorded (Builder.taps; DESIGN.md "Taps"): block outputs, and tensors inside blocks with the entry of
+        # plan.calls that completes each (the tuple, so the launch inserted above moves nothing)
+        lay["taps"] = pb.taps
         if dc is not None:
             # DeepCache: the shallow form of the same walk, a plan of its own on the same arena.  Its tensors lie ABOVE everything
             # the full plan allocated: nothing it writes can touch c (which lives among the full plan's tensors), the setup
