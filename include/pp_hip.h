@@ -1063,6 +1063,33 @@ int pp_masked_image_pack(const float* image, const float* mask, int batch, int c
 int pp_mask_blend(const void* sample, const void* cond, const float* mask, void* out, int batch, int h, int w, int c,
                   int mask_h, int mask_w, int64_t* acc, int groups, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * (added under ABI 29; purely additive) AutoencoderTiny -- TAESD, diffusers' autoencoder_tiny.py (vae.py: EncoderTiny /
+ * DecoderTiny / AutoencoderTinyBlock): a 64-channel conv net without norms or attention on the SD latent space.
+ *
+ * pp_conv3x3_c64: nn.Conv2d(64, 64, 3, padding=1) with bias, residual and ReLU in the epilogue,
+ *       out = [relu](acc + bias + res),   fp32 accumulator over the 576 products, ONE rounding to `dtype`.
+ *     x    : 16-bit NHWC [batch][hin][win][64], 16-byte aligned
+ *     w    : 16-bit [64][3][3][64] = [cout][(3 ky + kx) 64 + cin], 16-byte aligned
+ *     bias : fp32 [64], 16-byte aligned, or NULL
+ *     res  : NULL, or a 16-bit NHWC tensor of the output's shape, 8-byte aligned; must not alias out
+ *     out  : 16-bit NHWC [batch][hout][wout][64], 8-byte aligned
+ *     mode : 0  stride 1, hout = hin
+ *            1  stride 2, symmetric padding 1, hout = (hin - 1) / 2 + 1 (odd sides included)
+ *            2  nn.Upsample(scale_factor=2, mode="nearest") in front of the stride-1 conv: the conv reads source pixel
+ *               (output pixel >> 1), its padding 1 lies at the output resolution, hout = 2 hin
+ *   The whole weight matrix is kept in LDS by persistent workgroups that walk the output tiles; the input tile with its
+ *   one-pixel halo is staged in LDS, so an input element is fetched once per tile.  No atomics, no workspace.  A value is one
+ *   fixed-order sum: it does not depend on `batch` or on the item's place in the batch.  PP_ERR_BAD_ARG for a dtype that is
+ *   not bf16 / fp16, a NULL x / w / out, mode outside 0..2, non-positive sizes or a misaligned pointer -- without a launch.
+ * pp_taesd_pack: the two maps at the module boundary.  src fp32 | bf16 | fp16 (src_dtype: PP_DT_*) NCHW [batch][c][h w], c <= 8
+ *   -> out 16-bit NHWC [batch][h w][8] (16-byte aligned; what pp_conv3x3_direct reads), channels [c, 8) WRITTEN as zeros.
+ *     mode 0 (image)  : (x + 1) / 2            mode 1 (latents): 3 tanh(x / 3)   (+-inf -> +-3)
+ *   fp32 arithmetic, one rounding to `dtype`. */
+int pp_conv3x3_c64(const void* x, int batch, int hin, int win, const void* w, const float* bias, const void* res, int mode,
+                   int relu, void* out, int dtype, void* stream);
+int pp_taesd_pack(const void* src, int src_dtype, int batch, int c, int h, int w, int mode, void* out, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,8 @@ SIGNATURES = {
     "pp_relu": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp]),
     "pp_masked_image_pack": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "pp_mask_blend": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
+    "pp_conv3x3_c64": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "pp_taesd_pack": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
 }
 
 _lib = None

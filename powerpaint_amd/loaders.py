@@ -75,11 +75,13 @@ def config_class_name(d: str) -> str:
 
 def load_vae(root: str, device="cuda", torch_dtype=None, subfolder: Optional[str] = "vae", revision=None):
     """The VAE of a pipeline folder, by the `_class_name` of its config.json: `AsymmetricAutoencoderKL` (the mask-conditioned
-    decoder; computes in `torch_dtype` if that is a 16-bit format) or, for every other name, `AutoencoderKL` as before."""
+    decoder) and `AutoencoderTiny` (TAESD) compute in `torch_dtype` if that is a 16-bit format; every other name gives
+    `AutoencoderKL` as before."""
     from . import models as PM
-    if config_class_name(resolve_dir(root, subfolder, revision=revision)) == "AsymmetricAutoencoderKL":
-        return PM.AsymmetricAutoencoderKL.from_pretrained(root, subfolder=subfolder, device=device, torch_dtype=torch_dtype,
-                                                          revision=revision)
+    name = config_class_name(resolve_dir(root, subfolder, revision=revision))
+    if name in ("AsymmetricAutoencoderKL", "AutoencoderTiny"):
+        return getattr(PM, name).from_pretrained(root, subfolder=subfolder, device=device, torch_dtype=torch_dtype,
+                                                 revision=revision)
     return PM.AutoencoderKL.from_pretrained(root, subfolder=subfolder, device=device, revision=revision)
 
 

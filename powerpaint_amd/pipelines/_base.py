@@ -442,10 +442,10 @@ class PipelineBase(PipelinePretrainedMixin):
         if vae is None:
             raise ValueError("no VAE registered: pass the latent-space inputs directly")
         if isinstance(generator, list):
-            lat = torch.cat([vae.encode(image[i:i + 1]).latent_dist.sample(generator=generator[i])
+            lat = torch.cat([retrieve_latents(vae.encode(image[i:i + 1]), generator[i])
                              for i in range(image.shape[0])], dim=0)
         else:
-            lat = vae.encode(image).latent_dist.sample(generator=generator)
+            lat = retrieve_latents(vae.encode(image), generator)
         return vae.config.scaling_factor * lat
 
     def _decode_condition(self, init_image, mask, generator, device, dtype):
@@ -500,3 +500,14 @@ def randn_tensor(shape, generator=None, device=None, dtype=torch.float32):
     if gdev == "cpu" or generator is None and (device is None or torch.device(device).type == "cpu"):
         return torch.randn(shape, generator=generator, dtype=dtype).to(device)
     return torch.randn(shape, generator=generator, device=device, dtype=dtype)
+
+
+def retrieve_latents(encoder_output, generator=None):
+    """diffusers' `retrieve_latents` (sample mode): a posterior (`latent_dist`, AutoencoderKL / AsymmetricAutoencoderKL) is
+    sampled with `generator`; a deterministic encoder's `latents` (AutoencoderTiny) are taken as they are and the generator
+    is not touched."""
+    if hasattr(encoder_output, "latent_dist"):
+        return encoder_output.latent_dist.sample(generator=generator)
+    if hasattr(encoder_output, "latents"):
+        return encoder_output.latents
+    raise AttributeError("vae.encode(...) returned neither `latent_dist` nor `latents`")

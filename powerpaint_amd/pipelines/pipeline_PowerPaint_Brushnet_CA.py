@@ -15,7 +15,7 @@ from .. import _lib as L
 from .. import guidance as GDM
 from .. import ip_adapter as IPA
 from .. import pag as PAGM
-from ._base import PipelineBase, hip_mask_prep, randn_tensor
+from ._base import PipelineBase, hip_mask_prep, randn_tensor, retrieve_latents
 from ._loop import DenoiseLoop
 from .image_processor import VaeImageProcessor
 
@@ -345,7 +345,7 @@ class StableDiffusionPowerPaintBrushNetPipeline(PipelineBase):
                 vs = getattr(self, "vae_scale_factor", 8)
                 latents = randn_tensor((nb, self.unet.config.in_channels, height // vs, width // vs), generator=generator,
                                        device=device, dtype=self._noise_dtype(prompt_embeds))
-            cl = self.vae.encode(img.to(next(iter(self.vae.parameters())).dtype)).latent_dist.sample() * \
+            cl = retrieve_latents(self.vae.encode(img.to(next(iter(self.vae.parameters())).dtype))) * \
                 self.vae.config.scaling_factor                                               # :1338-1341
             hl, wl = cl.shape[-2:]
             ml = hip_mask_prep(2, original_mask, None, (B0, 1, hl, wl), B0, 1, H0, W0, hl, wl)  # nearest  :1342-1344
