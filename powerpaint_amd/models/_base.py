@@ -1,4 +1,4 @@
-"""Shared host-side plumbing of the three model wrappers."""
+"""Shared host-side plumbing of the model wrappers: `_HipModel` (UNet / BrushNet / ControlNet), `_VAEModel` (the three VAEs)."""
 from types import SimpleNamespace
 from typing import Dict
 
@@ -52,6 +52,49 @@ class Output(SimpleNamespace):
 
     def __getitem__(self, i):
         return list(self.__dict__.values())[i]
+
+
+class _VAEModel(PretrainedMixin):
+    """Base of the VAE wrappers.  The constructor of a subclass sets `_device`, `net` (whose `load_state_dict(sd, device)` packs
+    `params`) and `_runtimes`, every plan runtime it owns; the subclass gives `_max_pixels()`.  Not a `_HipModel`: the module
+    boundary is fp32 whatever the network's 16-bit format (inputs of any float dtype are accepted; the network computes in 16
+    bits / fp32 acc), and `to()` accepts everything."""
+    _runtimes = ()
+
+    @property
+    def dtype(self):
+        return torch.float32
+
+    @property
+    def device(self):
+        return self._device
+
+    def parameters(self):
+        yield torch.empty(0, dtype=torch.float32, device=self._device)
+
+    def to(self, *a, **k):
+        return self
+
+    def eval(self):
+        return self
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
+        self.net.load_state_dict(sd, self._device)
+        for rt in self._runtimes:
+            rt.key = None
+        return self
+
+    def param_buffer(self) -> torch.Tensor:
+        return self.net.params.buf
+
+    def _loaded(self):
+        if self.net.params is None:
+            raise L.PPError(f"{type(self).__name__}: load_state_dict first")
+
+    def _chunks(self, n: int, pixels_per_item: int):
+        """[(a, b)] batch slices of at most `_max_pixels()` image pixels each (one item at the least): one plan run per slice."""
+        step = max(1, self._max_pixels() // max(pixels_per_item, 1))
+        return [(i, min(i + step, n)) for i in range(0, n, step)]
 
 
 class _HipModel(PretrainedMixin):

@@ -8,20 +8,19 @@ checkpoints) that the reference's image-conditioned pipelines accept as `vae` an
 The network is `powerpaint_amd.vae_asym.AsymVAENet`; `load_state_dict` takes the checkpoint's key names unchanged.
 """
 from types import SimpleNamespace
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
 from .. import _lib as L
-from ..loaders import PretrainedMixin
 from ..vae_asym import BLOCK_DOWN, BLOCK_UP, AsymVAENet, AsymVAERuntime
 from ._base import Output
-from .autoencoder_kl import DiagonalGaussianDistribution
+from .autoencoder_kl import _KLModel
 
 MAX_BYTES = (1 << 31) - 1      # every tensor of a launch plan stays below 2^31 bytes
 
 
-class AsymmetricAutoencoderKL(PretrainedMixin):
+class AsymmetricAutoencoderKL(_KLModel):
     def __init__(self, in_channels: int = 3, out_channels: int = 3, down_block_types=(BLOCK_DOWN,),
                  down_block_out_channels=(64,), layers_per_down_block: int = 1, up_block_types=(BLOCK_UP,),
                  up_block_out_channels=(64,), layers_per_up_block: int = 1, act_fn: str = "silu", latent_channels: int = 4,
@@ -44,6 +43,7 @@ class AsymmetricAutoencoderKL(PretrainedMixin):
         self._dec = AsymVAERuntime(self.net, self._device, "decode")
         self._dec_cond = AsymVAERuntime(self.net, self._device, "decode_cond")
         self._enc = AsymVAERuntime(self.net, self._device, "encode")
+        self._runtimes = (self._dec, self._dec_cond, self._enc)
         self._scale = 2 ** (len(up_block_out_channels) - 1)             # decoder: image side / latent side
         self._enc_scale = 2 ** (len(down_block_out_channels) - 1)      # encoder (its own block count, as in diffusers)
         # (diffusers registers block_out_channels = up_block_out_channels and force_upcast = False on top of its arguments)
@@ -55,55 +55,9 @@ class AsymmetricAutoencoderKL(PretrainedMixin):
             norm_num_groups=norm_num_groups, sample_size=sample_size, scaling_factor=scaling_factor,
             block_out_channels=tuple(up_block_out_channels), force_upcast=False)
 
-    # the module boundary is fp32 (inputs of any float dtype are accepted; the network computes in 16 bits / fp32 acc)
-    @property
-    def dtype(self):
-        return torch.float32
-
-    @property
-    def device(self):
-        return self._device
-
-    def parameters(self):
-        yield torch.empty(0, dtype=torch.float32, device=self._device)
-
-    def to(self, *a, **k):
-        return self
-
-    def eval(self):
-        return self
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
-        self.net.load_state_dict(sd, self._device)
-        self._dec.key = self._dec_cond.key = self._enc.key = None
-        return self
-
-    def param_buffer(self) -> torch.Tensor:
-        return self.net.params.buf
-
-    def _chunks(self, n: int, pixels_per_item: int):
+    def _max_pixels(self) -> int:
         # the widest full-resolution tensor: layer 1 of the condition encoder, 2 up[0] channels of 2 bytes
-        max_pixels = min(1 << 21, MAX_BYTES // (4 * self.net.up[0]))
-        step = max(1, max_pixels // max(pixels_per_item, 1))
-        return [(i, min(i + step, n)) for i in range(0, n, step)]
-
-    def _loaded(self):
-        if self.net.params is None:
-            raise L.PPError("AsymmetricAutoencoderKL: load_state_dict first")
-
-    # ------------------------------------------------------------------
-    @torch.no_grad()
-    def encode(self, x: torch.Tensor, return_dict: bool = True):
-        self._loaded()
-        B, Cc, H, W = x.shape
-        s = self._enc_scale
-        if Cc != self.config.in_channels or H % s or W % s:
-            raise ValueError(f"encode expects [B, {self.config.in_channels}, {s}k, {s}m] images, got {tuple(x.shape)}")
-        xr = torch.flip(x.to(self._device), dims=(2, 3))            # the encoder runs rotated by 180 degrees (vae.py)
-        parts = [self._enc.run(xr[a:b]) for a, b in self._chunks(B, H * W)]
-        mom = torch.flip(torch.cat(parts, 0), dims=(2, 3))[:, :2 * self.config.latent_channels].contiguous()
-        dist = DiagonalGaussianDistribution(mom)
-        return Output(latent_dist=dist) if return_dict else (dist,)
+        return min(1 << 21, MAX_BYTES // (4 * self.net.up[0]))
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor, generator=None, image: Optional[torch.Tensor] = None,

@@ -6,14 +6,13 @@ ControlNet pipelines): `encode(x).latent_dist.sample(generator)`, `decode(z, ret
 `config.scaling_factor / block_out_channels / latent_channels`.  The network itself is `powerpaint_amd.vae.VAENet`.
 """
 from types import SimpleNamespace
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
 from .. import _lib as L
-from ..loaders import PretrainedMixin
 from ..vae import VAENet, VAERuntime
-from ._base import Output
+from ._base import Output, _VAEModel
 
 MAX_PIXELS = 1 << 21      # image pixels per launch plan (8 x 512^2, 2 x 1024^2): keeps every tensor below 2^31 bytes
 
@@ -41,7 +40,27 @@ class DiagonalGaussianDistribution:
         return self.mean
 
 
-class AutoencoderKL(PretrainedMixin):
+class _KLModel(_VAEModel):
+    """What AutoencoderKL and AsymmetricAutoencoderKL share beyond `_VAEModel`: `encode` to a posterior.  The constructor of
+    a subclass sets `_enc` (the encode runtime) and `_enc_scale` (the multiple an image side must be)."""
+
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor, return_dict: bool = True):
+        self._loaded()
+        B, Cc, H, W = x.shape
+        s = self._enc_scale
+        if Cc != self.config.in_channels or H % s or W % s:
+            raise ValueError(f"encode expects [B, {self.config.in_channels}, {s}k, {s}m] images, got {tuple(x.shape)}")
+        xr = torch.flip(x.to(self._device), dims=(2, 3))            # the encoder runs rotated by 180 degrees (vae.py)
+        parts = [self._enc.run(xr[a:b]) for a, b in self._chunks(B, H * W)]
+        mom = torch.flip(torch.cat(parts, 0), dims=(2, 3))[:, :2 * self.config.latent_channels].contiguous()
+        dist = DiagonalGaussianDistribution(mom)
+        return Output(latent_dist=dist) if return_dict else (dist,)
+
+
+class AutoencoderKL(_KLModel):
+    _enc_scale = 8
+
     def __init__(self, in_channels: int = 3, out_channels: int = 3,
                  down_block_types=("DownEncoderBlock2D",) * 4, up_block_types=("UpDecoderBlock2D",) * 4,
                  block_out_channels=(128, 256, 512, 512), layers_per_block: int = 2, act_fn: str = "silu",
@@ -55,6 +74,7 @@ class AutoencoderKL(PretrainedMixin):
                           norm_num_groups)
         self._dec = VAERuntime(self.net, self._device, "decode")
         self._enc = VAERuntime(self.net, self._device, "encode")
+        self._runtimes = (self._dec, self._enc)
         self.config = SimpleNamespace(
             in_channels=in_channels, out_channels=out_channels, down_block_types=tuple(down_block_types),
             up_block_types=tuple(up_block_types), block_out_channels=tuple(block_out_channels),
@@ -62,54 +82,12 @@ class AutoencoderKL(PretrainedMixin):
             norm_num_groups=norm_num_groups, sample_size=sample_size, scaling_factor=scaling_factor,
             force_upcast=False)
 
-    # the module boundary is fp32 (inputs of any float dtype are accepted; the network computes in bf16 / fp32 acc)
-    @property
-    def dtype(self):
-        return torch.float32
-
-    @property
-    def device(self):
-        return self._device
-
-    def parameters(self):
-        yield torch.empty(0, dtype=torch.float32, device=self._device)
-
-    def to(self, *a, **k):
-        return self
-
-    def eval(self):
-        return self
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
-        self.net.load_state_dict(sd, self._device)
-        self._dec.key = self._enc.key = None
-        return self
-
-    def param_buffer(self) -> torch.Tensor:
-        return self.net.params.buf
-
-    def _chunks(self, n: int, pixels_per_item: int):
-        step = max(1, MAX_PIXELS // max(pixels_per_item, 1))
-        return [(i, min(i + step, n)) for i in range(0, n, step)]
-
-    # ------------------------------------------------------------------
-    @torch.no_grad()
-    def encode(self, x: torch.Tensor, return_dict: bool = True):
-        if self.net.params is None:
-            raise L.PPError("AutoencoderKL: load_state_dict first")
-        B, Cc, H, W = x.shape
-        if Cc != self.config.in_channels or H % 8 or W % 8:
-            raise ValueError(f"encode expects [B, {self.config.in_channels}, 8k, 8m] images, got {tuple(x.shape)}")
-        xr = torch.flip(x.to(self._device), dims=(2, 3))            # the encoder runs rotated by 180 degrees (vae.py)
-        parts = [self._enc.run(xr[a:b]) for a, b in self._chunks(B, H * W)]
-        mom = torch.flip(torch.cat(parts, 0), dims=(2, 3))[:, :2 * self.config.latent_channels].contiguous()
-        dist = DiagonalGaussianDistribution(mom)
-        return Output(latent_dist=dist) if return_dict else (dist,)
+    def _max_pixels(self) -> int:
+        return MAX_PIXELS
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None):
-        if self.net.params is None:
-            raise L.PPError("AutoencoderKL: load_state_dict first")
+        self._loaded()
         B, Cc, h, w = z.shape
         if Cc != self.config.latent_channels:
             raise ValueError(f"decode expects [B, {self.config.latent_channels}, h, w] latents, got {tuple(z.shape)}")

@@ -20,7 +20,8 @@ sizes), and every other layer commutes with the rotation once its 3x3 filters ar
 "upside down" on the stock conv kernel -- rotated input, all encoder filters rotated at pack time, moments rotated
 back -- instead of growing a new padding mode in the hot GEMM loader.  tests/test_vae.py checks the identity on CPU.
 
-Arena zero fill.  The runtimes allocate their arena zero-filled, and ONE buffer relies on it: the pad channels of `x_in`
+Arena zero fill.  The runtimes (`PlanRuntime.ensure`, shared with vae_asym.py and vae_tiny.py, whose plans rely on nothing:
+pp_taesd_pack writes the pad channels) allocate their arena zero-filled, and ONE buffer relies on it: the pad channels of `x_in`
 (channels [latent_channels, 8) of the latents, [in_channels, 8) of the image), which pp_nchw_to_nhwc never writes and
 pp_conv3x3_direct multiplies by the zero-padded rows of its weights.  Everything else a plan reads it has written before:
 the GroupNorm and split-K workspaces, K with its pad rows (S's pad columns, the only values computed from rows the K GEMM
@@ -35,7 +36,7 @@ prefix of the block (`decoder.mask_blend.<i>` with the accumulator pointer as a 
 as an `_Image`); the runtimes keep the list of their build on the real arena as `lay["taps"]`.  No mark / release is taken at
 the top level of a build function, so every tap keeps its bytes until the plan ends.
 """
-from typing import Dict, List, NamedTuple, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -72,41 +73,55 @@ class _Image(NamedTuple):
 
 
 class VAENet:
-    """Architecture + parameters of one AutoencoderKL; `build_decode` / `build_encode` append launch plans."""
+    """Architecture + parameters of one AutoencoderKL: an encoder of widths `down` with `Ld` resnets per block, a decoder of
+    widths `up` with `Lu` + 1, stored as `dtype`; `build_decode` / `build_encode` append launch plans.  AutoencoderKL itself is
+    the symmetric bf16 case; vae_asym.AsymVAENet sets the two sides apart and adds the mask-conditioned decode."""
+    NAME = "AutoencoderKL"
 
     def __init__(self, in_channels: int = 3, out_channels: int = 3, latent_channels: int = 4,
                  block_out_channels=(128, 256, 512, 512), layers_per_block: int = 2, norm_num_groups: int = 32):
-        self.cin, self.cout, self.lat = in_channels, out_channels, latent_channels
-        self.boc = tuple(block_out_channels)
-        self.L = layers_per_block
-        self.groups = norm_num_groups
-        if in_channels > 8 or out_channels > 4 or 2 * latent_channels > 8:
-            raise L.PPError("AutoencoderKL: in_channels <= 8, out_channels <= 4, latent_channels <= 4 supported")
-        if any(c % 64 or c % norm_num_groups for c in self.boc):
+        self._setup(in_channels, out_channels, latent_channels, block_out_channels, layers_per_block, block_out_channels,
+                    layers_per_block, norm_num_groups, torch.bfloat16)
+        if any(c % 64 or c % norm_num_groups for c in self.up):
             raise L.PPError("AutoencoderKL: block_out_channels must be multiples of 64 (MFMA K steps) and of the groups")
+
+    def _setup(self, in_channels, out_channels, latent_channels, down, layers_down, up, layers_up, groups, dtype):
+        """The fields of either constructor, and the one check they share (the 8 / 4-channel ends)."""
+        self.cin, self.cout, self.lat = in_channels, out_channels, latent_channels
+        self.down, self.Ld = tuple(down), layers_down
+        self.up, self.Lu = tuple(up), layers_up
+        self.groups = groups
+        self.dtype = dtype
+        L.dtype_code(dtype)
+        if in_channels > 8 or out_channels > 4 or 2 * latent_channels > 8:
+            raise L.PPError(f"{self.NAME}: in_channels <= 8, out_channels <= 4, latent_channels <= 4 supported")
         self.params: Optional[ParamPack] = None
         self.P: Dict[str, int] = {}
 
     # ---------------------------------------------------------------- structure
     def _resnets(self) -> List[Tuple[str, int, int]]:
         """(prefix, cin, cout) of every ResnetBlock2D, encoder then decoder, in diffusers order."""
-        out, boc = [], self.boc
-        for i, c in enumerate(boc):
-            for j in range(self.L):
-                out.append((f"encoder.down_blocks.{i}.resnets.{j}", boc[max(i - 1, 0)] if j == 0 else c, c))
-        out += [(f"encoder.mid_block.resnets.{j}", boc[-1], boc[-1]) for j in range(2)]
-        rev = list(reversed(boc))
+        out, d = [], self.down
+        for i, c in enumerate(d):
+            for j in range(self.Ld):
+                out.append((f"encoder.down_blocks.{i}.resnets.{j}", d[max(i - 1, 0)] if j == 0 else c, c))
+        out += [(f"encoder.mid_block.resnets.{j}", d[-1], d[-1]) for j in range(2)]
+        rev = list(reversed(self.up))
         out += [(f"decoder.mid_block.resnets.{j}", rev[0], rev[0]) for j in range(2)]
         for i, c in enumerate(rev):
-            for j in range(self.L + 1):
+            for j in range(self.Lu + 1):
                 out.append((f"decoder.up_blocks.{i}.resnets.{j}", rev[max(i - 1, 0)] if j == 0 else c, c))
         return out
 
     def _samplers(self) -> List[Tuple[str, int]]:
-        n = len(self.boc)
-        rev = list(reversed(self.boc))
-        return [(f"encoder.down_blocks.{i}.downsamplers.0.conv", self.boc[i]) for i in range(n - 1)] + \
-               [(f"decoder.up_blocks.{i}.upsamplers.0.conv", rev[i]) for i in range(n - 1)]
+        rev = list(reversed(self.up))
+        return [(f"encoder.down_blocks.{i}.downsamplers.0.conv", self.down[i]) for i in range(len(self.down) - 1)] + \
+               [(f"decoder.up_blocks.{i}.upsamplers.0.conv", rev[i]) for i in range(len(rev) - 1)]
+
+    def _extra_convs(self) -> List[Tuple[str, Tuple[int, ...], Callable]]:
+        """(name, weight shape, fp32 weight -> packed matrix) of the convs a subclass adds to the state dict.  They sit in the
+        spec and in the pack behind the attentions and in front of the narrow ends (the pack order fixes every offset)."""
+        return []
 
     def state_dict_spec(self) -> Dict[str, Tuple[int, ...]]:
         sp: Dict[str, Tuple[int, ...]] = {}
@@ -117,8 +132,8 @@ class VAENet:
         def vec(name, c):
             sp[name + ".weight"], sp[name + ".bias"] = (c,), (c,)
 
-        conv("encoder.conv_in", self.boc[0], self.cin, 3)
-        conv("decoder.conv_in", self.boc[-1], self.lat, 3)
+        conv("encoder.conv_in", self.down[0], self.cin, 3)
+        conv("decoder.conv_in", self.up[-1], self.lat, 3)
         for pre, cin, cout in self._resnets():
             vec(pre + ".norm1", cin)
             conv(pre + ".conv1", cout, cin, 3)
@@ -128,15 +143,17 @@ class VAENet:
                 conv(pre + ".conv_shortcut", cout, cin, 1)
         for pre, c in self._samplers():
             conv(pre, c, c, 3)
-        for side in ("encoder", "decoder"):
-            a, c = f"{side}.mid_block.attentions.0", self.boc[-1]
+        for side, c in (("encoder", self.down[-1]), ("decoder", self.up[-1])):
+            a = f"{side}.mid_block.attentions.0"
             vec(a + ".group_norm", c)
             for n in ("to_q", "to_k", "to_v", "to_out.0"):
                 sp[f"{a}.{n}.weight"], sp[f"{a}.{n}.bias"] = (c, c), (c,)
-        vec("encoder.conv_norm_out", self.boc[-1])
-        conv("encoder.conv_out", 2 * self.lat, self.boc[-1], 3)
-        vec("decoder.conv_norm_out", self.boc[0])
-        conv("decoder.conv_out", self.cout, self.boc[0], 3)
+        for name, shape, _ in self._extra_convs():
+            sp[name + ".weight"], sp[name + ".bias"] = shape, shape[:1]
+        vec("encoder.conv_norm_out", self.down[-1])
+        conv("encoder.conv_out", 2 * self.lat, self.down[-1], 3)
+        vec("decoder.conv_norm_out", self.up[0])
+        conv("decoder.conv_out", self.cout, self.up[0], 3)
         conv("quant_conv", 2 * self.lat, 2 * self.lat, 1)
         conv("post_quant_conv", self.lat, self.lat, 1)
         return sp
@@ -166,9 +183,9 @@ class VAENet:
                     sd[k.replace(f".{old}.", f".{new}.")] = sd.pop(k)
         missing = [k for k in self.state_dict_spec() if k not in sd]
         if missing:
-            raise L.PPError(f"AutoencoderKL state dict misses {len(missing)} keys, e.g. {missing[:3]}")
+            raise L.PPError(f"{self.NAME} state dict misses {len(missing)} keys, e.g. {missing[:3]}")
         pk = ParamPack()
-        bf, f32 = torch.bfloat16, torch.float32
+        h16, f32 = self.dtype, torch.float32
 
         def W(k):
             return sd[k].float()
@@ -181,42 +198,48 @@ class VAENet:
             full[:, :, 1, 1] = w[:, :, 0, 0]
             return direct(full, n, n)
 
+        def vec(k):
+            pk.add(k, W(k), f32)
+
         for pre, cin, cout in self._resnets():
-            rot = _rot if pre.startswith("encoder") else (lambda t: t)
+            rot = _rot if pre.startswith("encoder") else (lambda t: t)      # the encoder runs rotated (module docstring)
             for nrm in ("norm1", "norm2"):
-                pk.add(f"{pre}.{nrm}.weight", W(f"{pre}.{nrm}.weight"), f32)
-                pk.add(f"{pre}.{nrm}.bias", W(f"{pre}.{nrm}.bias"), f32)
+                vec(f"{pre}.{nrm}.weight")
+                vec(f"{pre}.{nrm}.bias")
             for cv in ("conv1", "conv2"):
-                pk.add(f"{pre}.{cv}.weight", _conv_igemm(rot(W(f"{pre}.{cv}.weight"))), bf)
-                pk.add(f"{pre}.{cv}.bias", W(f"{pre}.{cv}.bias"), f32)
+                pk.add(f"{pre}.{cv}.weight", _conv_igemm(rot(W(f"{pre}.{cv}.weight"))), h16)
+                vec(f"{pre}.{cv}.bias")
             if cin != cout:
-                pk.add(f"{pre}.conv_shortcut.weight", W(f"{pre}.conv_shortcut.weight").reshape(cout, cin), bf)
-                pk.add(f"{pre}.conv_shortcut.bias", W(f"{pre}.conv_shortcut.bias"), f32)
+                pk.add(f"{pre}.conv_shortcut.weight", W(f"{pre}.conv_shortcut.weight").reshape(cout, cin), h16)
+                vec(f"{pre}.conv_shortcut.bias")
         for pre, c in self._samplers():
             rot = _rot if pre.startswith("encoder") else (lambda t: t)
-            pk.add(pre + ".weight", _conv_igemm(rot(W(pre + ".weight"))), bf)
-            pk.add(pre + ".bias", W(pre + ".bias"), f32)
-        for side in ("encoder", "decoder"):
-            a, c = f"{side}.mid_block.attentions.0", self.boc[-1]
-            pk.add(a + ".group_norm.weight", W(a + ".group_norm.weight"), f32)
-            pk.add(a + ".group_norm.bias", W(a + ".group_norm.bias"), f32)
+            pk.add(pre + ".weight", _conv_igemm(rot(W(pre + ".weight"))), h16)
+            vec(pre + ".bias")
+        for side, c in (("encoder", self.down[-1]), ("decoder", self.up[-1])):
+            a = f"{side}.mid_block.attentions.0"
+            vec(a + ".group_norm.weight")
+            vec(a + ".group_norm.bias")
             for n in ("to_q", "to_k", "to_v", "to_out.0"):
-                pk.add(f"{a}.{n}.weight", W(f"{a}.{n}.weight").reshape(c, c), bf)
-                pk.add(f"{a}.{n}.bias", W(f"{a}.{n}.bias"), f32)
-            pk.add(f"{side}.conv_norm_out.weight", W(f"{side}.conv_norm_out.weight"), f32)
-            pk.add(f"{side}.conv_norm_out.bias", W(f"{side}.conv_norm_out.bias"), f32)
+                pk.add(f"{a}.{n}.weight", W(f"{a}.{n}.weight").reshape(c, c), h16)
+                vec(f"{a}.{n}.bias")
+            vec(f"{side}.conv_norm_out.weight")
+            vec(f"{side}.conv_norm_out.bias")
+        for name, _, pack in self._extra_convs():
+            pk.add(name + ".weight", pack(W(name + ".weight")), h16)
+            vec(name + ".bias")
         # the narrow ends, channel-padded
-        pk.add("encoder.conv_in.weight", direct(_rot(W("encoder.conv_in.weight")), 8, self.boc[0]), bf)
-        pk.add("encoder.conv_in.bias", W("encoder.conv_in.bias"), f32)
-        pk.add("encoder.conv_out.weight", direct(_rot(W("encoder.conv_out.weight")), self.boc[-1], 8), bf)
+        pk.add("encoder.conv_in.weight", direct(_rot(W("encoder.conv_in.weight")), 8, self.down[0]), h16)
+        vec("encoder.conv_in.bias")
+        pk.add("encoder.conv_out.weight", direct(_rot(W("encoder.conv_out.weight")), self.down[-1], 8), h16)
         pk.add("encoder.conv_out.bias", _pad_to(W("encoder.conv_out.bias"), 0, 8), f32)
-        pk.add("quant_conv.weight", centre(W("quant_conv.weight"), 8), bf)
+        pk.add("quant_conv.weight", centre(W("quant_conv.weight"), 8), h16)
         pk.add("quant_conv.bias", _pad_to(W("quant_conv.bias"), 0, 8), f32)
-        pk.add("post_quant_conv.weight", centre(W("post_quant_conv.weight"), 8), bf)
+        pk.add("post_quant_conv.weight", centre(W("post_quant_conv.weight"), 8), h16)
         pk.add("post_quant_conv.bias", _pad_to(W("post_quant_conv.bias"), 0, 8), f32)
-        pk.add("decoder.conv_in.weight", direct(W("decoder.conv_in.weight"), 8, self.boc[-1]), bf)
-        pk.add("decoder.conv_in.bias", W("decoder.conv_in.bias"), f32)
-        pk.add("decoder.conv_out.weight", _conv_igemm(_pad_to(W("decoder.conv_out.weight"), 0, 4)), bf)
+        pk.add("decoder.conv_in.weight", direct(W("decoder.conv_in.weight"), 8, self.up[-1]), h16)
+        vec("decoder.conv_in.bias")
+        pk.add("decoder.conv_out.weight", _conv_igemm(_pad_to(W("decoder.conv_out.weight"), 0, 4)), h16)
         pk.add("decoder.conv_out.bias", _pad_to(W("decoder.conv_out.bias"), 0, 4), f32)
         pk.to_device(device)
         self.params, self.P = pk, pk.ptr
@@ -230,13 +253,20 @@ class VAENet:
         pb.taps.append((name, out))
         return out
 
-    def _resnet(self, pb: Builder, pre: str, x: Act, cout: int) -> Act:
+    def _norm(self, pb: Builder, x: Act, name: str, silu: bool, acc: Optional[int] = None) -> Act:
+        """GroupNorm(+SiLU) `name` of x.  acc: an accumulator that already holds x's statistics; only the plans of vae_asym.py,
+        which overrides this, have one."""
+        assert acc is None
+        return pb.groupnorm(x, self.P[name + ".weight"], self.P[name + ".bias"], EPS, silu, groups=self.groups)
+
+    def _resnet(self, pb: Builder, pre: str, x: Act, cout: int, acc: Optional[int] = None) -> Act:
+        """acc: norm1 takes its statistics from there (`_norm`)."""
         P = self.P
         out = pb.new_act(x.B, x.H, x.W, cout)
         m = pb.mark()
-        h = pb.groupnorm(x, P[f"{pre}.norm1.weight"], P[f"{pre}.norm1.bias"], EPS, True, groups=self.groups)
+        h = self._norm(pb, x, f"{pre}.norm1", True, acc)
         h = pb.conv3x3(h, P[f"{pre}.conv1.weight"], cout, P[f"{pre}.conv1.bias"])
-        h = pb.groupnorm(h, P[f"{pre}.norm2.weight"], P[f"{pre}.norm2.bias"], EPS, True, groups=self.groups)
+        h = self._norm(pb, h, f"{pre}.norm2", True)
         if x.C != cout:
             sc = pb.linear(x.ptr, x.rows, x.C, P[f"{pre}.conv_shortcut.weight"], cout, P[f"{pre}.conv_shortcut.bias"],
                            name="conv1x1")
@@ -258,8 +288,7 @@ class VAENet:
         npad = _align(n, 64)
         out = pb.new_act(B, x.H, x.W, Cc)
         m = pb.mark()
-        h = pb.groupnorm(x, P[f"{pre}.group_norm.weight"], P[f"{pre}.group_norm.bias"], EPS, False,
-                         groups=self.groups)
+        h = self._norm(pb, x, f"{pre}.group_norm", False)
         q = pb.linear(h.ptr, x.rows, Cc, P[f"{pre}.to_q.weight"], Cc, P[f"{pre}.to_q.bias"], name="linear")
         k = pb.linear(h.ptr, x.rows, Cc, P[f"{pre}.to_k.weight"], Cc, P[f"{pre}.to_k.bias"],
                       out=pb.alloc((x.rows + npad - n) * Cc * 2), name="linear")
@@ -286,22 +315,24 @@ class VAENet:
         return self._resnet(pb, f"{side}.mid_block.resnets.1", x, x.C)
 
     # ---------------------------------------------------------------- plans
-    def build_decode(self, pb: Builder, z: Act, out_nchw: int):
-        """z: latents padded to 8 channels [B,h,w,8] -> fp32 NCHW image [B,4,8h,8w] at `out_nchw` (channel 3 is 0)."""
+    def build_decode(self, pb: Builder, z: Act, out_nchw: int, stats: Optional[Callable[[Act, int], int]] = None):
+        """z: latents padded to 8 channels [B,h,w,8] -> fp32 NCHW image [B,4,8h,8w] at `out_nchw` (channel 3 is 0).
+        stats(x, i): called on the sample in front of up block i, and behind the last one; returns the accumulator its first
+        norm takes the statistics from (vae_asym.py: the blends).  Without it every norm launches its own."""
         P = self.P
         x = self._direct(pb, z, "post_quant_conv", 8)
-        x = self._direct(pb, x, "decoder.conv_in", self.boc[-1])
+        x = self._direct(pb, x, "decoder.conv_in", self.up[-1])
         x = self._mid(pb, "decoder", x)
-        rev = list(reversed(self.boc))
+        rev = list(reversed(self.up))
         for i, c in enumerate(rev):
-            for j in range(self.L + 1):
-                x = self._resnet(pb, f"decoder.up_blocks.{i}.resnets.{j}", x, c)
+            acc = stats(x, i) if stats else None
+            for j in range(self.Lu + 1):
+                x = self._resnet(pb, f"decoder.up_blocks.{i}.resnets.{j}", x, c, acc if j == 0 else None)
             if i != len(rev) - 1:
                 pre = f"decoder.up_blocks.{i}.upsamplers.0.conv"
                 x = pb.conv3x3(x, P[pre + ".weight"], c, P[pre + ".bias"], up=True)
                 pb.taps.append((pre, x))
-        x = pb.groupnorm(x, P["decoder.conv_norm_out.weight"], P["decoder.conv_norm_out.bias"], EPS, True,
-                         groups=self.groups)
+        x = self._norm(pb, x, "decoder.conv_norm_out", True, stats(x, len(rev)) if stats else None)
         pb.taps.append(("decoder.conv_norm_out", x))
         pb.plan.add("conv_out", pb.lib.pp_conv3x3_smallcout, x.ptr, x.B, x.H, x.W, x.C, P["decoder.conv_out.weight"],
                     P["decoder.conv_out.bias"], 4, out_nchw, pb.dt)
@@ -310,44 +341,35 @@ class VAENet:
 
     def build_encode(self, pb: Builder, img: Act) -> Act:
         """img: the 180-degree-rotated image padded to 8 channels [B,H,W,8] -> rotated moments [B,H/8,W/8,8]."""
-        P = self.P
-        x = self._direct(pb, img, "encoder.conv_in", self.boc[0])
-        for i, c in enumerate(self.boc):
-            for j in range(self.L):
+        P, d = self.P, self.down
+        x = self._direct(pb, img, "encoder.conv_in", d[0])
+        for i, c in enumerate(d):
+            for j in range(self.Ld):
                 x = self._resnet(pb, f"encoder.down_blocks.{i}.resnets.{j}", x, c)
-            if i != len(self.boc) - 1:
+            if i != len(d) - 1:
                 if x.H % 2 or x.W % 2:
-                    raise L.PPError("AutoencoderKL.encode: image sides must be multiples of 8")
+                    raise L.PPError(f"{self.NAME}.encode: image sides must be multiples of 2^(down blocks - 1)")
                 pre = f"encoder.down_blocks.{i}.downsamplers.0.conv"
                 x = pb.conv3x3(x, P[pre + ".weight"], c, P[pre + ".bias"], stride=2)
                 pb.taps.append((pre, x))
         x = self._mid(pb, "encoder", x)
-        x = pb.groupnorm(x, P["encoder.conv_norm_out.weight"], P["encoder.conv_norm_out.bias"], EPS, True,
-                         groups=self.groups)
+        x = self._norm(pb, x, "encoder.conv_norm_out", True)
         pb.taps.append(("encoder.conv_norm_out", x))
         x = self._direct(pb, x, "encoder.conv_out", 8)
         return self._direct(pb, x, "quant_conv", 8)
 
 
-class VAERuntime:
-    """Device state (arena + launch plan) of one direction of one VAENet for one input shape."""
+class PlanRuntime:
+    """Device state (arena + launch plan) of one direction of one VAE network for one input shape (B, H, W).  A subclass gives
+    `_build(arena, B, H, W) -> (lay, plan)`: `lay` names the buffers it allocated, "taps" among them."""
 
-    def __init__(self, net: VAENet, device, direction: str):
+    def __init__(self, net, device, direction: str):
         self.net, self.device, self.direction = net, torch.device(device), direction
         self.key = None
         self.plan: Optional[Plan] = None
         self.arena: Optional[Arena] = None
-
-    def _build(self, arena: Arena, B: int, H: int, W: int):
-        pb = Builder(arena)
-        lay = {"x_in": Act(arena.alloc(B * H * W * 8 * 2), B, H, W, 8)}
-        if self.direction == "decode":
-            lay["img"] = arena.alloc(B * 4 * (8 * H) * (8 * W) * 4)
-            lay["shape"] = self.net.build_decode(pb, lay["x_in"], lay["img"])
-        else:
-            lay["moments"] = self.net.build_encode(pb, lay["x_in"])
-        lay["taps"] = pb.taps
-        return lay, pb.plan
+        self.lay: Optional[dict] = None
+        self.builds = 0                  # plans built so far (new values in buffers of a known shape build nothing)
 
     def ensure(self, B: int, H: int, W: int):
         if (B, H, W) == self.key:
@@ -357,6 +379,25 @@ class VAERuntime:
         self.arena = Arena(_align(dry.peak, 4096), self.device)      # zero-filled: the pad channels of x_in stay 0
         self.lay, self.plan = self._build(self.arena, B, H, W)
         self.key = (B, H, W)
+        self.builds += 1
+
+
+class VAERuntime(PlanRuntime):
+    """One direction, "decode" or "encode", of one VAENet."""
+
+    def _build(self, arena: Arena, B: int, H: int, W: int):
+        pb = Builder(arena, dtype=self.net.dtype)
+        lay = {"x_in": Act(arena.alloc(B * H * W * 8 * 2), B, H, W, 8)}
+        if self.direction == "encode":
+            lay["moments"] = self.net.build_encode(pb, lay["x_in"])
+        else:
+            lay["img"] = arena.alloc(B * 4 * (8 * H) * (8 * W) * 4)
+            lay["shape"] = self._build_decode(pb, lay, B, H, W)
+        lay["taps"] = pb.taps
+        return lay, pb.plan
+
+    def _build_decode(self, pb: Builder, lay: dict, B: int, H: int, W: int):
+        return self.net.build_decode(pb, lay["x_in"], lay["img"])
 
     def run(self, x: torch.Tensor) -> torch.Tensor:
         """decode: latents [B,lat,h,w] -> fp32 [B,4,8h,8w] (a view of arena memory, valid until the next run);
@@ -369,14 +410,13 @@ class VAERuntime:
             x = x.float()
         x = x.contiguous()
         dt = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[x.dtype]
+        code = L.dtype_code(self.net.dtype)
         xin = self.lay["x_in"]
-        L.check(L.lib().pp_nchw_to_nhwc(x.data_ptr(), dt, B, Cc, H * W, 0, xin.ptr, 8, 0, L.PP_DT_BF16, stream),
-                "pp_nchw_to_nhwc")
+        L.check(L.lib().pp_nchw_to_nhwc(x.data_ptr(), dt, B, Cc, H * W, 0, xin.ptr, 8, 0, code, stream), "pp_nchw_to_nhwc")
         self.plan.run(stream)
-        if self.direction == "decode":
+        if self.direction != "encode":
             return self.arena.view(self.lay["img"], self.lay["shape"], torch.float32)
         m = self.lay["moments"]
         out = torch.empty(m.B, 8, m.H, m.W, dtype=torch.float32, device=self.device)
-        L.check(L.lib().pp_nhwc_to_nchw(m.ptr, m.B, 8, m.H * m.W, out.data_ptr(), 0, L.PP_DT_BF16, stream),
-                "pp_nhwc_to_nchw")
+        L.check(L.lib().pp_nhwc_to_nchw(m.ptr, m.B, 8, m.H * m.W, out.data_ptr(), 0, code, stream), "pp_nhwc_to_nchw")
         return out

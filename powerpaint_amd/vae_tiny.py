@@ -27,8 +27,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib as L
-from .engine import Act, Arena, Builder, ParamPack, Plan, _align, _conv_direct, _conv_igemm
-from .vae import _Image, _pad_to
+from .engine import Act, Arena, Builder, ParamPack, _conv_direct, _conv_igemm
+from .vae import PlanRuntime, _Image, _pad_to
 
 WIDTH = 64      # the only channel count pp_conv3x3_c64 is built for
 
@@ -207,14 +207,8 @@ class TinyVAENet:
         return H, W
 
 
-class TinyVAERuntime:
-    """Device state (arena + launch plan) of one direction of one TinyVAENet for one input shape."""
-
-    def __init__(self, net: TinyVAENet, device, direction: str):
-        self.net, self.device, self.direction = net, torch.device(device), direction
-        self.key = None
-        self.plan: Optional[Plan] = None
-        self.arena: Optional[Arena] = None
+class TinyVAERuntime(PlanRuntime):
+    """One direction, "decode" or "encode", of one TinyVAENet."""
 
     def _build(self, arena: Arena, B: int, H: int, W: int):
         net = self.net
@@ -226,15 +220,6 @@ class TinyVAERuntime:
         lay["shape"] = build(pb, lay["src"], B, H, W, lay["out"])
         lay["taps"] = pb.taps
         return lay, pb.plan
-
-    def ensure(self, B: int, H: int, W: int):
-        if (B, H, W) == self.key:
-            return
-        dry = Arena()
-        self._build(dry, B, H, W)
-        self.arena = Arena(_align(dry.peak, 4096), self.device)
-        self.lay, self.plan = self._build(self.arena, B, H, W)
-        self.key = (B, H, W)
 
     def run(self, x: torch.Tensor) -> torch.Tensor:
         """decode: latents [B,lat,h,w] -> fp32 [B,4,s h,s w]; encode: image [B,cin,H,W] -> fp32 latents [B,4,h,w].  Both are

@@ -136,6 +136,47 @@ def test_taps_name_every_block_and_keep_their_bytes():
     assert VC.tap_layout_violations([("x", fake)], log + [(log[0][0] + 8, 16)]) == [("x", f"allocation {len(log)} overlaps")]
 
 
+def test_runtimes_share_ensure_and_wrappers_reset_them():
+    """The three plan runtimes build once per shape (`builds`, `key`, the same `plan` object), and `load_state_dict` of each
+    wrapper resets `key` on every runtime it owns: plans hold parameter pointers, so new parameters mean new plans."""
+    import asym_vae_cases as AC
+    import taesd_cases as TC
+    from powerpaint_amd import models as PM
+    kl = PM.AutoencoderKL(device="cpu", **SMALL)
+    a = AC.TINY
+    asym = PM.AsymmetricAutoencoderKL(
+        down_block_types=("DownEncoderBlock2D",) * len(a["down"]), down_block_out_channels=a["down"],
+        layers_per_down_block=a["layers_down"], up_block_types=("UpDecoderBlock2D",) * len(a["up"]),
+        up_block_out_channels=a["up"], layers_per_up_block=a["layers_up"], device="cpu")
+    t = TC.SMALL
+    tiny = PM.AutoencoderTiny(device="cpu", num_encoder_blocks=t["enc_blocks"], num_decoder_blocks=t["dec_blocks"],
+                              encoder_block_out_channels=(64,) * len(t["enc_blocks"]),
+                              decoder_block_out_channels=(64,) * len(t["dec_blocks"]))
+    owned = {kl: {kl._dec, kl._enc}, asym: {asym._dec, asym._dec_cond, asym._enc}, tiny: {tiny._dec, tiny._enc}}
+    for vae, rts in owned.items():
+        assert set(vae._runtimes) == rts and len({type(rt) for rt in rts}) == 1
+        vae.load_state_dict(vae.net.synthetic_state_dict(seed=5))
+        rt = vae._dec
+        assert (rt.key, rt.plan, rt.builds) == (None, None, 0)
+        rt.ensure(2, 4, 6)
+        plan = rt.plan
+        assert rt.key == (2, 4, 6) and rt.builds == 1 and plan is not None and "taps" in rt.lay
+        rt.ensure(2, 4, 6)
+        assert rt.plan is plan and rt.builds == 1
+        rt.ensure(1, 4, 6)
+        assert rt.key == (1, 4, 6) and rt.builds == 2 and rt.plan is not plan
+        for other in rts:
+            other.key = (9, 9, 9)
+        vae.load_state_dict(vae.net.synthetic_state_dict(seed=6))
+        assert all(other.key is None for other in rts)
+        rt.ensure(1, 4, 6)                                                  # the same shape, new parameters: built again
+        assert rt.builds == 3 and rt.key == (1, 4, 6)
+    from powerpaint_amd.vae import VAERuntime
+    from powerpaint_amd.vae_asym import AsymVAERuntime
+    from powerpaint_amd.vae_tiny import TinyVAERuntime
+    assert [type(v._dec) for v in owned] == [VAERuntime, AsymVAERuntime, TinyVAERuntime]
+
+
 def test_distribution_matches_oracle():
     from powerpaint_amd.models.autoencoder_kl import DiagonalGaussianDistribution
     p = torch.randn(2, 8, 4, 4) * 20

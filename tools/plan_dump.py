@@ -4,7 +4,10 @@ field of each PPGemmArgs and every scalar argument of the other launches, pointe
 packed weights (W+), and per plan the FLOP accounting (flops, flops_skipped, flops_by_kind) and the arena's peak.
 In full text: both UNets (the 4-channel one behind a BrushNet), BrushNet and ControlNet, setup and step plans, twin prefix
 asked for and not, at 64x64 latents batch 8 and 16x16 batch 2; the full UNet at batch 2 at 32x32, 16x8 (twin), 8x8, 29x32 and
-13x10, and in fp16 at 64x64; the VAE plans.  As one sha256 line per case: the full UNet at batch 2 with every one and every
+13x10, and in fp16 at 64x64; the plans of the three VAE runtimes (VAENet; AsymVAENet at the x-1-5 widths in bf16 and fp16 and at
+the small widths of the tests; TinyVAENet at both block counts of the tests in bf16 and fp16), each as the runtime's own `_build`
+compiles it on a dry arena, with the tap names in plan order, and per VAE network a sha256 of the packed parameter bytes and one
+of its (name, offset) table.  As one sha256 line per case: the full UNet at batch 2 with every one and every
 pair of the transformer switches taken off on the instance, at 64x64, 32x32, 29x32 and 13x10, twin asked for and not, and with
 the wide cross-attention block let up to C = 1280.  Two trees whose dumps are equal byte for byte compile the same plans
 (TREE: the checkout to import from, default this one): how a change to the plan compiler shows that it leaves them alone."""
@@ -20,8 +23,13 @@ import torch
 from powerpaint_amd import _lib as L
 from powerpaint_amd.engine import SDNet
 from powerpaint_amd.runtime import NetRuntime
-from powerpaint_amd.vae import VAENet
-from powerpaint_amd.engine import Arena, Builder, Act
+from powerpaint_amd.vae import VAENet, VAERuntime
+from powerpaint_amd.vae_asym import AsymVAENet, AsymVAERuntime
+from powerpaint_amd.vae_tiny import TinyVAENet, TinyVAERuntime
+from powerpaint_amd.engine import Arena
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))      # the case files (data only)
+import asym_vae_cases as AV
+import taesd_cases as TC
 
 SWITCHES = ("fold_ln", "merge_ff2_proj_out", "fuse_xattn", "fuse_tfront", "fuse_xattn_pre", "fuse_ff", "ff_w8", "attn_log2",
             "fuse_xattn_wide", "fuse_xattn_2g")
@@ -90,17 +98,49 @@ full += [("unet", 9, dict(dtype=torch.float16), 2, 64, 64, False)]
 for case in full:
     lines += compiled(*case)
     n_full += 2
-# VAE
-net = VAENet(); net.load_state_dict(net.synthetic_state_dict(seed=1), "cpu")
-for hw in (64, 16):
-    dry = Arena(); pb = Builder(dry)
-    net.build_decode(pb, Act(dry.alloc(hw * hw * 16), 1, hw, hw, 8), dry.alloc(4 * 64 * hw * hw * 4))
-    RANGES[:] = [("A", dry.base, dry.base + (1 << 40)), ("W", net.params.buf.data_ptr(), net.params.buf.data_ptr() + net.params.buf.numel() + 4096)]
-    lines.append(f"## vae decode {hw}"); lines += desc(pb.plan); lines.append(f"# {totals(pb.plan)} peak={dry.peak}")
-    dry = Arena(); pb = Builder(dry)
-    net.build_encode(pb, Act(dry.alloc(64 * hw * hw * 16), 1, 8 * hw, 8 * hw, 8))
-    lines.append(f"## vae encode {hw}"); lines += desc(pb.plan); lines.append(f"# {totals(pb.plan)} peak={dry.peak}")
-    n_full += 2
+# VAE: every runtime's own _build on a dry arena, and per network the packed bytes and the offset table as digests
+def vae_net(tag, net):
+    net.load_state_dict(net.synthetic_state_dict(seed=1), "cpu")
+    buf = net.params.buf
+    table = repr(sorted((k, p - buf.data_ptr()) for k, p in net.P.items()))
+    lines.append(f"## {tag}")
+    lines.append(f"sha256 {hashlib.sha256(buf.numpy().tobytes()).hexdigest()} {tag} params.buf, {buf.numel()} bytes")
+    lines.append(f"sha256 {hashlib.sha256(table.encode()).hexdigest()} {tag} offsets of {len(net.P)} entries")
+    return net
+
+def vae_plan(tag, rt_cls, net, direction, B, H, W):
+    global n_full
+    dry = Arena()
+    lay, plan = rt_cls(net, "cpu", direction)._build(dry, B, H, W)
+    buf = net.params.buf
+    RANGES[:] = [("A", dry.base, dry.base + (1 << 40)), ("W", buf.data_ptr(), buf.data_ptr() + buf.numel() + 4096)]
+    lines.append(f"## {tag} {direction} B={B} {H}x{W}: {len(plan.calls)} launches, taps {' '.join(t[0] for t in lay['taps'])}")
+    lines.extend(desc(plan))
+    lines.append(f"# {totals(plan)} peak={dry.peak}")
+    n_full += 1
+
+n_nets = 0
+net = vae_net("vae", VAENet()); n_nets += 1
+for h, w in ((16, 16), (13, 10)):
+    vae_plan("vae", VAERuntime, net, "decode", 2, h, w)
+    vae_plan("vae", VAERuntime, net, "encode", 2, 8 * h, 8 * w)
+# TINY's encoder has two levels, the runtime's moments are sized for four (the factor 8): only its decode directions
+for name, cfg, dtype, dirs in (("X15", AV.X15, torch.bfloat16, ("encode", "decode", "decode_cond")),
+                               ("X15", AV.X15, torch.float16, ("encode", "decode", "decode_cond")),
+                               ("TINY", AV.TINY, torch.bfloat16, ("decode", "decode_cond"))):
+    tag = f"asym {name} {dtype}"
+    net = vae_net(tag, AsymVAENet(cfg["in_channels"], cfg["out_channels"], cfg["latent_channels"], cfg["down"], cfg["layers_down"],
+                                  cfg["up"], cfg["layers_up"], cfg["groups"], dtype=dtype)); n_nets += 1
+    for h, w in ((8, 8), (5, 7)):
+        for d in dirs:
+            vae_plan(tag, AsymVAERuntime, net, d, 2, *((8 * h, 8 * w) if d == "encode" else (h, w)))
+for name, cfg in (("default", TC.DEFAULT), ("SMALL", TC.SMALL)):
+    for dtype in (torch.bfloat16, torch.float16):
+        tag = f"taesd {name} {dtype}"
+        net = vae_net(tag, TinyVAENet(cfg["in_channels"], cfg["out_channels"], cfg["latent_channels"], cfg["enc_blocks"],
+                                      cfg["dec_blocks"], dtype=dtype)); n_nets += 1
+        vae_plan(tag, TinyVAERuntime, net, "decode", 2, *TC.DECODE_SHAPES[0])
+        vae_plan(tag, TinyVAERuntime, net, "encode", 2, *TC.ENCODE_SHAPES[0])
 # switched-off plans, one digest line each
 n_digest = 0
 def digest(tag, *a, **kw):
@@ -116,4 +156,5 @@ for (H, W) in ((64, 64), (32, 32), (29, 32), (13, 10)):
 for hw in (64, 32, 16):
     digest(f"{hw}x{hw} twin=False xattn_wide_max_c=1280", hw, hw, False, xattn_wide_max_c=1280)
 open(out, "w").write("\n".join(lines) + "\n")
-print(len(lines), "lines,", n_full, "full-text plans,", n_digest, "digest cases, library", L.build_id())
+print(len(lines), "lines,", n_full, "full-text plans,", n_nets, "VAE networks (2 digests each),", n_digest, "digest cases, library",
+      L.build_id())
